@@ -15,11 +15,15 @@ frame is sharded into interleaved 16-row (4-row beyond 4 ranks) stripes (one pro
 packed stripes are gathered to rank 0 over RCCL and de-interleaved there; the
 gather and assembly are inside the timed step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline line (with the
+per-kernel times of the timed steps and, for the headline workload, the stored PMC counters of profiles/counters.json).
+--full adds what takes runs of its own: the counters pass behind the roofline's work-based figures, the extra frames
+(early stop, library default form, elided, corrected sampling, BruteForceTracer, PLOC / SAH trees) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (frame.npy, counts.npy; see dump_outputs).
 """
 import argparse
 import gc
@@ -75,6 +79,28 @@ def trace_alg_bytes(stage):
     return 64 * stage["inner_visits"] + 48 * stage["tri_tests"] + 40 * stage["rays"]
 
 
+COUNT_KEYS = ("rays_primary", "rays_secondary", "samples", "samples_discarded", "passes")  # vmx_stats, summed over ranks
+DUMP_BYTES = 60_000_000  # what --dump-outputs may write of the frame (64 MB in all, with counts and headers)
+
+
+def dump_outputs(out_dir, frame, counts):
+    """--dump-outputs: what a caller of the timed path receives from its last step — the frame [H, W, 5] (RGBAZ, float32)
+    as frame.npy and the vmx_stats counts (COUNT_KEYS, float64) as counts.npy.  A frame larger than DUMP_BYTES is
+    replaced by a fixed, seeded sample of its pixels: frame_sample.npy [n, 5] and their flat indices y * W + x,
+    frame_sample_pixels.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    if frame.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_BYTES // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -85,10 +111,15 @@ def main():
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--scene", default="sponza260k")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-spp", type=int, default=32, help="spp of the bounded CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the counters pass (roofline work figures), the extra frames and the CPU baseline; "
+                         "without it a run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-spp", type=int, default=32, help="spp of the bounded CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline frame (no early-stop frame, no SAH-tree frame): the profiling runs of tools/pmc.sh")
+                    help="--full without the extra frames (no early-stop frame, no SAH-tree frame)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the N>1 path on a box with fewer GPUs than ranks (frames travel through host memory)")
     ap.add_argument("--device", type=int, default=-1, help="force this HIP device for every rank (rehearsal)")
@@ -102,6 +133,7 @@ def main():
     ap.add_argument("--reorder", type=lambda v: int(v, 0), default=0,
                     help="experiment (A/B library only, VMX_LIB=build/libvermilion_hip_ab.so): bounce reordering key, tools/sort_probe.py")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     if args.multi:
         return main_multi(args)
@@ -154,7 +186,7 @@ def main():
 
     exchange = {}  # N > 1: the exchange step of the timed headline steps, apart from the rendering
 
-    def timed(k, exchange_out=None, **kw):
+    def timed(k, exchange_out=None, last_out=None, **kw):
         # (a generation-2 Python garbage collection inside a timed region showed up as +36 ms on the three
         # early-stop frames whenever --steps happened to place it there: collect first, keep it out)
         gc.collect()
@@ -162,10 +194,15 @@ def main():
         times = vdist.ExchangeTimes() if (world > 1 and exchange_out is not None) else None
         sync()
         t0 = time.perf_counter()
-        stats = [step(times=times, **kw)[0] for _ in range(k)]
+        stats = []
+        for _ in range(k):
+            st, frame = step(times=times, **kw)
+            stats.append(st)
         sync()
         dt = time.perf_counter() - t0
         gc.enable()
+        if last_out is not None:  # what the last step handed its caller: the frame (rank 0) and its stats
+            last_out.update(frame=frame, stats=stats[-1])
         rays = float(sum(s["rays_primary"] + s["rays_secondary"] for s in stats))
         if world > 1:
             rdev = dev if args.backend == "nccl" else torch.device("cpu")
@@ -196,17 +233,27 @@ def main():
                 })
         return dt, rays, stats
 
-    # counters pass (instrumented kernels, untimed): algorithmic bytes of this exact frame
-    cst, _ = step(counters=True)
+    # counters pass (instrumented kernels, untimed; --full): algorithmic bytes of this exact frame
+    cst = step(counters=True)[0] if args.full else None
     for _ in range(args.warmup):
         step()
-    dt, rays, stats = timed(args.steps, exchange_out=exchange)
+    last = {}
+    dt, rays, stats = timed(args.steps, exchange_out=exchange, last_out=last)
     ms_per_step = dt / args.steps * 1e3
     value = rays / dt / 1e6
+    if args.dump_outputs:
+        # (before the extra frames of --full render into the same target)
+        counts = np.array([last["stats"][k] for k in COUNT_KEYS], dtype=np.float64)
+        if world > 1:
+            t = torch.tensor(counts, device=dev if args.backend == "nccl" else torch.device("cpu"))
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            counts = t.cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["frame"].cpu().numpy(), counts)
 
     # reference-faithful frame (early stop on, pathtracer.cpp:290-311), same frame otherwise
     es_k = 0
-    if not args.no_extras:
+    if extras:
         step(early_stop=True)
         es_k = max(1, min(args.steps, 3))
         es_dt, es_rays, es_stats = timed(es_k, early_stop=True)
@@ -218,7 +265,7 @@ def main():
     # finish — BVH query, the light spheres' reach test, counted — and hand only the others to k_shade.  Bit-identical
     # frame in less time, but its settled rays are not full RayCasts, so it is a frame time, not the headline's ray rate.
     sorted_info = None
-    if not args.no_extras:
+    if extras:
         _, g0 = step()
         g0 = g0.clone() if g0 is not None else None
         _, g1 = step(pipeline=0)
@@ -240,7 +287,7 @@ def main():
     # (78 % of them under the reference's r2 = 10 U).  Wall-clock per frame is the second half of BASELINE.json's metric;
     # the headline value above stays the default build's, which traces every ray the reference traces.
     el_info = None
-    if not args.no_extras:
+    if extras:
         ELIDE = va.VMX_SAMPLING_PARITY | va.VMX_SAMPLING_ELIDE_DEAD
         same = []
         for es in (False, True):
@@ -270,7 +317,7 @@ def main():
     # `corrected` sampling (r2 = U: a real cosine-weighted lobe, pathtracer.cpp:156,170 with the factor 10 removed):
     # SURVEY 8(d) / BASELINE.md §3 ask for it beside `parity`.  Bounces dominate here (~25 rays per sample).
     corr_info = None
-    if world == 1 and not args.no_extras and args.corrected_spp >= 4:
+    if world == 1 and extras and args.corrected_spp >= 4:
         ccam = va.make_camera(c["position"], c["rotation_deg"], W, H, args.corrected_spp, back_size=(3.6, 3.6 * H / W))
         copts = va.make_opts(seed=args.seed, early_stop=False, sampling=va.VMX_SAMPLING_CORRECTED)
         sc.render_device(ccam, copts, local.data_ptr(), stream)
@@ -294,7 +341,7 @@ def main():
     # §8 f-4: the engine's default integrator on the same scene and camera (BruteForceTracer, most pixels stop after
     # 3 samples): device time of one frame
     bf_info = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         bopts = va.make_opts(seed=args.seed)
         sc.render_bruteforce(cam, bopts)
         _, bst = sc.render_bruteforce(cam, bopts)
@@ -305,7 +352,7 @@ def main():
     # §8 f-1 quality builder (binned SAH, not the reference's topology): same frame, extra figure only
     q_info = None
     cq_info = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         # ... and the same quality from the GPU builder (PLOC): scene creation is then a per-frame operation
         va.Scene(pos, nrm, uv, device=dev_index, builder=va._lib.VMX_BVH_PLOC).close()  # first hipcub launches
         t0 = time.perf_counter()
@@ -408,9 +455,9 @@ def main():
         # what the two traversal kernels had to do in one step (counters pass of this exact frame): the camera-ray
         # kernel traces every depth-0 ray; the first bounce generation (the paths that continue after their first
         # hit) goes through k_trace_w<1>, later generations through the fused tail — the instrumented kernels count
-        # per stage, so the bounce kernel's share is the stage's per-ray averages x its rays
+        # per stage, so the bounce kernel's share is the stage's per-ray averages x its rays (--full only)
         work = {}
-        if world == 1:
+        if world == 1 and cst:
             pr, bo = cst["primary"], cst["bounce"]
             work["trace_camera"] = {"rays": pr["rays"], "inner_visits": pr["inner_visits"], "tri_tests": pr["tri_tests"],
                                     "alg_bytes": trace_alg_bytes(pr), "from": "counters pass, depth-0 stage"}
@@ -481,6 +528,8 @@ def main():
         if not prof:  # no PMC profile for this configuration: say so instead of inventing an issue fraction or a traffic figure
             roof["note"] = ("profiles/counters.json holds no counters for this workload / pipeline form: traffic and issue_frac "
                             "are null, frac is the work-based figure from the live counters pass")
+        if not cst:  # a plain run: live durations and the stored counters only
+            roof["work_note"] = "frac, work and algorithmic come from the counters pass, a run of its own: bench.py --full"
         roof["frac_what"] = ("(inner_visits x A_inner + tri_tests x A_tri) / 64 / launch duration / VALU issue peak: the share of the "
                              "issue roof spent on arithmetic the reference's tests need (bbox.cpp:70-83, bvh.cpp:103-114, "
                              "triangle.cpp:4-54); issue_frac counts every VALU instruction issued")
@@ -509,21 +558,23 @@ def main():
                                  if k != dominant and kms.get(k, 0) > 0}
         # SURVEY §8(d)'s algorithmic bytes, kept as the secondary view: the scene (34 MB) is cache-resident, so
         # HBM is not the roof of this path (measured HBM traffic is `hbm_frac_measured` of peak)
-        cam_bytes = trace_alg_bytes(cst["primary"]) / max(cst["primary"]["launches"], 1)
-        cam_ms = kms["trace_camera"] * args.steps / max(klaunch["trace_camera"], 1) if klaunch.get("trace_camera") else 0
-        roof["algorithmic"] = {
-            "what": "SURVEY 8(d) bytes per ray x rays of the camera-ray launch / its duration, against the 8 TB/s HBM "
-                    "peak: > 1 because the records come from L2 / scalar cache / Infinity Cache, not from HBM",
-            "alg_bytes_per_launch": int(cam_bytes),
-            "alg_GBs": round(cam_bytes / (cam_ms * 1e-3) / 1e9, 1) if cam_ms else None,
-            "alg_frac_of_hbm_peak": round(cam_bytes / (cam_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if cam_ms else None,
-            "alg_bytes_per_ray": round(trace_alg_bytes(cst["primary"]) / max(cst["primary"]["rays"], 1), 1),
-            "alg_bytes_per_ray_whole_path": round(alg_bytes(cst["primary"]) / max(cst["primary"]["rays"], 1), 1),
-            "inner_visits_per_ray": round(cst["primary"]["inner_visits"] / max(cst["primary"]["rays"], 1), 2),
-            "tri_tests_per_ray": round(cst["primary"]["tri_tests"] / max(cst["primary"]["rays"], 1), 2),
-            "bounce_inner_visits_per_ray": round(cst["bounce"]["inner_visits"] / max(cst["bounce"]["rays"], 1), 2),
-            "bounce_tri_tests_per_ray": round(cst["bounce"]["tri_tests"] / max(cst["bounce"]["rays"], 1), 2),
-        }
+        roof["algorithmic"] = None
+        if cst:
+            cam_bytes = trace_alg_bytes(cst["primary"]) / max(cst["primary"]["launches"], 1)
+            cam_ms = kms["trace_camera"] * args.steps / max(klaunch["trace_camera"], 1) if klaunch.get("trace_camera") else 0
+            roof["algorithmic"] = {
+                "what": "SURVEY 8(d) bytes per ray x rays of the camera-ray launch / its duration, against the 8 TB/s HBM "
+                        "peak: > 1 because the records come from L2 / scalar cache / Infinity Cache, not from HBM",
+                "alg_bytes_per_launch": int(cam_bytes),
+                "alg_GBs": round(cam_bytes / (cam_ms * 1e-3) / 1e9, 1) if cam_ms else None,
+                "alg_frac_of_hbm_peak": round(cam_bytes / (cam_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if cam_ms else None,
+                "alg_bytes_per_ray": round(trace_alg_bytes(cst["primary"]) / max(cst["primary"]["rays"], 1), 1),
+                "alg_bytes_per_ray_whole_path": round(alg_bytes(cst["primary"]) / max(cst["primary"]["rays"], 1), 1),
+                "inner_visits_per_ray": round(cst["primary"]["inner_visits"] / max(cst["primary"]["rays"], 1), 2),
+                "tri_tests_per_ray": round(cst["primary"]["tri_tests"] / max(cst["primary"]["rays"], 1), 2),
+                "bounce_inner_visits_per_ray": round(cst["bounce"]["inner_visits"] / max(cst["bounce"]["rays"], 1), 2),
+                "bounce_tri_tests_per_ray": round(cst["bounce"]["tri_tests"] / max(cst["bounce"]["rays"], 1), 2),
+            }
         out = {
             "metric": "Mrays/sec (primary+secondary), 1920x1080 Sponza",
             "value": round(value, 2),
@@ -557,7 +608,7 @@ def main():
                 "device_total": round(sum(s["ms_device"] for s in stats) / args.steps, 3),
             },
             "whole_frame_alg_GBs": round((alg_bytes(cst["primary"]) + alg_bytes(cst["bounce"])) / (ms_per_step * 1e-3) / 1e9, 1)
-            if world == 1 else None,
+            if world == 1 and cst else None,
         }
         if sorted_info and el_info:
             # wall-clock per frame is the second half of BASELINE.json's metric: three bit-identical frames
@@ -599,7 +650,7 @@ def main():
             out["corrected_frame"] = corr_info
         if bf_info:
             out["bruteforce_frame"] = bf_info
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pos, nrm, uv, c, W, H, args.cpu_spp, args.seed)
     # everything this process holds is released before the line goes out, so that nothing of it outlives the line
     sc.close()
@@ -652,13 +703,16 @@ def main_multi(args):
     dt = time.perf_counter() - t0
     gc.enable()
     rays = float(sum(s["rays_primary"] + s["rays_secondary"] for s in stats))
-    es_opts = va.make_opts(seed=args.seed, early_stop=True, stripe_rows=stripe, pipeline=HEADLINE_FORM)
-    ms.render_device(cam, es_opts, frame.data_ptr())
-    sync()
-    t0 = time.perf_counter()
-    es = ms.render_device(cam, es_opts, frame.data_ptr())
-    sync()
-    es_dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame.cpu().numpy(), [float(stats[-1][k]) for k in COUNT_KEYS])
+    if args.full:
+        es_opts = va.make_opts(seed=args.seed, early_stop=True, stripe_rows=stripe, pipeline=HEADLINE_FORM)
+        ms.render_device(cam, es_opts, frame.data_ptr())
+        sync()
+        t0 = time.perf_counter()
+        es = ms.render_device(cam, es_opts, frame.data_ptr())
+        sync()
+        es_dt = time.perf_counter() - t0
     out = {
         "metric": "Mrays/sec (primary+secondary), 1920x1080 Sponza", "value": round(rays / dt / 1e6, 2), "unit": "Mrays/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -690,10 +744,11 @@ def main_multi(args):
                     "device-to-device copy into the root's gather buffer, and on the root's stream around k_assemble; wall_ms is "
                     "the host clock from handing the jobs out to the assembled frame",
         },
-        "reference_frame": {"what": "same frame with the reference's early-stop rule on (pathtracer.cpp:290-311)",
-                            "ms_per_frame": round(es_dt * 1e3, 3),
-                            "Mrays_per_s": round((es["rays_primary"] + es["rays_secondary"]) / es_dt / 1e6, 2)},
     }
+    if args.full:
+        out["reference_frame"] = {"what": "same frame with the reference's early-stop rule on (pathtracer.cpp:290-311)",
+                                  "ms_per_frame": round(es_dt * 1e3, 3),
+                                  "Mrays_per_s": round((es["rays_primary"] + es["rays_secondary"]) / es_dt / 1e6, 2)}
     ms.close()
     del frame
     gc.collect()

@@ -1,31 +1,13 @@
 """The reference-side adapters (vermilion_amd/adapter/*.cpp) are C++ that a Vermilion maintainer
-compiles inside Vermilion.  Here they go through `g++ -std=c++17 -fsyntax-only` against the
-reference's OWN headers (read in place under /root/reference/core) with type-only stand-ins for
-GLM / Assimp (tests/stubs/, see its README): a check that every member the adapters touch
-(Integrator::Render's signature integrators.h:11-16, Camera's fields camera.h:60-104,
-MeshEngine::sceneMeshes / boundTextures meshEngine.h:32-65, pixelValue camera.h:49-58) exists with
-a compatible type.  Skipped where the reference is absent (the GPU box)."""
+compiles inside Vermilion.  Their syntax + type check against Vermilion's own headers needs a Vermilion
+checkout, which the repository does not hold: it is `tools/adapter_check.sh <Vermilion>/core` (type-only
+GLM / Assimp stand-ins in tests/stubs/, see its README).  The mesh walk itself runs in
+tests/test_adapter_flatten.py."""
 import glob
 import os
-import shutil
-import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/core"
 ADAPTERS = sorted(glob.glob(os.path.join(ROOT, "vermilion_amd", "adapter", "*.cpp")))
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present (GPU box)")
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-@pytest.mark.parametrize("src", ADAPTERS, ids=[os.path.basename(a) for a in ADAPTERS])
-def test_adapter_passes_a_syntax_and_type_check_against_the_reference_headers(src):
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Werror",
-           "-I", os.path.join(ROOT, "tests", "stubs"), "-I", REF, "-I", os.path.join(ROOT, "include"),
-           "-I", os.path.join(ROOT, "vermilion_amd", "adapter"), src]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
 
 
 def test_adapters_exist():

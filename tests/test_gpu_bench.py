@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ def check_common(d, n_gpus):
 
 
 def test_single_gpu_line_carries_roofline_cpu_baseline_and_the_extra_frames():
-    d = run([sys.executable, "bench.py"] + SMALL)
+    d = run([sys.executable, "bench.py", "--full"] + SMALL)
     check_common(d, 1)
     assert d["scaling"] in ("weak", "strong")
     # (the PMC counters in profiles/ belong to the 1920x1080x256 frame: on another workload the issue fraction and the
@@ -74,7 +75,7 @@ def test_single_gpu_line_carries_roofline_cpu_baseline_and_the_extra_frames():
 def test_two_ranks_with_the_extra_frames():
     """... and once with the extra frames (early stop, full shading, elision) through the sharded path"""
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-             "--master-port", "29534", "bench.py", "--gpus", "2", "--backend", "gloo", "--device", "0", "--no-cpu-baseline"] + SMALL)
+             "--master-port", "29534", "bench.py", "--gpus", "2", "--backend", "gloo", "--device", "0", "--full", "--no-cpu-baseline"] + SMALL)
     check_common(d, 2)
     assert d["elided_frame"]["frames_bit_identical_to_headline"] is True and d["sorted_frame"]["frame_bit_identical_to_headline"] is True
     x = d["exchange"]  # the exchange step timed apart from the rendering (SURVEY 8e)
@@ -83,7 +84,7 @@ def test_two_ranks_with_the_extra_frames():
 
 
 def test_multi_device_form_in_one_process():
-    d = run([sys.executable, "bench.py", "--multi", "0,0"] + SMALL)
+    d = run([sys.executable, "bench.py", "--multi", "0,0", "--full"] + SMALL)
     check_common(d, 2)
     assert d["config"]["distinct_devices"] == 1 and "vmx_multi" in d["config"]["parallelism"]
     assert d["reference_frame"]["ms_per_frame"] > 0
@@ -101,3 +102,24 @@ def test_two_ranks_under_torch_distributed_run():
     check_common(d, 2)
     assert d["scaling"] == "strong" and d["config"]["parallelism"].startswith("stripes")
     assert d["exchange"]["gather_ms"] > 0 and d["exchange"]["assemble_ms"] > 0
+
+
+def test_plain_line_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """without --full a run times the headline frame and nothing else; --dump-outputs writes that frame, the same bits
+    from run to run"""
+    frames = []
+    for i in range(2):
+        out = tmp_path / str(i)
+        d = run([sys.executable, "bench.py", "--dump-outputs", str(out)] + SMALL)
+        check_common(d, 1)
+        for k in ("cpu_baseline", "reference_frame", "sorted_frame", "elided_frame", "corrected_frame", "bruteforce_frame",
+                  "quality_bvh", "frame_ms"):
+            assert k not in d
+        assert d["roofline"]["frac"] is None and d["roofline"]["algorithmic"] is None and d["whole_frame_alg_GBs"] is None
+        f = np.load(out / "frame.npy")
+        c = np.load(out / "counts.npy")
+        assert f.dtype == np.float32 and f.shape == (360, 640, 5) and np.isfinite(f[..., :3]).all() and f[..., :3].max() > 0
+        assert c.dtype == np.float64 and c[0] + c[1] == d["config"]["rays_per_frame"] and c[0] == 640 * 360 * 64
+        frames.append((f, c))
+    assert np.array_equal(frames[0][0].view(np.uint32), frames[1][0].view(np.uint32))
+    assert np.array_equal(frames[0][1], frames[1][1])

@@ -3,7 +3,7 @@
 //
 // Built as part of Vermilion (add to SOURCE_FILES in CMakeLists.txt and link
 // vermilion_hip).  This repository's image has no GLM/Assimp/OpenImageIO, so here the file only goes
-// through a syntax + type check against the reference's own headers (tests/test_adapter_compiles.py).
+// through a syntax + type check against the reference's own headers (tools/adapter_check.sh).
 //
 // HipPathTracer replaces Vermilion::PathTracer (core/integrators/integrators.h:23-26,
 // core/integrators/pathtracer.cpp:200-328).  Installed exactly like it:
