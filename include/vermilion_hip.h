@@ -269,6 +269,46 @@ int vmx_trace(const vmx_scene *scene, const float *origin, const float *dir, uin
 /* MeshEngine::RayCast (meshEngine.cpp:239-509) */
 int vmx_raycast(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n,
                 vmx_rayhit *out);
+/* ---- device ray queries (explicit ray batches) --------------------------
+ * The query side of the reference's MeshEngine / BVH, served by a persistent traversal kernel (k_query).
+ * Rays: origin[n*3], dir[n*3] f32 packed like vmx_trace; tmax[n] f32 or NULL (no bound).
+ * Outputs (any may be NULL, at least one non-NULL when n > 0): tri_id[n] int32 (createBVH order, -1 = miss),
+ * t[n] f32, hit[n] uint8 (0 / 1).  Spheres are not part of any mode (neither BVH::getIntersection nor
+ * RayCastCollision sees them, meshEngine.cpp:201).
+ *
+ * With L = min(tmax, 999999999.f) (the reference's initial intersection->t, bvh.cpp:48; L = 999999999.f when
+ * tmax is NULL, +inf or larger):
+ *   - a ray with !(tmax > 0) (<= 0 or NaN) is a miss and is not traversed: tri_id -1, t = tmax, hit 0
+ *   - VMX_QUERY_NEAREST: BVH::getIntersection(occlusion == false) with the running nearest distance starting at L
+ *     instead of 999999999.f; same box tests, near-first order, strict `<` tie rule and NaN behaviour.  tri_id,
+ *     t (L on a miss), hit = tri_id >= 0.  So with (id, t) = vmx_trace's result: (t < L ? (id, t) : (-1, L)) —
+ *     except for L a few ulps above t, where a box's slab `near` can exceed the triangle's t and the box is pruned:
+ *     then a miss (-1, L) is possible (never another triangle).
+ *   - VMX_QUERY_ANY: occlusion == true (bvh.cpp:83-86): the first triangle Triangle::getIntersection accepts with
+ *     dist < L ends the ray; nodes with near > L are pruned.  hit only (tri_id or t non-NULL: VMX_ERR_INVALID);
+ *     hit == (vmx_trace's id >= 0 && its t < L).  Known difference: the reference's occlusion mode also accepts
+ *     a triangle beyond 999999999 found in a node it did not prune; that matters only for geometry ~1e9 away.
+ *   - VMX_QUERY_COLLISION: MeshEngine::RayCastCollision (meshEngine.cpp:196-206; public, meshEngine.h:114): NEAREST,
+ *     then hit = tri_id >= 0 && t > 1e-3, the float t compared with the DOUBLE 1e-3 — in float that is
+ *     t >= 1e-3f.  tri_id / t, if asked for, are the nearest hit that was judged.
+ */
+#define VMX_QUERY_NEAREST 0u   /* BVH::getIntersection(occlusion == false), bvh.cpp:47-145              */
+#define VMX_QUERY_ANY 1u       /* occlusion == true (bvh.cpp:83-86): stop at the first accepted triangle   */
+#define VMX_QUERY_COLLISION 2u /* MeshEngine::RayCastCollision (meshEngine.cpp:196-206)                   */
+/* Flag, OR-ed into the mode; tuning only, same results: each lane reads its own 64-byte node / triangle record
+ * instead of the quad-cooperative fetch the kernel uses by default (profiles/query_bench.txt has both). */
+#define VMX_QUERY_FETCH_PER_LANE 0x100u
+/* All pointers are DEVICE memory of the scene's device (checked with hipPointerGetAttributes: anything else is
+ * VMX_ERR_INVALID before any launch).  Enqueued on `stream` (a hipStream_t; NULL = the scene's stream); returns
+ * without synchronising.  The query workspace (work counter, stack overflow slab) is allocated on a scene's first
+ * query and reused: no allocation after that.  Queries of one scene on different streams are ordered by enqueue
+ * (each waits on an event the previous one recorded), so they never share the workspace while in flight. */
+int vmx_query_device(const vmx_scene *scene, uint32_t mode, const void *d_origin, const void *d_dir,
+                     const void *d_tmax, uint32_t n, void *d_tri_id, void *d_t, void *d_hit, void *stream);
+/* Same with HOST buffers: copies in, runs the device path on the scene's stream, copies out, synchronises. */
+int vmx_query(const vmx_scene *scene, uint32_t mode, const float *origin, const float *dir, const float *tmax,
+              uint32_t n, int32_t *tri_id, float *t, uint8_t *hit);
+
 /*
  * Primary-hit AOV: generates sample k's camera ray of every pixel on the
  * device (pathtracer.cpp:251-280) and returns BVH::getIntersection's result,

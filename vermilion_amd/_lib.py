@@ -29,6 +29,10 @@ VMX_BVH_PLOC = 3
 VMX_BF_ABS_INT = 1
 VMX_ROTATION_DEGREES = 0
 VMX_ROTATION_RADIANS = 1
+VMX_QUERY_NEAREST = 0
+VMX_QUERY_ANY = 1
+VMX_QUERY_COLLISION = 2
+VMX_QUERY_FETCH_PER_LANE = 0x100
 
 
 class Sphere(C.Structure):
@@ -171,6 +175,8 @@ SYMBOLS = {
     "vmx_scene_bvh": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "vmx_trace": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     "vmx_raycast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "vmx_query_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "vmx_query": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "vmx_primary_ids": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P]),
     "vmx_radiance": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_trig": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_int]),

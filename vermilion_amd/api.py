@@ -168,6 +168,16 @@ class MeshEngine:
         return ((h["flags"] & 1) != 0, (h["flags"] & 2) != 0, h["location"], h["normal"], h["distance"],
                 h["uv"], h["colour"])
 
+    def RayCastCollision(self, rayStart, rayDirection):
+        """MeshEngine::RayCastCollision (meshEngine.cpp:196-206): does the BVH's nearest hit lie beyond 1e-3?
+        (Spheres are not seen, :201.)  One ray (3 values each) -> bool; [n, 3] arrays -> bool array [n]."""
+        if self.sceneAccelerator is None:
+            raise RuntimeError("RayCastCollision before a scene was loaded")
+        o = np.asarray(rayStart, np.float32)
+        _, _, hit = self.sceneAccelerator.query(o.reshape(-1, 3), np.asarray(rayDirection, np.float32).reshape(-1, 3),
+                                                mode="collision")
+        return bool(hit[0]) if o.ndim == 1 else hit
+
 
 class Integrator:  # integrators.h:11-16
     def Render(self, cameraList, mEng):

@@ -181,6 +181,16 @@ struct vmx_scene {
     uint32_t block = 256;
     float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {1, 1, 1};  // vertex bounds (origin cells of the bounce reordering)
     vmx_timings timings{};  // per-kernel durations of the last render on this scene
+    // device ray queries (vmx_query_device): allocated on the first query, then reused.  `done` is recorded after each
+    // query's kernel and waited on by the next one, whatever its stream: one query at a time uses the workspace
+    struct QueryWs {
+        DevBuf<unsigned int> head;             // work counter of k_query
+        DevBuf<unsigned char> overflow_stack;  // stack levels beyond the LDS part, per wave of the largest grid
+        hipEvent_t done = nullptr;
+        bool recorded = false;
+        uint32_t lds_entries = 0, overflow_entries = 0;
+        uint32_t grid[2][3] = {};              // persistent blocks per [per-lane fetch][mode]
+    } qws;
 };
 
 namespace {
@@ -1245,6 +1255,8 @@ int vmx_scene_destroy(vmx_scene *sc) {
     sc->d_geom.release(), sc->d_attrs.release(), sc->d_spheres.release();
     lbvh_release(sc->lbvh);
     sc->d_tex.release(), sc->d_tex1.release();
+    sc->qws.head.release(), sc->qws.overflow_stack.release();
+    if (sc->qws.done) (void)hipEventDestroy(sc->qws.done);
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
     delete sc;
     return VMX_OK;
@@ -1377,6 +1389,148 @@ int vmx_raycast(const vmx_scene *csc, const float *origin, const float *dir, uin
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     d_o.release(), d_d.release(), d_out.release();
     if (e != hipSuccess) return fail(VMX_ERR_HIP, std::string("vmx_raycast: ") + hipGetErrorString(e));
+    return VMX_OK;
+}
+
+// ---- device ray queries (k_query, vmx_query.inc) -------------------------------------------------------
+namespace {
+
+constexpr uint32_t kQueryBlock = 256;
+constexpr uint32_t kQueryModeMask = 0xFFu;
+
+// argument checks that need no device: mode, rays, the output set (in this order, so that each can be seen alone)
+int query_args(const vmx_scene *sc, uint32_t mode, const void *o, const void *d, uint32_t n, const void *tri_id,
+               const void *t, const void *hit) {
+    if ((mode & ~(kQueryModeMask | VMX_QUERY_FETCH_PER_LANE)) || (mode & kQueryModeMask) > VMX_QUERY_COLLISION)
+        return fail(VMX_ERR_INVALID, "unknown query mode");
+    if (n > 0 && (!o || !d)) return fail(VMX_ERR_INVALID, "NULL rays");
+    if (n > 0 && !tri_id && !t && !hit) return fail(VMX_ERR_INVALID, "no output: tri_id, t and hit are all NULL");
+    if ((mode & kQueryModeMask) == VMX_QUERY_ANY && (tri_id || t))
+        return fail(VMX_ERR_INVALID, "VMX_QUERY_ANY returns hit only: tri_id and t must be NULL");
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    return VMX_OK;
+}
+
+// `p` must be device memory of `device`: a host pointer handed to the kernel would fault the GPU
+int check_device_ptr(const void *p, int device, const char *what) {
+    if (!p) return VMX_OK;
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof(a));
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (an unknown pointer sets the thread's error state)
+        return fail(VMX_ERR_INVALID, std::string(what) + " is not device memory");
+    }
+    if (a.type != hipMemoryTypeDevice) return fail(VMX_ERR_INVALID, std::string(what) + " is not device memory");
+    if (a.device != device) return fail(VMX_ERR_INVALID, std::string(what) + " is memory of another device");
+    return VMX_OK;
+}
+
+// first query of a scene: launch shapes from the occupancy of each instantiation, work counter, overflow slab, event
+int ensure_query_ws(vmx_scene *sc) {
+    auto &q = sc->qws;
+    if (q.done) return VMX_OK;
+    // stack levels in LDS: the bounce kernel's 9 (make_tuning); deeper levels go to the slab
+    q.lds_entries = std::min(sc->dev.stack_entries, 9u);
+    q.overflow_entries = sc->dev.stack_entries + 1 > q.lds_entries ? sc->dev.stack_entries + 1 - q.lds_entries : 1u;
+    const uint32_t lds = (kQueryBlock / 64) * (q.lds_entries + 1) * 512;
+    uint32_t max_grid = 1;
+    for (int pl = 0; pl < 2; ++pl)
+        for (uint32_t m = 0; m <= VMX_QUERY_COLLISION; ++m) {
+            int b = 0;
+            HIP_TRY((hipError_t)query_query_blocks_per_cu(kQueryBlock, lds, m, pl == 0, &b));
+            q.grid[pl][m] = (uint32_t)sc->num_cus * (uint32_t)std::max(b, 1);
+            max_grid = std::max(max_grid, q.grid[pl][m]);
+        }
+    if (q.head.ensure(32) || q.overflow_stack.ensure((size_t)max_grid * (kQueryBlock / 64) * q.overflow_entries * 64 * 8))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the query workspace");
+    HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    return VMX_OK;
+}
+
+// enqueues one query on `s`; the caller holds sc->mu and has checked the arguments
+int query_enqueue(vmx_scene *sc, uint32_t mode, const float *o, const float *d, const float *tmax, uint32_t n,
+                  int32_t *tri_id, float *t, uint8_t *hit, hipStream_t s) {
+    if (int rc = ensure_query_ws(sc)) return rc;
+    auto &w = sc->qws;
+    const uint32_t m = mode & kQueryModeMask;
+    const bool quad = (mode & VMX_QUERY_FETCH_PER_LANE) == 0;
+    QueryDev q{};
+    q.o = o, q.d = d, q.tmax = tmax, q.n = n;
+    q.tri_id = tri_id, q.t = t, q.hit = hit;
+    q.head = w.head.p;
+    q.lds_entries = w.lds_entries, q.overflow_entries = w.overflow_entries;
+    q.overflow_stack = w.overflow_stack.p;
+    // refill as soon as 8 lanes are idle: the bounce kernel's setting for incoherent rays (make_tuning)
+    q.refill_min = 8;
+    LaunchCfg cfg;
+    cfg.block = kQueryBlock;
+    cfg.lds_bytes = (kQueryBlock / 64) * (w.lds_entries + 1) * 512;
+    cfg.grid = (uint32_t)std::min<uint64_t>(w.grid[quad ? 0 : 1][m], std::max<uint64_t>(1, ((uint64_t)n + kQueryBlock - 1) / kQueryBlock));
+    // reservation per atomic: WorkDev::reserve's rule (bind_stack)
+    const uint64_t per_lane = n / ((uint64_t)cfg.grid * kQueryBlock);
+    q.reserve = per_lane >= 256 ? 256u : (per_lane >= 64 ? 128u : 64u);
+    if (w.recorded) HIP_TRY(hipStreamWaitEvent(s, w.done, 0));
+    HIP_TRY(hipMemsetAsync(w.head.p, 0, sizeof(unsigned int), s));
+    LAUNCH_TRY(launch_query(sc->dev, q, m, quad, cfg, s));
+    HIP_TRY(hipEventRecord(w.done, s));
+    w.recorded = true;
+    return VMX_OK;
+}
+
+}  // namespace
+
+int vmx_query_device(const vmx_scene *csc, uint32_t mode, const void *d_origin, const void *d_dir, const void *d_tmax,
+                     uint32_t n, void *d_tri_id, void *d_t, void *d_hit, void *stream) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (int rc = query_args(sc, mode, d_origin, d_dir, n, d_tri_id, d_t, d_hit)) return rc;
+    if (n == 0) return VMX_OK;
+    if (n > 0x7FFFFFFFu) return fail(VMX_ERR_INVALID, "more than 2^31 - 1 rays");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    const void *ptrs[6] = {d_origin, d_dir, d_tmax, d_tri_id, d_t, d_hit};
+    const char *names[6] = {"origin", "dir", "tmax", "tri_id", "t", "hit"};
+    for (int i = 0; i < 6; ++i)
+        if (int rc = check_device_ptr(ptrs[i], sc->device, names[i])) return rc;
+    return query_enqueue(sc, mode, (const float *)d_origin, (const float *)d_dir, (const float *)d_tmax, n,
+                         (int32_t *)d_tri_id, (float *)d_t, (uint8_t *)d_hit, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int vmx_query(const vmx_scene *csc, uint32_t mode, const float *origin, const float *dir, const float *tmax, uint32_t n,
+              int32_t *tri_id, float *t, uint8_t *hit) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (int rc = query_args(sc, mode, origin, dir, n, tri_id, t, hit)) return rc;
+    if (n == 0) return VMX_OK;
+    if (n > 0x7FFFFFFFu) return fail(VMX_ERR_INVALID, "more than 2^31 - 1 rays");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    DevBuf<float> d_o, d_d, d_tmax, d_t;
+    DevBuf<int32_t> d_id;
+    DevBuf<uint8_t> d_hit;
+    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || (tmax && d_tmax.ensure(n)) || (t && d_t.ensure(n)) ||
+        (tri_id && d_id.ensure(n)) || (hit && d_hit.ensure(n)))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the ray batch");
+    hipStream_t s = sc->stream;
+    auto cleanup = [&]() { d_o.release(), d_d.release(), d_tmax.release(), d_t.release(), d_id.release(), d_hit.release(); };
+    hipError_t e = hipMemcpyAsync(d_o.p, origin, (size_t)n * 12, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d.p, dir, (size_t)n * 12, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax.p, tmax, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(VMX_ERR_HIP, std::string("vmx_query: ") + hipGetErrorString(e));
+    }
+    int rc = query_enqueue(sc, mode, d_o.p, d_d.p, tmax ? d_tmax.p : nullptr, n, tri_id ? d_id.p : nullptr,
+                           t ? d_t.p : nullptr, hit ? d_hit.p : nullptr, s);
+    if (rc == VMX_OK) {
+        if (tri_id) e = hipMemcpyAsync(tri_id, d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && t) e = hipMemcpyAsync(t, d_t.p, (size_t)n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && hit) e = hipMemcpyAsync(hit, d_hit.p, n, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t es = hipStreamSynchronize(s);  // (also before the buffers are freed when the enqueue failed)
+    cleanup();
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(VMX_ERR_HIP, std::string("vmx_query: ") + hipGetErrorString(e));
     return VMX_OK;
 }
 

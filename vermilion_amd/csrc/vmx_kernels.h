@@ -94,6 +94,23 @@ struct WorkDev {
     const void *cam_tris;   // float4[ntris * 4]
 };
 
+// explicit ray batch of k_query (vmx_query.inc): device pointers, any output may be NULL
+struct QueryDev {
+    const float *o, *d;     // [n*3] origins / directions
+    const float *tmax;      // [n] or NULL (no bound: 999999999.f, bvh.cpp:48)
+    uint32_t n;
+    uint32_t reserve;       // ray indices a wave reserves per atomic on `head` (multiple of 64)
+    uint32_t refill_min;    // refill when this many lanes of a wave are idle
+    uint32_t lds_entries;   // stack levels kept in LDS
+    uint32_t overflow_entries;  // deeper levels, in the global slab below (64 lanes x 8 B each)
+    uint32_t pad;
+    void *overflow_stack;   // uint2[waves][overflow_entries][64]
+    unsigned int *head;     // work counter, zeroed before the launch
+    int32_t *tri_id;
+    float *t;
+    uint8_t *hit;
+};
+
 struct LaunchCfg {
     uint32_t grid;            // persistent blocks
     uint32_t block;           // threads per block (multiple of 64)
@@ -107,6 +124,10 @@ int launch_raycast(const SceneDev &sc, const float *o, const float *d, uint32_t 
                    LaunchCfg cfg, void *stream);
 int launch_primary_ids(const SceneDev &sc, const FrameDev &fr, uint32_t k, int32_t *tri_id, float *t,
                        LaunchCfg cfg, void *stream);
+
+// device ray queries (vmx_query.inc): mode = VMX_QUERY_NEAREST / _ANY / _COLLISION; quad: quad-cooperative record fetch
+int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream);
+int query_query_blocks_per_cu(uint32_t block, uint32_t lds_bytes, uint32_t mode, bool quad, int *blocks);
 
 int launch_trig(const float *x, uint32_t n, float *cs, float *sn, void *stream);
 

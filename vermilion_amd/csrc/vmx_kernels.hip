@@ -17,6 +17,7 @@
 //   k_paths        traversal + shading fused, paths kept to their end (small passes, the tail of a pass)
 //   k_resolve      per-pixel accumulation, early stop, pixel write (pathtracer.cpp:282-324)
 //   k_bruteforce*  BruteForceTracer::Render                        (integrators.cpp:9-186)
+//   k_query        device ray queries: nearest hit with a bound, any hit, RayCastCollision (vmx_query.inc)
 // (the first-generation kernels k_primary / k_bounce live in vmx_kernels_ab.inc: A/B library only)
 //
 // Execution model: persistent blocks stride over block-sized work items; the
@@ -3649,6 +3650,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
     hipLaunchKernelGGL(k_quantize, dim3(grid), dim3(256), 0, (hipStream_t)stream, frame, npix, (uchar4 *)rgba8, depth);
     return launch_status();
 }
+
+// device ray queries of explicit batches: k_query<MODE> + launch_query
+#include "vmx_query.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

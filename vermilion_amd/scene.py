@@ -9,6 +9,10 @@ import numpy as np
 from . import _lib as L
 
 
+def _is_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
+
+
 def _f32(a, shape_last=None):
     a = np.ascontiguousarray(a, dtype=np.float32)
     if shape_last is not None and (a.ndim == 0 or a.shape[-1] != shape_last):
@@ -169,6 +173,86 @@ class Scene:
         out = np.zeros(n, dtype=RAYHIT_DTYPE)
         self._check(self._lib.vmx_raycast(self._h, o.ctypes.data, d.ctypes.data, n, out.ctypes.data))
         return out
+
+    # -- ray queries -----------------------------------------------------------
+    QUERY_MODES = {"nearest": L.VMX_QUERY_NEAREST, "any": L.VMX_QUERY_ANY, "collision": L.VMX_QUERY_COLLISION}
+
+    def query(self, origin, direction, tmax=None, mode="nearest", stream=None, per_lane_fetch=False):
+        """Ray queries of a batch (vmx_query / vmx_query_device; semantics in include/vermilion_hip.h):
+        "nearest" -> (tri_id, t, hit), "collision" -> (tri_id, t, hit) with hit = MeshEngine::RayCastCollision,
+        "any" -> hit.  tmax: per-ray bound or None.
+
+        numpy in -> the host entry, numpy out (int32, float32, bool).  torch tensors on this scene's device
+        in -> the device entry on `stream` (default torch.cuda.current_stream()), tensors out (int32, float32,
+        torch.bool), nothing synchronised.  Device rays must be contiguous float32 [n, 3] (tmax [n]): anything
+        else is a ValueError, never a copy through the host.  per_lane_fetch: VMX_QUERY_FETCH_PER_LANE (tuning)."""
+        if mode not in self.QUERY_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.QUERY_MODES)}")
+        m = self.QUERY_MODES[mode] | (L.VMX_QUERY_FETCH_PER_LANE if per_lane_fetch else 0)
+        want_ids = mode != "any"
+        if _is_tensor(origin) or _is_tensor(direction) or _is_tensor(tmax):
+            return self._query_device(origin, direction, tmax, m, want_ids, stream)
+        o, d = _f32(origin, 3), _f32(direction, 3)
+        if o.shape != d.shape:
+            raise ValueError("origin and direction must both be [n, 3]")
+        n = o.shape[0]
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if tm.shape[0] != n:
+                raise ValueError("tmax must hold one value per ray")
+        hit = np.zeros(n, np.uint8)
+        tri = np.empty(n, np.int32) if want_ids else None
+        t = np.empty(n, np.float32) if want_ids else None
+        self._check(self._lib.vmx_query(self._h, m, o.ctypes.data, d.ctypes.data, None if tm is None else tm.ctypes.data,
+                                        n, None if tri is None else tri.ctypes.data, None if t is None else t.ctypes.data,
+                                        hit.ctypes.data))
+        hit = hit.view(np.bool_)
+        return (tri, t, hit) if want_ids else hit
+
+    def _query_device(self, origin, direction, tmax, m, want_ids, stream):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def rays(x, name, last):
+            if not _is_tensor(x):
+                raise ValueError(f"{name}: mix of torch tensors and other arrays")
+            if x.device != dev:
+                raise ValueError(f"{name} must be on {dev} (got {x.device})")
+            if x.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32 (got {x.dtype})")
+            if not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if last and (x.dim() != 2 or x.shape[1] != 3):
+                raise ValueError(f"{name} must be [n, 3]")
+            return x
+
+        o, d = rays(origin, "origin", True), rays(direction, "direction", True)
+        if o.shape != d.shape:
+            raise ValueError("origin and direction must both be [n, 3]")
+        n = o.shape[0]
+        tm = None
+        if tmax is not None:
+            tm = rays(tmax, "tmax", False)
+            if tm.dim() != 1 or tm.shape[0] != n:
+                raise ValueError("tmax must be [n]")
+        hit = torch.empty(n, dtype=torch.bool, device=dev)
+        tri = torch.empty(n, dtype=torch.int32, device=dev) if want_ids else None
+        t = torch.empty(n, dtype=torch.float32, device=dev) if want_ids else None
+        if n:
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            # torch's default stream is the legacy NULL stream, which the ABI reads as "the scene's own stream": run
+            # the query on a side stream ordered after `s`, and `s` after it
+            side = torch.cuda.Stream(dev) if s.cuda_stream == 0 else None
+            run = side if side is not None else s
+            if side is not None:
+                side.wait_stream(s)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+            self._check(self._lib.vmx_query_device(self._h, m, ptr(o), ptr(d), ptr(tm), n, ptr(tri), ptr(t), ptr(hit),
+                                                   C.c_void_p(run.cuda_stream)))
+            if side is not None:
+                s.wait_stream(side)
+        return (tri, t, hit) if want_ids else hit
 
     def primary_ids(self, cam, opts, k=0):
         n = cam.image_res[0] * cam.image_res[1]
