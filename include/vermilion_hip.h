@@ -262,6 +262,46 @@ int vmx_scene_timings(const vmx_scene *scene, vmx_timings *out);
 int vmx_scene_bvh(const vmx_scene *scene, uint32_t *start, uint32_t *nprims,
                   uint32_t *right_offset, float *bbox, uint32_t *prim_order);
 
+/* ---- moving geometry: in-place updates ----------------------------------
+ * New positions, normals and / or uvs for the SAME triangles: pos / nrm [ntris*9], uv [ntris*6], in the createBVH
+ * order of the scene's creation (triangle IDs keep their meaning); ntris must be the scene's count (another count or
+ * order is a new scene).  Each of pos / nrm / uv may be NULL, which KEEPS that attribute — unlike creation, where a
+ * NULL uv means zeros; all three NULL is VMX_ERR_INVALID.  Updating only nrm / uv does no box work.
+ *
+ * VMX_UPDATE_REFIT: the tree's nodes, leaves and prim_order stay; every box becomes the tight union of its triangles'
+ *   new vertices, and the triangle / attribute records are rewritten with the float operations of a fresh build (a
+ *   rewritten record is bit-identical to the one a build writes for that triangle).  The scene then behaves exactly
+ *   like the OLD topology with tight boxes over the new positions.  A refitted VMX_BVH_REFERENCE tree is therefore no
+ *   longer the reference's topology for the new positions: its parity bar becomes that of SAH / LBVH / PLOC — the
+ *   reference's traversal over the exported tree.  Boxes loosen as vertices move: see VMX_UPDATE_REBUILD.
+ * VMX_UPDATE_REBUILD: runs the scene's own builder again on the new positions, in place: export and frames are
+ *   bit-identical to a fresh vmx_scene_create_ex on the same arrays.  Built into new buffers that replace the old ones
+ *   only when the build succeeds; everything sized from the tree's depth (stack entries, block size, the render and
+ *   query workspaces' overflow stacks) follows.
+ *
+ * A failed update leaves the scene exactly as it was: non-finite positions (host variant), a wrong ntris, unknown
+ * flags, a REBUILD whose tree exceeds the 64-entry stack (VMX_ERR_DEPTH).
+ *
+ * Ordering: an update waits for the scene's last query before it writes a record.  Every later render (path tracer and
+ * BruteForceTracer), query, parity hook and flat export of the scene waits for the update, whatever stream either runs
+ * on.  vmx_scene_bvh / vmx_scene_describe report the refitted boxes (topology arrays and prim_order unchanged).
+ */
+#define VMX_UPDATE_REFIT 0u   /* keep the tree's topology, recompute every box from the new positions */
+#define VMX_UPDATE_REBUILD 1u /* run the scene's own builder again on the new positions, in place      */
+/* HOST arrays; returns once the scene is updated.  Positions are checked as vmx_scene_create checks them.  The first
+ * update that moves vertices derives the refit plan from the tree (creation time and memory are unchanged); the host
+ * variant keeps a device staging buffer of ntris * 96 bytes after its first call. */
+int vmx_scene_update(vmx_scene *scene, const float *pos, const float *nrm, const float *uv, uint32_t ntris,
+                     uint32_t flags);
+/* DEVICE arrays of the scene's device (checked as vmx_query_device checks its pointers), enqueued on `stream` (a
+ * hipStream_t; NULL = the scene's stream).  Positions are not validated: finite positions are the caller's
+ * precondition.  A REFIT returns without synchronising (except the scene's first, which derives the refit plan); the
+ * arrays must stay valid until it completes on `stream`.  VMX_UPDATE_REBUILD is accepted for VMX_BVH_LBVH / _PLOC
+ * only (the device builders read the arrays where they are) and blocks: the depth check needs the root's height on
+ * the host.  For VMX_BVH_REFERENCE / _SAH it is VMX_ERR_INVALID: use vmx_scene_update. */
+int vmx_scene_update_device(vmx_scene *scene, const void *d_pos, const void *d_nrm, const void *d_uv, uint32_t ntris,
+                            uint32_t flags, void *stream);
+
 /* ---- parity hooks (explicit ray batches, host buffers) ----------------- */
 /* BVH::getIntersection (bvh.cpp:47-145): tri_id[n] (-1 = miss), t[n] */
 int vmx_trace(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n,
@@ -387,6 +427,9 @@ typedef struct vmx_multi_times {
 } vmx_multi_times;
 int vmx_multi_timings(const vmx_multi *m, vmx_multi_times *out, double *render_ms, double *copy_ms);
 int vmx_multi_bind_texture(vmx_multi *m, const float *data, uint32_t width, uint32_t height, uint32_t channels);
+/* vmx_scene_update on every replica (HOST arrays).  Host builders with VMX_UPDATE_REBUILD: one host build, uploaded to
+ * each device; device builders build on each device.  The frame is bit-identical to one scene updated the same way. */
+int vmx_multi_update(vmx_multi *m, const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t flags);
 /* whole frame (W*H*5 floats) into a caller-owned HOST buffer / into DEVICE memory on devices[0];
  * stats: rays and samples summed over the devices, times = the slowest device's */
 int vmx_multi_render(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats);

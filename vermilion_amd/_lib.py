@@ -33,6 +33,8 @@ VMX_QUERY_NEAREST = 0
 VMX_QUERY_ANY = 1
 VMX_QUERY_COLLISION = 2
 VMX_QUERY_FETCH_PER_LANE = 0x100
+VMX_UPDATE_REFIT = 0
+VMX_UPDATE_REBUILD = 1
 
 
 class Sphere(C.Structure):
@@ -173,6 +175,8 @@ SYMBOLS = {
     "vmx_scene_describe": (C.c_int, [_P, C.POINTER(SceneDesc)]),
     "vmx_scene_timings": (C.c_int, [_P, C.POINTER(Timings)]),
     "vmx_scene_bvh": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "vmx_scene_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
+    "vmx_scene_update_device": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     "vmx_trace": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     "vmx_raycast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "vmx_query_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
@@ -193,6 +197,7 @@ SYMBOLS = {
     "vmx_multi_routes": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vmx_multi_timings": (C.c_int, [_P, C.POINTER(MultiTimes), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vmx_multi_bind_texture": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "vmx_multi_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
     "vmx_multi_render": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P,

@@ -54,6 +54,10 @@ bool build_bvh_lbvh_device(const float *pos, const float *nrm, const float *uv, 
 // the same product from parallel locally-ordered clustering (PLOC): a quality tree, also built entirely on the GPU
 bool build_bvh_ploc_device(const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t leaf_size,
                            int device, LbvhDevice &out, std::string &err);
+// either build (ploc) from inputs that are already device memory of `device`, on `stream` (an in-place REBUILD): read
+// where they are, not copied; positions are not validated (finite positions are the caller's precondition)
+bool build_bvh_device_inputs(const float *d_pos, const float *d_nrm, const float *d_uv, uint32_t ntris, uint32_t leaf_size,
+                             int device, bool ploc, void *stream, LbvhDevice &out, std::string &err);
 // reference flat layout (start / nprims / right_offset / bbox / prim_order, n_leaves, max_depth) of such a tree
 bool lbvh_export_flat(const LbvhDevice &d, int device, HostBvh &out, std::string &err);
 void lbvh_release(LbvhDevice &d);

@@ -421,9 +421,19 @@ void lbvh_release(LbvhDevice &d) {
 // InnerRecord / TriRecord / AttrRecord emission.  Nothing comes back to the host except the root's height
 // (for the traversal stack depth); the hierarchy arrays stay in `out.arena` for lbvh_export_flat, everything else
 // the build needed is released before it returns.
+// dev_in: pos / nrm / uv are already device memory of `device` (an in-place REBUILD): they are read where they are, not
+// copied, and not validated on the host.  The build runs on `stream`.
 static bool build_device(const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t leaf_size,
-                         int device, bool ploc, LbvhDevice &out, std::string &err) {
-    if (!check_bvh_input(pos, nrm, ntris, leaf_size, err)) return false;
+                         int device, bool ploc, bool dev_in, hipStream_t stream, LbvhDevice &out, std::string &err) {
+    if (dev_in) {
+        if (!pos || !nrm || ntris == 0 || ntris > kMaxTris || leaf_size > kMaxLeafSize) {
+            err = "LBVH builder: bad device input";
+            return false;
+        }
+        if (leaf_size == 0) leaf_size = 4;
+    } else if (!check_bvh_input(pos, nrm, ntris, leaf_size, err)) {
+        return false;
+    }
     const int n = (int)ntris;
     const size_t ni = n > 1 ? (size_t)n - 1 : 1;
     LB_TRY(hipSetDevice(device));
@@ -436,7 +446,7 @@ static bool build_device(const float *pos, const float *nrm, const float *uv, ui
     // lbvh_export_flat (68 B per triangle, counted in vmx_scene_desc.device_bytes); `scratch` holds the input copies,
     // keys, sort / scan temporaries and the PLOC cluster buffers (250-400 B per triangle) and is freed when the
     // records have been written
-    const size_t in_floats = (size_t)n * (uv ? 24 : 18);
+    const size_t in_floats = dev_in ? 0 : (size_t)n * (uv ? 24 : 18);
     size_t arena_bytes = 0, scratch_bytes = 0;
     auto keep = [&](size_t bytes) { arena_bytes += (bytes + 255) & ~(size_t)255; };
     auto add = [&](size_t bytes) { scratch_bytes += (bytes + 255) & ~(size_t)255; };
@@ -467,7 +477,8 @@ static bool build_device(const float *pos, const float *nrm, const float *uv, ui
     out.first = carve<uint32_t>(kcur, ni), out.last = carve<uint32_t>(kcur, ni);
     out.leaf_box = carve<float>(kcur, (size_t)n * 6), out.node_box = carve<float>(kcur, ni * 6);
     float *d_in = carve<float>(cur, in_floats);
-    float *d_pos = d_in, *d_nrm = d_in + (size_t)n * 9, *d_uv = uv ? d_in + (size_t)n * 18 : nullptr;
+    const float *d_pos = dev_in ? pos : d_in, *d_nrm = dev_in ? nrm : d_in + (size_t)n * 9;
+    const float *d_uv = dev_in ? uv : (uv ? d_in + (size_t)n * 18 : nullptr);
     unsigned long long *d_keys = carve<unsigned long long>(cur, n), *d_keys2 = carve<unsigned long long>(cur, n);
     uint32_t *d_ids = carve<uint32_t>(cur, n);
     uint32_t *d_pint = carve<uint32_t>(cur, ni), *d_height = carve<uint32_t>(cur, ni);
@@ -485,10 +496,12 @@ static bool build_device(const float *pos, const float *nrm, const float *uv, ui
     LB_TRY(hipMalloc(&out.attrs, (size_t)n * sizeof(AttrRecord)));
     out.geom_bytes = inner_bytes + tri_bytes + 64, out.tri_off = (uint32_t)inner_bytes;
 
-    hipStream_t s = 0;
-    LB_TRY(hipMemcpyAsync(d_pos, pos, (size_t)n * 36, hipMemcpyHostToDevice, s));
-    LB_TRY(hipMemcpyAsync(d_nrm, nrm, (size_t)n * 36, hipMemcpyHostToDevice, s));
-    if (uv) LB_TRY(hipMemcpyAsync(d_uv, uv, (size_t)n * 24, hipMemcpyHostToDevice, s));
+    hipStream_t s = stream;
+    if (!dev_in) {
+        LB_TRY(hipMemcpyAsync(d_in, pos, (size_t)n * 36, hipMemcpyHostToDevice, s));
+        LB_TRY(hipMemcpyAsync(d_in + (size_t)n * 9, nrm, (size_t)n * 36, hipMemcpyHostToDevice, s));
+        if (uv) LB_TRY(hipMemcpyAsync(d_in + (size_t)n * 18, uv, (size_t)n * 24, hipMemcpyHostToDevice, s));
+    }
     LB_TRY(hipMemsetAsync(d_arr, 0, ni * 4, s));
     LB_TRY(hipMemsetAsync(d_height, 0, ni * 4, s));
     LB_TRY(hipMemsetAsync((unsigned char *)out.geom + inner_bytes + tri_bytes, 0, 64, s));
@@ -570,11 +583,15 @@ static bool build_device(const float *pos, const float *nrm, const float *uv, ui
 
 bool build_bvh_lbvh_device(const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t leaf_size,
                            int device, LbvhDevice &out, std::string &err) {
-    return build_device(pos, nrm, uv, ntris, leaf_size, device, false, out, err);
+    return build_device(pos, nrm, uv, ntris, leaf_size, device, false, false, 0, out, err);
 }
 bool build_bvh_ploc_device(const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t leaf_size,
                            int device, LbvhDevice &out, std::string &err) {
-    return build_device(pos, nrm, uv, ntris, leaf_size, device, true, out, err);
+    return build_device(pos, nrm, uv, ntris, leaf_size, device, true, false, 0, out, err);
+}
+bool build_bvh_device_inputs(const float *d_pos, const float *d_nrm, const float *d_uv, uint32_t ntris, uint32_t leaf_size,
+                             int device, bool ploc, void *stream, LbvhDevice &out, std::string &err) {
+    return build_device(d_pos, d_nrm, d_uv, ntris, leaf_size, device, ploc, true, (hipStream_t)stream, out, err);
 }
 
 // The reference's flat layout (bvh.h:11-14) of a device-built tree, for vmx_scene_bvh / vmx_scene_describe:

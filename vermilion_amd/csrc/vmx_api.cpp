@@ -162,7 +162,9 @@ struct vmx_scene {
     HostBvh bvh;        // host-built trees: flat layout + device records; device-built (LBVH): filled on demand
     LbvhDevice lbvh;    // VMX_BVH_LBVH: the tree was built and flattened on the device (lbvh_build.hip)
     bool device_built = false;
+    uint32_t builder = VMX_BVH_REFERENCE;  // what vmx_scene_update's VMX_UPDATE_REBUILD runs again
     std::atomic<bool> flat_ready{true};
+    bool flat_topology = true;  // bvh.start / nprims / right_offset / prim_order hold the current tree (device-built: on demand)
     uint32_t n_inner = 0;  // inner record slots on the device
     uint32_t ntris = 0, leaf_size = 4;
     std::vector<vmx_sphere> spheres;
@@ -190,7 +192,22 @@ struct vmx_scene {
         bool recorded = false;
         uint32_t lds_entries = 0, overflow_entries = 0;
         uint32_t grid[2][3] = {};              // persistent blocks per [per-lane fetch][mode]
+        uint32_t stack_entries = 0;            // the tree depth the slab was sized for (a REBUILD can change it)
     } qws;
+    // in-place geometry updates (vmx_scene_update*): `done` is recorded after each update and waited on by every later
+    // render, query and export of the scene, whatever its stream.  The refit plan is built on the first update that
+    // moves vertices (scene creation is unchanged) and dropped by a REBUILD.
+    struct UpdateState {
+        hipEvent_t done = nullptr;
+        bool recorded = false;
+        bool plan_ready = false;
+        bool refitted = false;      // boxes differ from the builder's: the flat export's bbox comes from the records
+        bool bounds_stale = false;  // bounds_lo / bounds_hi are root_box (a device REFIT does not wait for it)
+        DevBuf<unsigned char> plan;                // RefitItem[], deepest tree level first
+        std::vector<std::pair<uint32_t, uint32_t>> levels;  // (first entry, entries) per launch
+        DevBuf<float> root_box;                    // [6] the root's box (no record holds it)
+        DevBuf<float> scratch;                     // host-variant uploads and REBUILD inputs: pos | nrm | uv
+    } upd;
 };
 
 namespace {
@@ -279,6 +296,13 @@ int make_frame(const vmx_camera &cam, const vmx_opts &o, FrameDev &fr) {
 
 int bind_device(const vmx_scene *sc) {
     HIP_TRY(hipSetDevice(sc->device));
+    return VMX_OK;
+}
+
+// work on a scene waits on its last geometry update (vmx_scene_update*), whatever stream that ran on; nothing is
+// enqueued before a scene's first update
+int wait_update(const vmx_scene *sc, hipStream_t s) {
+    if (sc->upd.recorded) HIP_TRY(hipStreamWaitEvent(s, sc->upd.done, 0));
     return VMX_OK;
 }
 
@@ -531,6 +555,13 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
             if (ws.sort_keys[0].ensure(qsize) || ws.sort_keys[1].ensure(qsize) || ws.ids_sorted.ensure(qsize) ||
                 ws.sort_tmp.ensure(tmp_bytes))
                 return fail(VMX_ERR_NOMEM, "hipMalloc failed for the path sort");
+            if (sc->upd.bounds_stale) {  // after a device REFIT: the root's box, written by the refit
+                float rb[6];
+                HIP_TRY(hipMemcpyAsync(rb, sc->upd.root_box.p, sizeof(rb), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                for (int a = 0; a < 3; ++a) sc->bounds_lo[a] = rb[a], sc->bounds_hi[a] = rb[3 + a];
+                sc->upd.bounds_stale = false;
+            }
             SortKeyCfg kc;
             for (int a = 0; a < 3; ++a) {
                 kc.lo[a] = sc->bounds_lo[a];
@@ -692,6 +723,7 @@ int render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, floa
     FrameDev fr;
     int rc = make_frame(*cam, *opts, fr);
     if (rc) return rc;
+    if ((rc = wait_update(sc, s))) return rc;
     Workspace &ws = sc->ws;
     const uint32_t W = fr.width, rows = fr.local_rows;
     const uint32_t npix = W * rows;
@@ -1122,6 +1154,49 @@ int vmx_scene_create(const float *pos, const float *nrm, const float *uv, uint32
     return vmx_scene_create_ex(pos, nrm, uv, ntris, spheres, nspheres, leaf_size, VMX_BVH_REFERENCE, device, out);
 }
 
+// the device records of a host-built tree, into `geom` (inner records, then the triangle records) and `attrs`
+static int upload_records(const HostBvh &b, DevBuf<unsigned char> &geom, DevBuf<AttrRecord> &attrs) {
+    const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
+    const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
+    // + 64: the quad-cooperative fetch reads 64 bytes from a 48-byte triangle record's start
+    if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "scene too large for 32-bit record offsets");
+    if (geom.ensure(inner_bytes + tri_bytes + 64) || attrs.ensure(b.attrs.size()))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
+    HIP_TRY(hipMemset(geom.p, 0, inner_bytes + tri_bytes + 64));
+    if (b.inner.size()) HIP_TRY(hipMemcpy(geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(attrs.p, b.attrs.data(), b.attrs.size() * sizeof(AttrRecord), hipMemcpyHostToDevice));
+    return VMX_OK;
+}
+
+// points the kernels' view of the scene (SceneDev) at its records; sizes what follows the tree's depth
+static void bind_records(vmx_scene *sc) {
+    if (sc->device_built) {
+        // records were written on the device (k_lbvh_emit_*): the scene takes the builder's buffers over
+        const LbvhDevice &l = sc->lbvh;
+        sc->dev.inner = l.geom;
+        sc->dev.tris = (const unsigned char *)l.geom + l.tri_off;
+        sc->dev.tri_off = l.tri_off;
+        sc->dev.attrs = l.attrs;
+        sc->dev.root_ref = l.root_ref;
+        sc->dev.stack_entries = l.height + 2;
+        sc->n_inner = l.n_inner;
+    } else {
+        const HostBvh &b = sc->bvh;
+        const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
+        sc->dev.inner = sc->d_geom.p;
+        sc->dev.tris = sc->d_geom.p + inner_bytes;
+        sc->dev.tri_off = (uint32_t)inner_bytes;
+        sc->dev.attrs = sc->d_attrs.p;
+        sc->dev.root_ref = b.root_ref;
+        sc->dev.stack_entries = b.max_depth + 2;
+        sc->n_inner = (uint32_t)b.inner.size();
+    }
+    // LDS budget: shrink the block until one block's stacks fit in 64 KiB
+    sc->block = 256;
+    while (sc->block > 64 && (sc->block / 64) * sc->dev.stack_entries * 512 > 65536) sc->block /= 2;
+}
+
 // device half of scene creation: uploads sc->bvh / sc->spheres to sc->device (used for the first scene
 // and for the replicas of a multi-device scene, which share one host-side build)
 static int scene_upload(vmx_scene *sc) {
@@ -1153,39 +1228,9 @@ static int scene_upload(vmx_scene *sc) {
     for (size_t i = 0; i < sd.size(); ++i)
         if (sd[i].flags & 1u) sc->dev.emit_prefix = (uint32_t)i + 1;
     sc->dev.ntris = sc->ntris;
-    if (sc->device_built) {
-        // records were written on the device (k_lbvh_emit_*): the scene takes the builder's buffers over
-        const LbvhDevice &l = sc->lbvh;
-        sc->dev.inner = l.geom;
-        sc->dev.tris = (const unsigned char *)l.geom + l.tri_off;
-        sc->dev.tri_off = l.tri_off;
-        sc->dev.attrs = l.attrs;
-        sc->dev.root_ref = l.root_ref;
-        sc->dev.stack_entries = l.height + 2;
-        sc->n_inner = l.n_inner;
-    } else {
-        const HostBvh &b = sc->bvh;
-        const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
-        const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
-        // + 64: the quad-cooperative fetch reads 64 bytes from a 48-byte triangle record's start
-        if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "scene too large for 32-bit record offsets");
-        if (sc->d_geom.ensure(inner_bytes + tri_bytes + 64) || sc->d_attrs.ensure(b.attrs.size()))
-            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
-        HIP_TRY(hipMemset(sc->d_geom.p, 0, inner_bytes + tri_bytes + 64));
-        if (b.inner.size()) HIP_TRY(hipMemcpy(sc->d_geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(sc->d_geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(sc->d_attrs.p, b.attrs.data(), b.attrs.size() * sizeof(AttrRecord), hipMemcpyHostToDevice));
-        sc->dev.inner = sc->d_geom.p;
-        sc->dev.tris = sc->d_geom.p + inner_bytes;
-        sc->dev.tri_off = (uint32_t)inner_bytes;
-        sc->dev.attrs = sc->d_attrs.p;
-        sc->dev.root_ref = b.root_ref;
-        sc->dev.stack_entries = b.max_depth + 2;
-        sc->n_inner = (uint32_t)b.inner.size();
-    }
-    // LDS budget: shrink the block until one block's stacks fit in 64 KiB
-    sc->block = 256;
-    while (sc->block > 64 && (sc->block / 64) * sc->dev.stack_entries * 512 > 65536) sc->block /= 2;
+    if (!sc->device_built)
+        if (int rc = upload_records(sc->bvh, sc->d_geom, sc->d_attrs)) return rc;
+    bind_records(sc);
     return VMX_OK;
 }
 
@@ -1208,10 +1253,11 @@ int vmx_scene_create_ex(const float *pos, const float *nrm, const float *uv, uin
     sc->device = device;
     sc->ntris = ntris;
     sc->leaf_size = leaf_size ? leaf_size : 4;
+    sc->builder = builder;
     std::string err;
     bool built;
     if (builder == VMX_BVH_LBVH || builder == VMX_BVH_PLOC) {
-        sc->device_built = true, sc->flat_ready.store(false);
+        sc->device_built = true, sc->flat_ready.store(false), sc->flat_topology = false;
         built = builder == VMX_BVH_PLOC ? build_bvh_ploc_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err)
                                         : build_bvh_lbvh_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err);
     } else {
@@ -1257,6 +1303,8 @@ int vmx_scene_destroy(vmx_scene *sc) {
     sc->d_tex.release(), sc->d_tex1.release();
     sc->qws.head.release(), sc->qws.overflow_stack.release();
     if (sc->qws.done) (void)hipEventDestroy(sc->qws.done);
+    sc->upd.plan.release(), sc->upd.root_box.release(), sc->upd.scratch.release();
+    if (sc->upd.done) (void)hipEventDestroy(sc->upd.done);
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
     delete sc;
     return VMX_OK;
@@ -1286,14 +1334,55 @@ int vmx_scene_bind_texture(vmx_scene *sc, const float *data, uint32_t width, uin
     return VMX_OK;
 }
 
-// device-built trees: the reference's flat layout is produced on the first request for it
+// A refitted tree's boxes in the flat layout: one depth-first walk from root_ref over the downloaded records, left child
+// first — the export order of both kinds of builder (pre-order, left child = i + 1).  A node's box is its half of the
+// parent's record; the root's is the refit's root_box.  Topology and prim_order are the builder's and stay.
+static int export_refit_boxes(vmx_scene *sc) {
+    HostBvh &b = sc->bvh;
+    const size_t n_nodes = b.start.size();
+    std::vector<InnerRecord> rec(sc->n_inner);
+    if (sc->n_inner) HIP_TRY(hipMemcpy(rec.data(), sc->dev.inner, rec.size() * sizeof(InnerRecord), hipMemcpyDeviceToHost));
+    float root[6];
+    HIP_TRY(hipMemcpy(root, sc->upd.root_box.p, sizeof(root), hipMemcpyDeviceToHost));
+    struct Item {
+        uint32_t ref;
+        const float *box;  // six floats: min, max
+    };
+    std::vector<Item> work{{sc->dev.root_ref, root}};
+    size_t i = 0;
+    while (!work.empty()) {
+        const Item it = work.back();
+        work.pop_back();
+        const bool leaf = (it.ref & kLeafBit) != 0;
+        if (i >= n_nodes || leaf != (b.right_offset[i] == 0) || (!leaf && it.ref >= rec.size()))
+            return fail(VMX_ERR_HIP, "flat export: the device records do not match the tree's topology");
+        std::memcpy(&b.bbox[i * 6], it.box, 24);
+        ++i;
+        if (leaf) continue;
+        const InnerRecord &r = rec[it.ref];
+        work.push_back({r.right, r.rmin});  // rmin, rmax: six consecutive floats
+        work.push_back({r.left, r.lmin});
+    }
+    if (i != n_nodes) return fail(VMX_ERR_HIP, "flat export: the device records do not match the tree's topology");
+    return VMX_OK;
+}
+
+// device-built trees: the reference's flat layout is produced on the first request for it; after a REFIT the boxes are
+// read back from the records
 static int ensure_flat(const vmx_scene *csc) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
     if (sc->flat_ready.load(std::memory_order_acquire)) return VMX_OK;
     std::lock_guard<std::mutex> lock(sc->mu);
     if (sc->flat_ready.load(std::memory_order_relaxed)) return VMX_OK;
+    if (int rc = bind_device(sc)) return rc;
+    if (sc->upd.recorded) HIP_TRY(hipEventSynchronize(sc->upd.done));
     std::string err;
-    if (!lbvh_export_flat(sc->lbvh, sc->device, sc->bvh, err)) return fail(VMX_ERR_HIP, err);
+    if (!sc->flat_topology) {
+        if (!lbvh_export_flat(sc->lbvh, sc->device, sc->bvh, err)) return fail(VMX_ERR_HIP, err);
+        sc->flat_topology = true;
+    }
+    if (sc->upd.refitted)
+        if (int rc = export_refit_boxes(sc)) return rc;
     sc->flat_ready.store(true, std::memory_order_release);
     return VMX_OK;
 }
@@ -1346,6 +1435,7 @@ int vmx_trace(const vmx_scene *csc, const float *origin, const float *dir, uint3
     std::lock_guard<std::mutex> lock(sc->mu);
     int rc = bind_device(sc);
     if (rc) return rc;
+    if ((rc = wait_update(sc, sc->stream))) return rc;
     DevBuf<float> d_o, d_d, d_t;
     DevBuf<int32_t> d_id;
     if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || d_t.ensure(n) || d_id.ensure(n))
@@ -1374,6 +1464,7 @@ int vmx_raycast(const vmx_scene *csc, const float *origin, const float *dir, uin
     std::lock_guard<std::mutex> lock(sc->mu);
     int rc = bind_device(sc);
     if (rc) return rc;
+    if ((rc = wait_update(sc, sc->stream))) return rc;
     DevBuf<float> d_o, d_d;
     DevBuf<vmx_rayhit> d_out;
     if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || d_out.ensure(n))
@@ -1429,7 +1520,9 @@ int check_device_ptr(const void *p, int device, const char *what) {
 // first query of a scene: launch shapes from the occupancy of each instantiation, work counter, overflow slab, event
 int ensure_query_ws(vmx_scene *sc) {
     auto &q = sc->qws;
-    if (q.done) return VMX_OK;
+    if (q.done && q.stack_entries == sc->dev.stack_entries) return VMX_OK;
+    // first query, or the tree's depth changed (VMX_UPDATE_REBUILD): the slab is sized again, once no query uses it
+    if (q.done && q.recorded) HIP_TRY(hipEventSynchronize(q.done));
     // stack levels in LDS: the bounce kernel's 9 (make_tuning); deeper levels go to the slab
     q.lds_entries = std::min(sc->dev.stack_entries, 9u);
     q.overflow_entries = sc->dev.stack_entries + 1 > q.lds_entries ? sc->dev.stack_entries + 1 - q.lds_entries : 1u;
@@ -1444,7 +1537,8 @@ int ensure_query_ws(vmx_scene *sc) {
         }
     if (q.head.ensure(32) || q.overflow_stack.ensure((size_t)max_grid * (kQueryBlock / 64) * q.overflow_entries * 64 * 8))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the query workspace");
-    HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    q.stack_entries = sc->dev.stack_entries;
     return VMX_OK;
 }
 
@@ -1471,6 +1565,7 @@ int query_enqueue(vmx_scene *sc, uint32_t mode, const float *o, const float *d, 
     const uint64_t per_lane = n / ((uint64_t)cfg.grid * kQueryBlock);
     q.reserve = per_lane >= 256 ? 256u : (per_lane >= 64 ? 128u : 64u);
     if (w.recorded) HIP_TRY(hipStreamWaitEvent(s, w.done, 0));
+    if (int rc = wait_update(sc, s)) return rc;
     HIP_TRY(hipMemsetAsync(w.head.p, 0, sizeof(unsigned int), s));
     LAUNCH_TRY(launch_query(sc->dev, q, m, quad, cfg, s));
     HIP_TRY(hipEventRecord(w.done, s));
@@ -1545,6 +1640,7 @@ int vmx_primary_ids(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts 
     std::lock_guard<std::mutex> lock(sc->mu);
     rc = bind_device(sc);
     if (rc) return rc;
+    if ((rc = wait_update(sc, sc->stream))) return rc;
     const uint32_t n = fr.width * fr.height;
     DevBuf<float> d_t;
     DevBuf<int32_t> d_id;
@@ -1585,6 +1681,7 @@ int vmx_radiance(const vmx_scene *csc, const float *origin, const float *dir, ui
     if (rc) return rc;
     Workspace &ws = sc->ws;
     hipStream_t s = sc->stream;
+    if ((rc = wait_update(sc, s))) return rc;
     const bool count = opts->collect_counters != 0;
     const bool legacy = pipeline == 2 || pipeline == 3;  // first-generation kernels
     (void)legacy;
@@ -1755,6 +1852,7 @@ int bruteforce_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, 
     int rc = make_frame(c, o, fr);
     if (rc) return rc;
     fr.spp = spp;
+    if ((rc = wait_update(sc, s))) return rc;
     Workspace &ws = sc->ws;
     const uint32_t W = fr.width, rows = fr.local_rows, npix = W * rows;
     if (npix == 0) {
@@ -2044,6 +2142,7 @@ int vmx_multi_create(const float *pos, const float *nrm, const float *uv, uint32
         } else {
             sc = new vmx_scene();  // replica: shares the host-side build, uploads to its own device
             sc->device = devices[i];
+            sc->builder = first->builder;
             sc->ntris = first->ntris, sc->leaf_size = first->leaf_size;
             sc->bvh = first->bvh;
             sc->spheres = first->spheres;
@@ -2170,6 +2269,305 @@ int vmx_multi_render_bruteforce(vmx_multi *m, const vmx_camera *cam, const vmx_o
                         [&](vmx_scene *sc, const vmx_opts *o, float *d_out, vmx_stats *st) {
                             return bruteforce_impl(sc, cam, o, flags, d_out, sc->stream, st);
                         });
+}
+
+} /* extern "C" */
+
+// ---------------------------------------------------------------------------
+// in-place geometry updates (vmx_scene_update*, vmx_multi_update; kernels in vmx_update.inc)
+// ---------------------------------------------------------------------------
+namespace {
+
+// argument checks that need no device, in this order so that each can be seen alone (the scene is checked last)
+int update_args(const void *scene, const void *pos, const void *nrm, const void *uv, uint32_t ntris, uint32_t flags) {
+    if (flags & ~VMX_UPDATE_REBUILD) return fail(VMX_ERR_INVALID, "unknown update flags");
+    if (!pos && !nrm && !uv) return fail(VMX_ERR_INVALID, "nothing to update: pos, nrm and uv are all NULL");
+    if (ntris == 0) return fail(VMX_ERR_INVALID, "ntris is 0: it must be the scene's triangle count");
+    if (!scene) return fail(VMX_ERR_INVALID, "NULL scene");
+    return VMX_OK;
+}
+
+int update_scene_args(const vmx_scene *sc, const float *pos, uint32_t ntris) {
+    if (ntris != sc->ntris)
+        return fail(VMX_ERR_INVALID, "ntris " + std::to_string(ntris) + " is not the scene's triangle count " +
+                                         std::to_string(sc->ntris) + " (another count or order is a new scene)");
+    if (pos)  // as vmx_scene_create checks them (bvh_build.cpp: check_input)
+        for (size_t i = 0; i < (size_t)ntris * 9; ++i)
+            if (!std::isfinite(pos[i])) return fail(VMX_ERR_INVALID, "non-finite vertex position");
+    return VMX_OK;
+}
+
+// the next update's writes wait for the last query (it reads the records) and the last update
+int update_wait(vmx_scene *sc, hipStream_t s) {
+    if (sc->qws.recorded) HIP_TRY(hipStreamWaitEvent(s, sc->qws.done, 0));
+    return wait_update(sc, s);
+}
+
+int update_record(vmx_scene *sc, hipStream_t s) {
+    if (!sc->upd.done) HIP_TRY(hipEventCreateWithFlags(&sc->upd.done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(sc->upd.done, s));
+    sc->upd.recorded = true;
+    return VMX_OK;
+}
+
+void vertex_bounds(vmx_scene *sc, const float *pos) {  // as vmx_scene_create_ex computes them
+    for (int a = 0; a < 3; ++a) sc->bounds_lo[a] = sc->bounds_hi[a] = pos[a];
+    for (size_t v = 0; v < (size_t)sc->ntris * 3; ++v)
+        for (int a = 0; a < 3; ++a) {
+            sc->bounds_lo[a] = std::min(sc->bounds_lo[a], pos[v * 3 + a]);
+            sc->bounds_hi[a] = std::max(sc->bounds_hi[a], pos[v * 3 + a]);
+        }
+    sc->upd.bounds_stale = false;
+}
+
+// The refit plan: every referenced child of every inner record with the half of its parent it goes to, plus the root,
+// bucketed by tree level (deepest first: one launch each).  Derived by a walk from root_ref — the device builders leave
+// unused records zeroed, and their left = right = 0 would read as references to record 0.
+int ensure_refit_plan(vmx_scene *sc, hipStream_t s) {
+    auto &u = sc->upd;
+    if (u.plan_ready) return VMX_OK;
+    std::vector<InnerRecord> rec(sc->n_inner);
+    if (!(sc->dev.root_ref & kLeafBit)) {
+        HIP_TRY(hipMemcpyAsync(rec.data(), sc->dev.inner, rec.size() * sizeof(InnerRecord), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    struct Item {
+        uint32_t ref, dst, depth;
+    };
+    std::vector<std::vector<RefitItem>> level;
+    std::vector<Item> work{{sc->dev.root_ref, kRefitRoot, 0u}};
+    while (!work.empty()) {
+        const Item it = work.back();
+        work.pop_back();
+        if (it.depth >= kMaxStack || (!(it.ref & kLeafBit) && it.ref >= rec.size()))
+            return fail(VMX_ERR_HIP, "refit plan: the device records do not form a tree");
+        if (level.size() <= it.depth) level.resize(it.depth + 1);
+        level[it.depth].push_back({it.ref, it.dst});
+        if (it.ref & kLeafBit) continue;
+        const InnerRecord &r = rec[it.ref];
+        work.push_back({r.right, it.ref * 2u + 1u, it.depth + 1});
+        work.push_back({r.left, it.ref * 2u, it.depth + 1});
+    }
+    std::vector<RefitItem> flat;
+    u.levels.clear();
+    for (size_t d = level.size(); d-- > 0;) {
+        u.levels.emplace_back((uint32_t)flat.size(), (uint32_t)level[d].size());
+        flat.insert(flat.end(), level[d].begin(), level[d].end());
+    }
+    if (u.plan.ensure(flat.size() * sizeof(RefitItem)) || u.root_box.ensure(6))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the refit plan");
+    HIP_TRY(hipMemcpyAsync(u.plan.p, flat.data(), flat.size() * sizeof(RefitItem), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (`flat` is a host temporary)
+    u.plan_ready = true;
+    return VMX_OK;
+}
+
+// record rewrite and, with positions, the refit: enqueued on `s`, not synchronised (the first update that moves
+// vertices builds the refit plan and does)
+int update_enqueue(vmx_scene *sc, const float *d_pos, const float *d_nrm, const float *d_uv, hipStream_t s) {
+    auto &u = sc->upd;
+    if (d_pos)
+        if (int rc = ensure_refit_plan(sc, s)) return rc;
+    if (int rc = update_wait(sc, s)) return rc;
+    unsigned char *inner = (unsigned char *)const_cast<void *>(sc->dev.inner);
+    unsigned char *tris = inner + sc->dev.tri_off;
+    LAUNCH_TRY(launch_update_records(sc->ntris, d_pos, d_nrm, d_uv, tris, const_cast<void *>(sc->dev.attrs), s));
+    if (d_pos) {
+        const RefitItem *plan = (const RefitItem *)u.plan.p;
+        for (const auto &lv : u.levels)
+            LAUNCH_TRY(launch_refit_level(plan + lv.first, lv.second, d_pos, tris, inner, u.root_box.p, s));
+        u.refitted = true, u.bounds_stale = true;
+        sc->flat_ready.store(false, std::memory_order_release);
+    }
+    return update_record(sc, s);
+}
+
+// after a REBUILD: the new tree's records are bound; what was derived from the old tree goes
+void rebuilt(vmx_scene *sc) {
+    bind_records(sc);  // stack_entries, block; the render workspace's overflow stacks follow in bind_stack, the query
+                       // workspace in ensure_query_ws
+    sc->upd.plan_ready = false, sc->upd.refitted = false;
+    sc->flat_topology = !sc->device_built;
+    sc->flat_ready.store(!sc->device_built, std::memory_order_release);
+}
+
+// a host build's error as vmx_scene_create_ex reports it
+int build_error(const std::string &err) {
+    int code = VMX_ERR_INVALID;
+    if (err.find("deeper") != std::string::npos) code = VMX_ERR_DEPTH;
+    else if (err.rfind("LBVH builder: hip", 0) == 0)
+        code = (err.find("hipMalloc") != std::string::npos || err.find("out of memory") != std::string::npos) ? VMX_ERR_NOMEM : VMX_ERR_HIP;
+    return fail(code, err);
+}
+
+// normals / uvs of a host-built scene in triangle-ID order (what a REBUILD that keeps them hands the builder); the
+// caller has synchronised with the scene's last update
+int host_attrs_by_id(vmx_scene *sc, std::vector<float> &nrm, std::vector<float> &uv) {
+    std::vector<AttrRecord> a(sc->ntris);
+    HIP_TRY(hipMemcpy(a.data(), sc->dev.attrs, a.size() * sizeof(AttrRecord), hipMemcpyDeviceToHost));
+    const std::vector<uint32_t> &order = sc->bvh.prim_order;  // leaf slot -> triangle ID
+    nrm.resize((size_t)sc->ntris * 9), uv.resize((size_t)sc->ntris * 6);
+    for (uint32_t slot = 0; slot < sc->ntris; ++slot) {
+        const size_t t = order[slot];
+        std::memcpy(&nrm[t * 9], a[slot].n0, 36);
+        std::memcpy(&uv[t * 6], a[slot].uv0, 24);
+    }
+    return VMX_OK;
+}
+
+// host builders: build on the host (into a new HostBvh; the scene is untouched on failure)
+int host_rebuild_tree(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, HostBvh &out) {
+    std::vector<float> kn, ku;
+    if (!nrm || !uv) {
+        if (int rc = host_attrs_by_id(sc, kn, ku)) return rc;
+        if (!nrm) nrm = kn.data();
+        if (!uv) uv = ku.data();
+    }
+    std::string err;
+    const bool ok = sc->builder == VMX_BVH_SAH ? build_bvh_sah(pos, nrm, uv, sc->ntris, sc->leaf_size, out, err)
+                                               : build_bvh(pos, nrm, uv, sc->ntris, sc->leaf_size, out, err);
+    return ok ? VMX_OK : build_error(err);
+}
+
+// swaps a host-built tree in: new buffers, uploaded, then the old ones freed.  The caller has synchronised `s` after
+// update_wait, so nothing in flight reads the old records.
+int host_apply_tree(vmx_scene *sc, const HostBvh &b, hipStream_t s) {
+    DevBuf<unsigned char> geom;
+    DevBuf<AttrRecord> attrs;
+    if (int rc = upload_records(b, geom, attrs)) {
+        geom.release(), attrs.release();
+        return rc;
+    }
+    sc->d_geom.release(), sc->d_attrs.release();
+    sc->d_geom = geom, sc->d_attrs = attrs;
+    sc->bvh = b;
+    rebuilt(sc);
+    return update_record(sc, s);
+}
+
+// device builders: the build runs on `s` from device inputs; a kept attribute comes back from the records in
+// triangle-ID order first.  Blocks (the depth check needs the root's height on the host).
+int device_rebuild(vmx_scene *sc, const float *d_pos, const float *d_nrm, const float *d_uv, hipStream_t s) {
+    auto &u = sc->upd;
+    if (int rc = update_wait(sc, s)) return rc;
+    const size_t n = sc->ntris;
+    if (!d_nrm || !d_uv) {
+        if (u.scratch.ensure(n * 24)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the update inputs");
+        float *kn = d_nrm ? nullptr : u.scratch.p + n * 9, *ku = d_uv ? nullptr : u.scratch.p + n * 18;
+        LAUNCH_TRY(launch_attrs_by_id(sc->ntris, sc->dev.tris, sc->dev.attrs, kn, ku, s));
+        if (kn) d_nrm = kn;
+        if (ku) d_uv = ku;
+    }
+    LbvhDevice l;
+    std::string err;
+    const bool ok = build_bvh_device_inputs(d_pos, d_nrm, d_uv, sc->ntris, sc->leaf_size, sc->device,
+                                            sc->builder == VMX_BVH_PLOC, s, l, err);
+    if (!ok) {
+        (void)hipStreamSynchronize(s);
+        lbvh_release(l);
+        return build_error(err);
+    }
+    lbvh_release(sc->lbvh);  // (the build synchronised `s` after the waits: nothing in flight reads it)
+    sc->lbvh = l;
+    rebuilt(sc);
+    float rb[6];  // the root's box: vertex bounds of the new positions
+    HIP_TRY(hipMemcpy(rb, n > 1 ? l.node_box : l.leaf_box, sizeof(rb), hipMemcpyDeviceToHost));
+    for (int a = 0; a < 3; ++a) sc->bounds_lo[a] = rb[a], sc->bounds_hi[a] = rb[3 + a];
+    u.bounds_stale = false;
+    return update_record(sc, s);
+}
+
+// vmx_scene_update after the argument checks, under the scene's lock; `tree`: a host build shared by the replicas of
+// a vmx_multi (host builders with REBUILD), else NULL
+int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, uint32_t flags, const HostBvh *tree) {
+    if (int rc = bind_device(sc)) return rc;
+    hipStream_t s = sc->stream;
+    const size_t n = sc->ntris;
+    const bool rebuild = (flags & VMX_UPDATE_REBUILD) && pos;
+    if (rebuild && !sc->device_built) {
+        if (int rc = update_wait(sc, s)) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        HostBvh own;
+        if (!tree) {
+            if (int rc = host_rebuild_tree(sc, pos, nrm, uv, own)) return rc;
+            tree = &own;
+        }
+        if (int rc = host_apply_tree(sc, *tree, s)) return rc;
+        vertex_bounds(sc, pos);
+        HIP_TRY(hipStreamSynchronize(s));
+        return VMX_OK;
+    }
+    if (sc->upd.scratch.ensure(n * 24)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the update inputs");
+    float *d_pos = pos ? sc->upd.scratch.p : nullptr, *d_nrm = nrm ? sc->upd.scratch.p + n * 9 : nullptr;
+    float *d_uv = uv ? sc->upd.scratch.p + n * 18 : nullptr;
+    // (the scratch may still feed the previous update if that one ran on another stream)
+    if (int rc = wait_update(sc, s)) return rc;
+    if (pos) HIP_TRY(hipMemcpyAsync(d_pos, pos, n * 36, hipMemcpyHostToDevice, s));
+    if (nrm) HIP_TRY(hipMemcpyAsync(d_nrm, nrm, n * 36, hipMemcpyHostToDevice, s));
+    if (uv) HIP_TRY(hipMemcpyAsync(d_uv, uv, n * 24, hipMemcpyHostToDevice, s));
+    int rc = rebuild ? device_rebuild(sc, d_pos, d_nrm, d_uv, s) : update_enqueue(sc, d_pos, d_nrm, d_uv, s);
+    const hipError_t es = hipStreamSynchronize(s);  // (also before the inputs are overwritten when the update failed)
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(VMX_ERR_HIP, std::string("vmx_scene_update: ") + hipGetErrorString(es));
+    if (pos) vertex_bounds(sc, pos);
+    return VMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmx_scene_update(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t flags) {
+    if (int rc = update_args(sc, pos, nrm, uv, ntris, flags)) return rc;
+    if (int rc = update_scene_args(sc, pos, ntris)) return rc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return host_update(sc, pos, nrm, uv, flags, nullptr);
+}
+
+int vmx_scene_update_device(vmx_scene *sc, const void *d_pos, const void *d_nrm, const void *d_uv, uint32_t ntris,
+                            uint32_t flags, void *stream) {
+    if (int rc = update_args(sc, d_pos, d_nrm, d_uv, ntris, flags)) return rc;
+    if (int rc = update_scene_args(sc, nullptr, ntris)) return rc;
+    const bool rebuild = (flags & VMX_UPDATE_REBUILD) && d_pos;
+    if (rebuild && !sc->device_built)
+        return fail(VMX_ERR_INVALID, "VMX_UPDATE_REBUILD of a tree built on the host (VMX_BVH_REFERENCE / VMX_BVH_SAH) "
+                                     "needs host positions: use vmx_scene_update");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    const void *ptrs[3] = {d_pos, d_nrm, d_uv};
+    const char *names[3] = {"pos", "nrm", "uv"};
+    for (int i = 0; i < 3; ++i)
+        if (int rc = check_device_ptr(ptrs[i], sc->device, names[i])) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+    if (rebuild) return device_rebuild(sc, (const float *)d_pos, (const float *)d_nrm, (const float *)d_uv, s);
+    return update_enqueue(sc, (const float *)d_pos, (const float *)d_nrm, (const float *)d_uv, s);
+}
+
+int vmx_multi_update(vmx_multi *m, const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t flags) {
+    if (int rc = update_args(m, pos, nrm, uv, ntris, flags)) return rc;
+    std::lock_guard<std::mutex> mlock(m->mu);
+    vmx_scene *first = m->replica[0];
+    if (int rc = update_scene_args(first, pos, ntris)) return rc;
+    HostBvh tree;
+    const HostBvh *shared = nullptr;
+    if ((flags & VMX_UPDATE_REBUILD) && pos && !first->device_built) {
+        // host builders: one host build, uploaded to every replica
+        std::lock_guard<std::mutex> lock(first->mu);
+        if (int rc = bind_device(first)) return rc;
+        if (int rc = update_wait(first, first->stream)) return rc;
+        HIP_TRY(hipStreamSynchronize(first->stream));
+        if (int rc = host_rebuild_tree(first, pos, nrm, uv, tree)) return rc;
+        shared = &tree;
+    }
+    // replica by replica; device builders build on each device (a failure — too deep a tree — shows on the first one,
+    // before any replica changed)
+    for (size_t r = 0; r < m->replica.size(); ++r) {
+        vmx_scene *sc = m->replica[r];
+        std::lock_guard<std::mutex> lock(sc->mu);
+        const int rc = host_update(sc, pos, nrm, uv, flags, shared);
+        if (rc) return r ? fail(rc, "device " + std::to_string(sc->device) + ": " + g_err) : rc;
+    }
+    return VMX_OK;
 }
 
 } /* extern "C" */

@@ -129,6 +129,21 @@ int launch_primary_ids(const SceneDev &sc, const FrameDev &fr, uint32_t k, int32
 int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream);
 int query_query_blocks_per_cu(uint32_t block, uint32_t lds_bytes, uint32_t mode, bool quad, int *blocks);
 
+// in-place geometry updates (vmx_update.inc).  Refit plan entry: a child reference (vmx_device.h) and where its box goes —
+// parent record * 2 + side (0: lmin/lmax, 1: rmin/rmax), or kRefitRoot for the root's box
+struct RefitItem {
+    uint32_t ref, dst;
+};
+constexpr uint32_t kRefitRoot = 0xFFFFFFFFu;
+// records of every leaf slot from new positions (pos) and / or attributes (nrm, uv); NULL keeps that part
+int launch_update_records(uint32_t ntris, const float *pos, const float *nrm, const float *uv, void *tris, void *attrs,
+                          void *stream);
+// one tree level of the refit: n plan entries
+int launch_refit_level(const RefitItem *items, uint32_t n, const float *pos, const void *tris, void *inner,
+                       float *root_box, void *stream);
+// attribute records back in triangle-ID order: nrm [ntris*9], uv [ntris*6] (either may be NULL)
+int launch_attrs_by_id(uint32_t ntris, const void *tris, const void *attrs, float *nrm, float *uv, void *stream);
+
 int launch_trig(const float *x, uint32_t n, float *cs, float *sn, void *stream);
 
 // ---- render pipeline -----------------------------------------------------------

@@ -18,6 +18,7 @@
 //   k_resolve      per-pixel accumulation, early stop, pixel write (pathtracer.cpp:282-324)
 //   k_bruteforce*  BruteForceTracer::Render                        (integrators.cpp:9-186)
 //   k_query        device ray queries: nearest hit with a bound, any hit, RayCastCollision (vmx_query.inc)
+//   k_update_records, k_refit_level  in-place geometry updates: record rewrite, refit (vmx_update.inc)
 // (the first-generation kernels k_primary / k_bounce live in vmx_kernels_ab.inc: A/B library only)
 //
 // Execution model: persistent blocks stride over block-sized work items; the
@@ -3653,6 +3654,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 
 // device ray queries of explicit batches: k_query<MODE> + launch_query
 #include "vmx_query.inc"
+
+// in-place geometry updates: record rewrite and per-level refit
+#include "vmx_update.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

@@ -254,6 +254,61 @@ class Scene:
                 s.wait_stream(side)
         return (tri, t, hit) if want_ids else hit
 
+    # -- moving geometry --------------------------------------------------------
+    def update(self, pos=None, nrm=None, uv=None, rebuild=False, stream=None):
+        """In-place update of the same triangles (vmx_scene_update / vmx_scene_update_device; semantics in
+        include/vermilion_hip.h): pos / nrm [ntris, 9], uv [ntris, 6]; None keeps that attribute.  rebuild=False
+        refits the tree (topology kept, boxes tight over the new positions), True runs the scene's builder again.
+
+        numpy arrays (any float type, converted as at creation) -> the host entry, returns once the scene is updated.
+        torch tensors on this scene's device ->
+        the device entry on `stream` (default torch.cuda.current_stream()), not synchronised; they must be contiguous
+        float32 of exactly those shapes: anything else is a ValueError, never a copy through the host."""
+        arrays = {"pos": (pos, 9), "nrm": (nrm, 9), "uv": (uv, 6)}
+        given = {k: v for k, v in arrays.items() if v[0] is not None}
+        if not given:
+            raise ValueError("nothing to update: pos, nrm and uv are all None")
+        flags = L.VMX_UPDATE_REBUILD if rebuild else L.VMX_UPDATE_REFIT
+        if any(_is_tensor(a) for a, _ in given.values()):
+            return self._update_device(given, flags, stream)
+        ptrs, keep = {}, []
+        for k, (a, w) in given.items():
+            a = _f32(a).reshape(-1, w)
+            if a.shape[0] != self.ntris:
+                raise ValueError(f"{k} must be [{self.ntris}, {w}] (got {list(a.shape)}): another count is a new scene")
+            keep.append(a)
+            ptrs[k] = a.ctypes.data
+        self._check(self._lib.vmx_scene_update(self._h, ptrs.get("pos"), ptrs.get("nrm"), ptrs.get("uv"), self.ntris,
+                                               flags))
+
+    def _update_device(self, given, flags, stream):
+        import torch
+        dev = torch.device("cuda", self.device)
+        ptrs = {}
+        for k, (a, w) in given.items():
+            if not _is_tensor(a):
+                raise ValueError(f"{k}: mix of torch tensors and other arrays")
+            if a.device != dev:
+                raise ValueError(f"{k} must be on {dev} (got {a.device})")
+            if a.dtype != torch.float32:
+                raise ValueError(f"{k} must be float32 (got {a.dtype})")
+            if not a.is_contiguous():
+                raise ValueError(f"{k} must be contiguous")
+            if tuple(a.shape) != (self.ntris, w):
+                raise ValueError(f"{k} must be [{self.ntris}, {w}] (got {list(a.shape)})")
+            ptrs[k] = C.c_void_p(a.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        # torch's default stream is the legacy NULL stream, which the ABI reads as "the scene's own stream": run the
+        # update on a side stream ordered after `s`, and `s` after it (as Scene.query)
+        side = torch.cuda.Stream(dev) if s.cuda_stream == 0 else None
+        run = side if side is not None else s
+        if side is not None:
+            side.wait_stream(s)
+        self._check(self._lib.vmx_scene_update_device(self._h, ptrs.get("pos"), ptrs.get("nrm"), ptrs.get("uv"),
+                                                      self.ntris, flags, C.c_void_p(run.cuda_stream)))
+        if side is not None:
+            s.wait_stream(side)
+
     def primary_ids(self, cam, opts, k=0):
         n = cam.image_res[0] * cam.image_res[1]
         tri = np.empty(n, np.int32)
@@ -355,6 +410,22 @@ class MultiScene:
         data = np.ascontiguousarray(data, dtype=np.float32)
         c = 1 if data.ndim == 2 else data.shape[2]
         L.check(L.lib().vmx_multi_bind_texture(self._h, data.ctypes.data, data.shape[1], data.shape[0], c))
+
+    def update(self, pos=None, nrm=None, uv=None, rebuild=False):
+        """vmx_multi_update: Scene.update's host entry on every replica (numpy arrays; None keeps that attribute)"""
+        ptrs, keep = {}, []
+        for k, a, w in (("pos", pos, 9), ("nrm", nrm, 9), ("uv", uv, 6)):
+            if a is None:
+                continue
+            a = _f32(a).reshape(-1, w)
+            if a.shape[0] != self.ntris:
+                raise ValueError(f"{k} must be [{self.ntris}, {w}] (got {list(a.shape)}): another count is a new scene")
+            keep.append(a)
+            ptrs[k] = a.ctypes.data
+        if not ptrs:
+            raise ValueError("nothing to update: pos, nrm and uv are all None")
+        L.check(L.lib().vmx_multi_update(self._h, ptrs.get("pos"), ptrs.get("nrm"), ptrs.get("uv"), self.ntris,
+                                         L.VMX_UPDATE_REBUILD if rebuild else L.VMX_UPDATE_REFIT))
 
     def render(self, cam, opts):
         out = np.empty((cam.image_res[1], cam.image_res[0], 5), np.float32)
