@@ -348,6 +348,25 @@ int vmx_query_device(const vmx_scene *scene, uint32_t mode, const void *d_origin
 /* Same with HOST buffers: copies in, runs the device path on the scene's stream, copies out, synchronises. */
 int vmx_query(const vmx_scene *scene, uint32_t mode, const float *origin, const float *dir, const float *tmax,
               uint32_t n, int32_t *tri_id, float *t, uint8_t *hit);
+/* ---- MeshEngine::RayCast of device batches -------------------------------
+ * The whole hit record (meshEngine.cpp:239-509: BVH nearest hit, shading normal, uv, the sphere table) for device
+ * rays, without copies through the host.  out[n] vmx_rayhit is byte for byte what vmx_raycast returns for the same
+ * rays (pad = 0); no bound: the reference's RayCast has none.  Served by the query kernel (unbounded NEAREST, which
+ * leaves (tri_t, leaf slot) in each record) and a dense finish kernel (normal, uv, spheres, the rest of the record).
+ * flags: 0 or VMX_QUERY_FETCH_PER_LANE (same meaning as in vmx_query_device, same results); anything else is
+ * VMX_ERR_INVALID.  Pointers follow vmx_query_device's rules (DEVICE memory of the scene's device, checked before any
+ * launch); in addition d_out must be 16-byte aligned and must not overlap the rays.  n > 2^31 - 1 is VMX_ERR_INVALID,
+ * n == 0 is VMX_OK with no launch.  Enqueued on `stream` (NULL = the scene's stream), no synchronisation: ordered
+ * with the scene's queries and updates exactly as vmx_query_device (same workspace and event); no allocation after
+ * the scene's first query. */
+int vmx_raycast_device(const vmx_scene *scene, const void *d_origin, const void *d_dir, uint32_t n, void *d_out,
+                       uint32_t flags, void *stream);
+/* The same for sample k's camera ray of every pixel — the ray vmx_render traces for that sample and vmx_primary_ids
+ * reports (origin = cam->position): a device G-buffer, out[W*H] vmx_rayhit in pixel order p = y*W + x.  cam / opts
+ * are checked as vmx_render checks them (rays_per_pixel >= 4, rotation_units); only opts->seed is used, and
+ * opts->world > 1 is VMX_ERR_INVALID (whole images only).  k < 4 * (rays_per_pixel / 4), as in vmx_primary_ids. */
+int vmx_raycast_camera_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t k,
+                              void *d_out, uint32_t flags, void *stream);
 
 /*
  * Primary-hit AOV: generates sample k's camera ray of every pixel on the

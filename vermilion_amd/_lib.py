@@ -181,6 +181,9 @@ SYMBOLS = {
     "vmx_raycast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "vmx_query_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "vmx_query": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    "vmx_raycast_device": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "vmx_raycast_camera_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.c_uint32,
+                                            _P]),
     "vmx_primary_ids": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P]),
     "vmx_radiance": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_trig": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_int]),

@@ -161,10 +161,12 @@ class MeshEngine:
         return True
 
     def RayCast(self, rayStart, rayDirection):
-        """-> (hit, material, location, normal, distance, uv, colour) for one ray or a batch"""
+        """-> (hit, material, location, normal, distance, uv, colour) for one ray or a batch.  torch tensors on the
+        scene's device (contiguous float32 [n, 3]) -> the device entry on the current stream, the same tuple as
+        tensors (hit / material torch.bool), nothing synchronised"""
         if self.sceneAccelerator is None:
             raise RuntimeError("RayCast before a scene was loaded")
-        h = self.sceneAccelerator.raycast(rayStart, rayDirection)
+        h = self.sceneAccelerator.raycast(rayStart, rayDirection)  # a record array, or a dict of tensors: same fields
         return ((h["flags"] & 1) != 0, (h["flags"] & 2) != 0, h["location"], h["normal"], h["distance"],
                 h["uv"], h["colour"])
 

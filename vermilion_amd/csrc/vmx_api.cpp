@@ -191,7 +191,8 @@ struct vmx_scene {
         hipEvent_t done = nullptr;
         bool recorded = false;
         uint32_t lds_entries = 0, overflow_entries = 0;
-        uint32_t grid[2][3] = {};              // persistent blocks per [per-lane fetch][mode]
+        uint32_t grid[2][kQueryModes] = {};    // persistent blocks per [per-lane fetch][mode]: VMX_QUERY_* and the
+                                               // raycast entries' kQueryCastRays / kQueryCastCamera
         uint32_t stack_entries = 0;            // the tree depth the slab was sized for (a REBUILD can change it)
     } qws;
     // in-place geometry updates (vmx_scene_update*): `done` is recorded after each update and waited on by every later
@@ -1529,7 +1530,7 @@ int ensure_query_ws(vmx_scene *sc) {
     const uint32_t lds = (kQueryBlock / 64) * (q.lds_entries + 1) * 512;
     uint32_t max_grid = 1;
     for (int pl = 0; pl < 2; ++pl)
-        for (uint32_t m = 0; m <= VMX_QUERY_COLLISION; ++m) {
+        for (uint32_t m = 0; m < kQueryModes; ++m) {
             int b = 0;
             HIP_TRY((hipError_t)query_query_blocks_per_cu(kQueryBlock, lds, m, pl == 0, &b));
             q.grid[pl][m] = (uint32_t)sc->num_cus * (uint32_t)std::max(b, 1);
@@ -1542,35 +1543,115 @@ int ensure_query_ws(vmx_scene *sc) {
     return VMX_OK;
 }
 
-// enqueues one query on `s`; the caller holds sc->mu and has checked the arguments
-int query_enqueue(vmx_scene *sc, uint32_t mode, const float *o, const float *d, const float *tmax, uint32_t n,
-                  int32_t *tri_id, float *t, uint8_t *hit, hipStream_t s) {
-    if (int rc = ensure_query_ws(sc)) return rc;
-    auto &w = sc->qws;
-    const uint32_t m = mode & kQueryModeMask;
-    const bool quad = (mode & VMX_QUERY_FETCH_PER_LANE) == 0;
-    QueryDev q{};
-    q.o = o, q.d = d, q.tmax = tmax, q.n = n;
-    q.tri_id = tri_id, q.t = t, q.hit = hit;
+// QueryDev (work source and stack, no rays or outputs) and launch shape of one query of n rays in mode m
+void query_shape(const vmx_scene *sc, uint32_t m, bool quad, uint32_t n, QueryDev &q, LaunchCfg &cfg) {
+    const auto &w = sc->qws;
+    q = QueryDev{};
+    q.n = n;
     q.head = w.head.p;
     q.lds_entries = w.lds_entries, q.overflow_entries = w.overflow_entries;
     q.overflow_stack = w.overflow_stack.p;
     // refill as soon as 8 lanes are idle: the bounce kernel's setting for incoherent rays (make_tuning)
     q.refill_min = 8;
-    LaunchCfg cfg;
     cfg.block = kQueryBlock;
     cfg.lds_bytes = (kQueryBlock / 64) * (w.lds_entries + 1) * 512;
     cfg.grid = (uint32_t)std::min<uint64_t>(w.grid[quad ? 0 : 1][m], std::max<uint64_t>(1, ((uint64_t)n + kQueryBlock - 1) / kQueryBlock));
     // reservation per atomic: WorkDev::reserve's rule (bind_stack)
     const uint64_t per_lane = n / ((uint64_t)cfg.grid * kQueryBlock);
     q.reserve = per_lane >= 256 ? 256u : (per_lane >= 64 ? 128u : 64u);
+}
+
+// a query's kernels on `s` run after the previous query (the workspace) and the last update, and reset the counter
+int query_begin(vmx_scene *sc, hipStream_t s) {
+    auto &w = sc->qws;
     if (w.recorded) HIP_TRY(hipStreamWaitEvent(s, w.done, 0));
     if (int rc = wait_update(sc, s)) return rc;
     HIP_TRY(hipMemsetAsync(w.head.p, 0, sizeof(unsigned int), s));
-    LAUNCH_TRY(launch_query(sc->dev, q, m, quad, cfg, s));
+    return VMX_OK;
+}
+
+// after a query's last kernel: the next query and the next update wait for it
+int query_end(vmx_scene *sc, hipStream_t s) {
+    auto &w = sc->qws;
     HIP_TRY(hipEventRecord(w.done, s));
     w.recorded = true;
     return VMX_OK;
+}
+
+// enqueues one query on `s`; the caller holds sc->mu and has checked the arguments
+int query_enqueue(vmx_scene *sc, uint32_t mode, const float *o, const float *d, const float *tmax, uint32_t n,
+                  int32_t *tri_id, float *t, uint8_t *hit, hipStream_t s) {
+    if (int rc = ensure_query_ws(sc)) return rc;
+    const uint32_t m = mode & kQueryModeMask;
+    const bool quad = (mode & VMX_QUERY_FETCH_PER_LANE) == 0;
+    QueryDev q;
+    LaunchCfg cfg;
+    query_shape(sc, m, quad, n, q, cfg);
+    q.o = o, q.d = d, q.tmax = tmax;
+    q.tri_id = tri_id, q.t = t, q.hit = hit;
+    if (int rc = query_begin(sc, s)) return rc;
+    LAUNCH_TRY(launch_query(sc->dev, q, m, quad, cfg, s));
+    return query_end(sc, s);
+}
+
+// ---- MeshEngine::RayCast of device batches (k_query_cast + k_raycast_finish) ----------------------------------
+// argument checks that need no device, in this order (each can be seen alone): flags, rays, output, count, the
+// output's alignment and overlap with the rays; the NULL scene comes last (vmx_raycast_device_args / _camera_args)
+int raycast_flags(uint32_t flags) {
+    if (flags & ~VMX_QUERY_FETCH_PER_LANE) return fail(VMX_ERR_INVALID, "unknown raycast flags");
+    return VMX_OK;
+}
+
+int raycast_out(const void *out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL d_out");
+    if ((uintptr_t)out & 15u) return fail(VMX_ERR_INVALID, "d_out must be 16-byte aligned");
+    return VMX_OK;
+}
+
+int raycast_args(const vmx_scene *sc, const void *o, const void *d, uint32_t n, const void *out, uint32_t flags) {
+    if (int rc = raycast_flags(flags)) return rc;
+    if (n > 0 && (!o || !d)) return fail(VMX_ERR_INVALID, "NULL rays");
+    if (n > 0)
+        if (int rc = raycast_out(out)) return rc;
+    if (n > 0x7FFFFFFFu) return fail(VMX_ERR_INVALID, "more than 2^31 - 1 rays");
+    if (n > 0) {
+        // the records are written while the rays are still read: [out, out + 64 n) must not meet either ray array
+        const uintptr_t a = (uintptr_t)out, b = a + (uintptr_t)n * sizeof(vmx_rayhit);
+        const uintptr_t ro[2] = {(uintptr_t)o, (uintptr_t)d};
+        for (uintptr_t r : ro)
+            if (r < b && a < r + (uintptr_t)n * 12) return fail(VMX_ERR_INVALID, "d_out overlaps the rays");
+    }
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    return VMX_OK;
+}
+
+// flags, camera / opts, output, the frame (make_frame's checks), world, sample index; the NULL scene comes last
+int raycast_camera_args(const vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t k, const void *out,
+                        uint32_t flags, FrameDev &fr) {
+    if (int rc = raycast_flags(flags)) return rc;
+    if (!cam || !opts) return fail(VMX_ERR_INVALID, "NULL camera or opts");
+    if (int rc = raycast_out(out)) return rc;
+    if (int rc = make_frame(*cam, *opts, fr)) return rc;
+    if (opts->world > 1) return fail(VMX_ERR_INVALID, "world > 1: the camera raycast returns the whole image only");
+    if (k >= fr.kmax) return fail(VMX_ERR_INVALID, "sample index out of range");
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    return VMX_OK;
+}
+
+// enqueues one raycast of n rays (camera: sample k's camera ray of every pixel of fr) on `s`; the caller holds sc->mu
+// and has checked the arguments and pointers
+int raycast_enqueue(vmx_scene *sc, bool camera, bool quad, const float *o, const float *d, uint32_t n, const FrameDev &fr,
+                    uint32_t k, void *out, hipStream_t s) {
+    if (int rc = ensure_query_ws(sc)) return rc;
+    QueryDev q;
+    LaunchCfg cfg;
+    query_shape(sc, camera ? kQueryCastCamera : kQueryCastRays, quad, n, q, cfg);
+    q.o = o, q.d = d, q.sample = k;
+    // the finish kernel: one lane per ray, a few rays per lane at the largest sizes (its LDS table is staged per block)
+    const uint32_t finish_grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 255) / 256, (uint64_t)std::max(sc->num_cus, 1) * 16);
+    if (int rc = query_begin(sc, s)) return rc;
+    LAUNCH_TRY(launch_raycast_query(sc->dev, q, fr, camera, quad, out, cfg, finish_grid, s));
+    return query_end(sc, s);
 }
 
 }  // namespace
@@ -1589,6 +1670,35 @@ int vmx_query_device(const vmx_scene *csc, uint32_t mode, const void *d_origin, 
         if (int rc = check_device_ptr(ptrs[i], sc->device, names[i])) return rc;
     return query_enqueue(sc, mode, (const float *)d_origin, (const float *)d_dir, (const float *)d_tmax, n,
                          (int32_t *)d_tri_id, (float *)d_t, (uint8_t *)d_hit, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int vmx_raycast_device(const vmx_scene *csc, const void *d_origin, const void *d_dir, uint32_t n, void *d_out,
+                       uint32_t flags, void *stream) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (int rc = raycast_args(sc, d_origin, d_dir, n, d_out, flags)) return rc;
+    if (n == 0) return VMX_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    const void *ptrs[3] = {d_origin, d_dir, d_out};
+    const char *names[3] = {"origin", "dir", "d_out"};
+    for (int i = 0; i < 3; ++i)
+        if (int rc = check_device_ptr(ptrs[i], sc->device, names[i])) return rc;
+    FrameDev fr;
+    std::memset(&fr, 0, sizeof(fr));
+    return raycast_enqueue(sc, false, (flags & VMX_QUERY_FETCH_PER_LANE) == 0, (const float *)d_origin,
+                           (const float *)d_dir, n, fr, 0, d_out, stream ? (hipStream_t)stream : sc->stream);
+}
+
+int vmx_raycast_camera_device(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t k, void *d_out,
+                              uint32_t flags, void *stream) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    FrameDev fr;
+    if (int rc = raycast_camera_args(sc, cam, opts, k, d_out, flags, fr)) return rc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    if (int rc = check_device_ptr(d_out, sc->device, "d_out")) return rc;
+    return raycast_enqueue(sc, true, (flags & VMX_QUERY_FETCH_PER_LANE) == 0, nullptr, nullptr, fr.width * fr.height, fr,
+                           k, d_out, stream ? (hipStream_t)stream : sc->stream);
 }
 
 int vmx_query(const vmx_scene *csc, uint32_t mode, const float *origin, const float *dir, const float *tmax, uint32_t n,

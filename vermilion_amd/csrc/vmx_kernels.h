@@ -103,7 +103,7 @@ struct QueryDev {
     uint32_t refill_min;    // refill when this many lanes of a wave are idle
     uint32_t lds_entries;   // stack levels kept in LDS
     uint32_t overflow_entries;  // deeper levels, in the global slab below (64 lanes x 8 B each)
-    uint32_t pad;
+    uint32_t sample;        // camera source of k_query<kQueryCastCamera>: the sample index k of every pixel's ray
     void *overflow_stack;   // uint2[waves][overflow_entries][64]
     unsigned int *head;     // work counter, zeroed before the launch
     int32_t *tri_id;
@@ -126,8 +126,16 @@ int launch_primary_ids(const SceneDev &sc, const FrameDev &fr, uint32_t k, int32
                        LaunchCfg cfg, void *stream);
 
 // device ray queries (vmx_query.inc): mode = VMX_QUERY_NEAREST / _ANY / _COLLISION; quad: quad-cooperative record fetch
+// Internal modes of the raycast entries (no ABI name, k_query<3 / 4, true | false, QueryCast>): unbounded NEAREST over explicit rays / camera rays
+constexpr uint32_t kQueryCastRays = 3, kQueryCastCamera = 4, kQueryModes = 5;
 int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream);
 int query_query_blocks_per_cu(uint32_t block, uint32_t lds_bytes, uint32_t mode, bool quad, int *blocks);
+// MeshEngine::RayCast of a device batch (vmx_raycast_device, camera = false: rays q.o / q.d) or of sample q.sample's
+// camera ray of every pixel of fr (vmx_raycast_camera_device, camera = true; q.n = W * H): k_query<3 | 4> with cfg, then
+// k_raycast_finish on finish_grid blocks of 256; out = vmx_rayhit[q.n], 16-byte aligned.  Occupancy: the modes
+// kQueryCastRays = 3 / kQueryCastCamera = 4 of query_query_blocks_per_cu
+int launch_raycast_query(const SceneDev &sc, const QueryDev &q, const FrameDev &fr, bool camera, bool quad, void *out,
+                         LaunchCfg cfg, uint32_t finish_grid, void *stream);
 
 // in-place geometry updates (vmx_update.inc).  Refit plan entry: a child reference (vmx_device.h) and where its box goes —
 // parent record * 2 + side (0: lmin/lmax, 1: rmin/rmax), or kRefitRoot for the root's box

@@ -25,12 +25,27 @@
 // is k_trace_w's: lane-strided LDS levels [0, lds_entries) with the bottom entry (near = -inf) at level 0, deeper
 // levels in the per-wave HBM slab.
 constexpr uint32_t kQueryNearest = 0, kQueryAny = 1, kQueryCollision = 2;  // VMX_QUERY_* of vermilion_hip.h
+// Internal modes of vmx_raycast_device / vmx_raycast_camera_device (no ABI name): NEAREST with L = 999999999.f — the
+// (best, slot) of bvh_nearest — over the rays of q.o / q.d (CAST_RAYS) or over sample q.sample's camera ray of pixel
+// `item` (CAST_CAMERA: primary_ray, origin = the camera).  A finished ray's (best, slot) goes into the caller's own
+// vmx_rayhit record (tri_t, pad words), which k_raycast_finish then completes: no scratch that grows with n.
+// (kQueryCastRays = 3, kQueryCastCamera = 4: vmx_kernels.h)
+
+// what the cast modes add to k_query's arguments: the camera (kQueryCastCamera) and the caller's vmx_rayhit records
+struct QueryCast {
+    FrameDev fr;
+    float *rec;  // [n * 16] words
+};
+__device__ __forceinline__ const QueryCast &query_cast(const QueryCast &c) { return c; }
 
 // QUAD: record fetch of k_trace_w<1> (quad-cooperative + DPP transpose, the default); else per-lane 64-B loads as in
-// bvh_nearest (VMX_QUERY_FETCH_PER_LANE)
-template <uint32_t MODE, bool QUAD>
+// bvh_nearest (VMX_QUERY_FETCH_PER_LANE).  Cast: one QueryCast for the cast modes, nothing for the others (whose
+// kernels keep the two-argument form)
+template <uint32_t MODE, bool QUAD, typename... Cast>
 __global__ void __launch_bounds__(256, VMX_TRACE_WAVES_PER_SIMD)
-k_query(SceneDev sc, QueryDev q) {
+k_query(SceneDev sc, QueryDev q, Cast... cast) {
+    constexpr bool CAST = MODE >= kQueryCastRays;
+    static_assert(CAST == (sizeof...(Cast) == 1), "the cast modes and only they take a QueryCast");
     extern __shared__ uint2 lds_stack[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const int lds_entries = (int)q.lds_entries;
@@ -53,6 +68,12 @@ k_query(SceneDev sc, QueryDev q) {
 
     // results of ray `i` (t = best: L on a miss)
     auto write_out = [&](uint32_t i, int s, float t) {
+        if constexpr (CAST) {  // vmx_rayhit words 10 (tri_t) and 15 (pad): k_raycast_finish reads them back
+            float *rec = query_cast(cast...).rec;
+            rec[(size_t)i * 16 + 10] = t;
+            rec[(size_t)i * 16 + 15] = __int_as_float(s);
+            return;
+        }
         if (MODE != kQueryAny) {
             if (q.tri_id) q.tri_id[i] = s >= 0 ? (int32_t)__float_as_uint(tris[(uint32_t)s * 3 + 2].y) : -1;
             if (q.t) q.t[i] = t;
@@ -175,12 +196,19 @@ k_query(SceneDev sc, QueryDev q) {
                 const uint32_t item = res_lo + rank;
                 res_lo = __builtin_amdgcn_readfirstlane(res_lo + min((uint32_t)__popcll(want), avail));
                 if (take) {
-                    const size_t i3 = (size_t)item * 3;
-                    ox = q.o[i3], oy = q.o[i3 + 1], oz = q.o[i3 + 2];
-                    dx = q.d[i3], dy = q.d[i3 + 1], dz = q.d[i3 + 2];
+                    if constexpr (MODE == kQueryCastCamera) {  // the ray k_raygen / k_primary_ids form for (pixel, sample)
+                        const FrameDev &fr = query_cast(cast...).fr;
+                        Rng rng;
+                        ox = fr.px, oy = fr.py, oz = fr.pz;
+                        primary_ray(fr, item, q.sample, rng, dx, dy, dz);
+                    } else {
+                        const size_t i3 = (size_t)item * 3;
+                        ox = q.o[i3], oy = q.o[i3 + 1], oz = q.o[i3 + 2];
+                        dx = q.d[i3], dy = q.d[i3 + 1], dz = q.d[i3 + 2];
+                    }
                     float lim = 999999999.f;  // bvh.cpp:48
                     bool valid = true;
-                    if (q.tmax) {
+                    if (!CAST && q.tmax) {
                         const float tm = q.tmax[item];
                         valid = tm > 0.0f;  // !(tmax > 0), NaN included: a miss, not traversed
                         lim = valid ? fminf(tm, 999999999.f) : tm;
@@ -210,6 +238,52 @@ k_query(SceneDev sc, QueryDev q) {
     }
 }
 
+// MeshEngine::RayCast after the BVH query (meshEngine.cpp:365-508) for the (best, slot) k_query<3 / 4> left in each
+// record: one lane per ray, dense, grid-stride.  The sphere table is staged in LDS as k_shade does; SRC 1 (camera
+// rays: the ray is formed again by primary_ray, origin = the camera) also stages (centre - camera, |op|^2), which is
+// what sphere_hit computes from the same floats for that origin (k_shade<0>).  Writes the whole 64-byte vmx_rayhit in
+// k_raycast's order: location, distance | normal, tri_id | uv, tri_t, flags | colour, pad = 0.
+template <int SRC>
+__global__ void __launch_bounds__(256)
+k_raycast_finish(SceneDev sc, FrameDev fr, const float *__restrict__ o, const float *__restrict__ d, uint32_t n,
+                 uint32_t k, float4 *out) {
+    __shared__ float4 s_geom[kLdsSpheres];
+    __shared__ float4 s_cam_op[kLdsSpheres];
+    if (threadIdx.x < min(sc.nspheres, kLdsSpheres)) {
+        const SphereDev &q = sc.spheres[threadIdx.x];
+        s_geom[threadIdx.x] = make_float4(q.cx, q.cy, q.cz, q.rad2);
+        if (SRC == 1) {
+            const float opx = q.cx - fr.px, opy = q.cy - fr.py, opz = q.cz - fr.pz;
+            s_cam_op[threadIdx.x] = make_float4(opx, opy, opz, dot3(opx, opy, opz, opx, opy, opz));
+        }
+    }
+    __syncthreads();
+    const float4 *__restrict__ tris = (const float4 *)sc.tris;
+    const float *rec = (const float *)out;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float ox, oy, oz, dx, dy, dz;
+        if (SRC == 1) {
+            Rng rng;
+            ox = fr.px, oy = fr.py, oz = fr.pz;
+            primary_ray(fr, i, k, rng, dx, dy, dz);
+        } else {
+            const size_t i3 = (size_t)i * 3;
+            ox = o[i3], oy = o[i3 + 1], oz = o[i3 + 2];
+            dx = d[i3], dy = d[i3 + 1], dz = d[i3 + 2];
+        }
+        const float best = rec[(size_t)i * 16 + 10];
+        const int slot = __float_as_int(rec[(size_t)i * 16 + 15]);
+        CastResult c;
+        cast_finish<true, SRC == 1>(sc, ox, oy, oz, dx, dy, dz, best, slot, c, s_geom, s_cam_op);
+        const int32_t id = c.slot >= 0 ? (int32_t)__float_as_uint(tris[c.slot * 3 + 2].y) : -1;
+        const uint32_t flags = ((c.nearest < kInf) ? 1u : 0u) | (c.material ? 2u : 0u);
+        out[(size_t)i * 4] = make_float4(ox + (dx * c.nearest), oy + (dy * c.nearest), oz + (dz * c.nearest), c.nearest);
+        out[(size_t)i * 4 + 1] = make_float4(c.nx, c.ny, c.nz, __int_as_float(id));
+        out[(size_t)i * 4 + 2] = make_float4(c.uvx, c.uvy, c.tri_t, __uint_as_float(flags));
+        out[(size_t)i * 4 + 3] = make_float4(c.cr, c.cg, c.cb, 0.f);
+    }
+}
+
 int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream) {
     const dim3 g(cfg.grid), b(cfg.block);
     hipStream_t s = (hipStream_t)stream;
@@ -234,8 +308,34 @@ int query_query_blocks_per_cu(uint32_t block, uint32_t lds_bytes, uint32_t mode,
 #define VMX_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, K, (int)block, lds_bytes)
     if (mode == kQueryAny) e = quad ? VMX_OCC((k_query<kQueryAny, true>)) : VMX_OCC((k_query<kQueryAny, false>));
     else if (mode == kQueryCollision) e = quad ? VMX_OCC((k_query<kQueryCollision, true>)) : VMX_OCC((k_query<kQueryCollision, false>));
+    else if (mode == kQueryCastRays) e = quad ? VMX_OCC((k_query<kQueryCastRays, true, QueryCast>)) : VMX_OCC((k_query<kQueryCastRays, false, QueryCast>));
+    else if (mode == kQueryCastCamera) e = quad ? VMX_OCC((k_query<kQueryCastCamera, true, QueryCast>)) : VMX_OCC((k_query<kQueryCastCamera, false, QueryCast>));
     else e = quad ? VMX_OCC((k_query<kQueryNearest, true>)) : VMX_OCC((k_query<kQueryNearest, false>));
 #undef VMX_OCC
     if (blocks) *blocks = a;
     return (int)e;
+}
+
+int launch_raycast_query(const SceneDev &sc, const QueryDev &q, const FrameDev &fr, bool camera, bool quad, void *out,
+                         LaunchCfg cfg, uint32_t finish_grid, void *stream) {
+    const dim3 g(cfg.grid), b(cfg.block);
+    hipStream_t s = (hipStream_t)stream;
+    const QueryCast c = {fr, (float *)out};
+#define VMX_QC(M)                                                                                   \
+    if (quad) hipLaunchKernelGGL((k_query<M, true, QueryCast>), g, b, cfg.lds_bytes, s, sc, q, c); \
+    else hipLaunchKernelGGL((k_query<M, false, QueryCast>), g, b, cfg.lds_bytes, s, sc, q, c);
+    if (camera) {
+        VMX_QC(kQueryCastCamera)
+    } else {
+        VMX_QC(kQueryCastRays)
+    }
+#undef VMX_QC
+    if (int e = launch_status()) return e;
+    if (camera)
+        hipLaunchKernelGGL(k_raycast_finish<1>, dim3(finish_grid), dim3(256), 0, s, sc, fr, nullptr, nullptr, q.n,
+                           q.sample, (float4 *)out);
+    else
+        hipLaunchKernelGGL(k_raycast_finish<0>, dim3(finish_grid), dim3(256), 0, s, sc, fr, q.o, q.d, q.n, 0u,
+                           (float4 *)out);
+    return launch_status();
 }

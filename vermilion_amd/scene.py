@@ -20,6 +20,49 @@ def _f32(a, shape_last=None):
     return a
 
 
+def _device_rays(x, name):
+    """a ray array as the device entries take it (contiguous float32 [n, 3] tensor), or a ValueError"""
+    import torch
+    if not _is_tensor(x):
+        raise ValueError(f"{name}: mix of torch tensors and other arrays")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name} must be [n, 3]")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32 (got {x.dtype})")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return x
+
+
+class _SideStream:
+    """The stream a device entry runs on: `stream` (default: the current stream).  torch's default stream is the
+    legacy NULL stream, which the ABI reads as "the scene's own stream": then a side stream ordered after it, and it
+    after the side stream (as Scene.query)"""
+
+    def __init__(self, dev, stream):
+        import torch
+        self.s = stream if stream is not None else torch.cuda.current_stream(dev)
+        self.side = torch.cuda.Stream(dev) if self.s.cuda_stream == 0 else None
+
+    def __enter__(self):
+        if self.side is not None:
+            self.side.wait_stream(self.s)
+            return self.side
+        return self.s
+
+    def __exit__(self, *exc):
+        if self.side is not None:
+            self.s.wait_stream(self.side)
+
+
+def _rayhit_views(raw):
+    """named views over [..., 16] float32 vmx_rayhit records (RAYHIT_DTYPE's fields; tri_id / flags as int32)"""
+    import torch
+    words = raw.view(torch.int32)
+    return {"location": raw[..., 0:3], "distance": raw[..., 3], "normal": raw[..., 4:7], "tri_id": words[..., 7],
+            "uv": raw[..., 8:10], "tri_t": raw[..., 10], "flags": words[..., 11], "colour": raw[..., 12:15], "raw": raw}
+
+
 def make_camera(position, rotation_deg, width, height, spp, back_distance=6.0, back_size=(3.6, 2.4), rotation_rad=None):
     """cameraSettings subset (core/camera/camera.h:32-47); defaults follow
     RenderEngine::CreateInternalDefaultCamera (core/engines/renderEngine.cpp:135-139).
@@ -167,12 +210,55 @@ class Scene:
         self._check(self._lib.vmx_trace(self._h, o.ctypes.data, d.ctypes.data, n, tri.ctypes.data, t.ctypes.data))
         return tri, t
 
-    def raycast(self, origin, direction):
+    def raycast(self, origin, direction, stream=None, per_lane_fetch=False):
+        """MeshEngine::RayCast (meshEngine.cpp:239-509) of a batch.
+
+        numpy in -> vmx_raycast (host buffers, synchronous), a RAYHIT_DTYPE array out.  torch tensors on this scene's
+        device in -> vmx_raycast_device on `stream` (default torch.cuda.current_stream()), nothing synchronised; out: a
+        dict of views over one [n, 16] float32 tensor ("raw") — location [n, 3], distance [n], normal [n, 3], tri_id [n]
+        (int32), uv [n, 2], tri_t [n], flags [n] (int32), colour [n, 3].  Device rays must be contiguous float32 [n, 3]:
+        anything else is a ValueError, never a copy through the host.  per_lane_fetch: VMX_QUERY_FETCH_PER_LANE."""
+        if _is_tensor(origin) or _is_tensor(direction):
+            return self._raycast_device(origin, direction, stream, per_lane_fetch)
         o, d = _f32(origin, 3), _f32(direction, 3)
         n = o.shape[0]
         out = np.zeros(n, dtype=RAYHIT_DTYPE)
         self._check(self._lib.vmx_raycast(self._h, o.ctypes.data, d.ctypes.data, n, out.ctypes.data))
         return out
+
+    def _raycast_device(self, origin, direction, stream, per_lane_fetch):
+        import torch
+        dev = torch.device("cuda", self.device)
+        o, d = _device_rays(origin, "origin"), _device_rays(direction, "direction")
+        if o.shape != d.shape:
+            raise ValueError("origin and direction must both be [n, 3]")
+        for x, name in ((o, "origin"), (d, "direction")):
+            if x.device != dev:
+                raise ValueError(f"{name} must be on {dev} (got {x.device})")
+        n = o.shape[0]
+        raw = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        if n:
+            flags = L.VMX_QUERY_FETCH_PER_LANE if per_lane_fetch else 0
+            with _SideStream(dev, stream) as run:
+                self._check(self._lib.vmx_raycast_device(self._h, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                         n, C.c_void_p(raw.data_ptr()), flags,
+                                                         C.c_void_p(run.cuda_stream)))
+        return _rayhit_views(raw)
+
+    def raycast_camera(self, cam, opts, k=0, stream=None, per_lane_fetch=False):
+        """vmx_raycast_camera_device: Scene.raycast's device record for sample k's camera ray of every pixel (the ray
+        vmx_render traces and primary_ids reports), as a dict of [H, W, ...] views over one [H, W, 16] float32 tensor
+        on this scene's device, computed on `stream` (default torch.cuda.current_stream()), nothing synchronised."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        W, H = int(cam.image_res[0]), int(cam.image_res[1])
+        raw = torch.empty((H, W, 16), dtype=torch.float32, device=dev)
+        flags = L.VMX_QUERY_FETCH_PER_LANE if per_lane_fetch else 0
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_raycast_camera_device(self._h, C.byref(cam), C.byref(opts), int(k),
+                                                            C.c_void_p(raw.data_ptr()), flags,
+                                                            C.c_void_p(run.cuda_stream)))
+        return _rayhit_views(raw)
 
     # -- ray queries -----------------------------------------------------------
     QUERY_MODES = {"nearest": L.VMX_QUERY_NEAREST, "any": L.VMX_QUERY_ANY, "collision": L.VMX_QUERY_COLLISION}
