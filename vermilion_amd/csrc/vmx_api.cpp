@@ -845,6 +845,12 @@ int render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, floa
 #endif
     PathArrays pa{};
     IdQueue qi[3];
+    // one-phase shading (no two_phase): the bounce generations still go through dense ray records, all of them kept
+    // (reference sampling only: there one path in seven goes on, and the gathered 8-byte hit records were a quarter of
+    // k_shade<1>'s traffic — 5.9 -> 5.2 ms on the bench frame.  Under `corrected` sampling nearly every path goes on, and
+    // records arrive in the order the rays FINISH, which scatters the state reads and writes that the id queue's order
+    // keeps nearly sequential: measured 243 -> 328 ms of shading per 64-spp frame, so that form keeps hit[pid])
+    tn.bounce_records = split_any && !tn.two_phase && !count && !tn.pool && fr.r2scale == 10.0f;
     int tb = 1, tbb = 1;  // blocks per CU of the trace kernel: camera rays, bounce rays
     if (split_any) {
         rc = ensure_paths(sc, (size_t)n_pad_max * smax, pa, qi);
@@ -855,7 +861,7 @@ int render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, floa
         HIP_TRY((hipError_t)query_trace_q_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_primary + 1) * 512, count, false,
                                                         tn.sorted, fr.elide_dead != 0, &tb));
         HIP_TRY((hipError_t)query_trace_q_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_bounce + 1) * 512, count, true,
-                                                        tn.sorted || (!tn.two_phase && !count && !tn.pool && fr.r2scale == 10.0f), false, &tbb));
+                                                        tn.sorted || tn.bounce_records, false, &tbb));
         if (tb < 1 || tbb < 1) return fail(VMX_ERR_HIP, "trace kernel does not fit on a CU");
 #ifdef VMX_AB_KERNELS
         // A/B library only: cap the bounce kernel's blocks per CU (how much of its time is latency hiding:
@@ -883,12 +889,6 @@ int render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, floa
             return fail(VMX_ERR_NOMEM, "hipMalloc failed for the two-phase shading lists");
         ws.full_words = words, ws.full_tmp_bytes = tmp;
     }
-    // one-phase shading (no two_phase): the bounce generations still go through dense ray records, all of them kept
-    // (reference sampling only: there one path in seven goes on, and the gathered 8-byte hit records were a quarter of
-    // k_shade<1>'s traffic — 5.9 -> 5.2 ms on the bench frame.  Under `corrected` sampling nearly every path goes on, and
-    // records arrive in the order the rays FINISH, which scatters the state reads and writes that the id queue's order
-    // keeps nearly sequential: measured 243 -> 328 ms of shading per 64-spp frame, so that form keeps hit[pid])
-    tn.bounce_records = split_any && !tn.two_phase && !count && !tn.pool && fr.r2scale == 10.0f;
     if (split_any && (tn.sorted || tn.bounce_records)) {
         // every path of a pass may need a record; each wave of the launch leaves at most the tail of one chunk of 256 unused
         // (camera-ray records are 32 bytes, bounce-ray records 16)

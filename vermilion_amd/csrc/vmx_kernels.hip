@@ -258,14 +258,157 @@ __device__ __forceinline__ void box_net_exact(float t0x, float t0y, float t0z, f
     tfar = sel_min(sel_min(bx, by), bz);
 }
 
-// ---------------------------------------------------------------------------
-// BVH::getIntersection, nearest hit (bvh.cpp:47-145) + Triangle::getIntersection
-// (triangle.cpp:4-54).  `stk` points at this lane's column of the wave's LDS stack.
-// ---------------------------------------------------------------------------
 // (per-lane traversal stack helpers, defined with the persistent kernels below)
 __device__ __forceinline__ void stack_push(uint2 *stk, uint2 *ovf, int lds_entries, int sp, uint2 e);
 __device__ __forceinline__ uint2 stack_pop(const uint2 *stk, const uint2 *ovf, int lds_entries, int sp);
 
+// ---------------------------------------------------------------------------
+// The traversal primitives: the reference's tests (triangle.cpp:4-54, bbox.cpp:70-83, bvh.cpp:61-134), each written
+// down ONCE.  Every traversal kernel — k_paths, k_trace_w, k_trace_q, k_query, bvh_nearest, and the A/B library's
+// k_trace_pool — calls these; the operation order of each expression is the contract with the oracle (bit-identical
+// results), so a change here is a change everywhere.  The one other statement of the same arithmetic is the assembly
+// loop uniform_descent.
+// k_trace_q and bvh_nearest share the triangle tests only: their stack has no bottom entry and their lanes carry a
+// `cur_near`, so they keep a ray start, node step and pop of their own.
+// ---------------------------------------------------------------------------
+// Lane states of the persistent kernels, kept in the node reference itself.  Inner references are the values below
+// kPop; leaf references have bit 31; these three lie between and are never valid inner indices.
+constexpr uint32_t kIdle = 0x7FFFFFFFu;    // the lane is not traversing
+constexpr uint32_t kBottom = 0x7FFFFFFEu;  // ref of the stack's level-0 entry (near = -inf): popping it ends the ray
+constexpr uint32_t kPop = 0x7FFFFFFDu;     // the lane must pop its next node
+
+// Triangle::getIntersection's four rejections (triangle.cpp:25,34,40,44)
+__device__ __forceinline__ bool tri_accept(float det, float u, float v, float dist) {
+    // (det < 1e-8 && det > -1e-8) in double  <=>  |det| <= float(1e-8)  (float(1e-8) < 1e-8)
+    const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
+    const bool u_out = (u < 0.0f) || (u > 1.0f);
+    const bool v_out = (v < 0.0f) || (u + v > 1.0f);
+    return !parallel && !u_out && !v_out && (dist > 0.0f);
+}
+// Moeller-Trumbore on a triangle record q0 = (v0, e1.x)  q1 = (e1.yz, e2.xy)  e2z.  The caller keeps
+// `if (hit && dist < best)`: strict <, the first triangle tested wins ties (bvh.cpp:90).
+__device__ __forceinline__ bool tri_test(float4 q0, float4 q1, float e2z, float ox, float oy, float oz, float dx, float dy,
+                                         float dz, float &dist) {
+    const float e1x = q0.w, e1y = q1.x, e1z = q1.y, e2x = q1.z, e2y = q1.w;
+    float pvx, pvy, pvz;
+    cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
+    const float det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
+    const float inv_det = 1.0f / det;
+    const float tx = ox - q0.x, ty = oy - q0.y, tz = oz - q0.z;
+    const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
+    float qx, qy, qz;
+    cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
+    const float v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
+    dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
+    return tri_accept(det, u, v, dist);
+}
+// The same on a camera-relative record (k_camera_tables): a = (e1, e2.x)  b = (e2.yz, tvec.xy)  c = (tvec.z, qvec)
+// cd = dot(e2, qvec)
+__device__ __forceinline__ bool tri_test_cam(float4 a, float4 b, float4 c, float cd, float dx, float dy, float dz,
+                                             float &dist) {
+    float pvx, pvy, pvz;
+    cross3(dx, dy, dz, a.w, b.x, b.y, pvx, pvy, pvz);
+    const float det = dot3(a.x, a.y, a.z, pvx, pvy, pvz);
+    const float inv_det = 1.0f / det;
+    const float u = dot3(b.z, b.w, c.x, pvx, pvy, pvz) * inv_det;
+    const float v = dot3(dx, dy, dz, c.y, c.z, c.w) * inv_det;
+    dist = cd * inv_det;
+    return tri_accept(det, u, v, dist);
+}
+// A leaf reference carries its own progress: the next triangle is start + 1, count - 1; after the last one the lane pops
+__device__ __forceinline__ uint32_t leaf_advance(uint32_t cur) {
+    return (((cur >> kLeafCountShift) & 31u) == 1u) ? kPop : cur + (1u - (1u << kLeafCountShift));
+}
+
+// Both child boxes of an inner-node record (lo0, hi0, lo1, hi1 in q0..q2): entry and exit distances (bbox.cpp:70-83)
+template <bool EXACT>
+__device__ __forceinline__ void child_boxes(float4 q0, float4 q1, float4 q2, float ox, float oy, float oz, float ix, float iy,
+                                            float iz, float &tn0, float &tf0, float &tn1, float &tf1) {
+    const float a0 = (q0.x - ox) * ix, a1 = (q0.y - oy) * iy, a2 = (q0.z - oz) * iz;
+    const float a3 = (q0.w - ox) * ix, a4 = (q1.x - oy) * iy, a5 = (q1.y - oz) * iz;
+    const float b0 = (q1.z - ox) * ix, b1 = (q1.w - oy) * iy, b2 = (q2.x - oz) * iz;
+    const float b3 = (q2.y - ox) * ix, b4 = (q2.z - oy) * iy, b5 = (q2.w - oz) * iz;
+    if (EXACT) {
+        box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
+        box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
+    } else {
+        box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
+        box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
+    }
+}
+// Same with (lo - o), (hi - o) already formed (k_camera_tables)
+template <bool EXACT>
+__device__ __forceinline__ void child_boxes_rel(float4 q0, float4 q1, float4 q2, float ix, float iy, float iz, float &tn0,
+                                                float &tf0, float &tn1, float &tf1) {
+    const float a0 = q0.x * ix, a1 = q0.y * iy, a2 = q0.z * iz, a3 = q0.w * ix, a4 = q1.x * iy, a5 = q1.y * iz;
+    const float b0 = q1.z * ix, b1 = q1.w * iy, b2 = q2.x * iz, b3 = q2.y * ix, b4 = q2.z * iy, b5 = q2.w * iz;
+    if (EXACT) {
+        box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
+        box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
+    } else {
+        box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
+        box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
+    }
+}
+
+// Nearer child first (bvh.cpp:103-132).  Both hit: the strictly closer right child, else the left, is next and the
+// other one is handed to `push` (farther first, bvh.cpp:120: the caller's own stack store); one hit: that child.
+// Returns the next reference, or kPop if no child was hit or the child taken directly fails `near > t` (bvh.cpp:69).
+// Two forms, one per instruction-level shape; they decide alike.  This one is plain booleans (k_trace_w<1>, k_query,
+// k_trace_pool):
+template <class Push>
+__device__ __forceinline__ uint32_t choose_child(float tn0, float tf0, float tn1, float tf1, uint32_t lref, uint32_t rref,
+                                                 float best, Push push) {
+    const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
+    const bool both = h0 && h1;
+    const bool go_right = h1 && (!h0 || tn1 < tn0);
+    if (both) push(make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1)));
+    const float near = go_right ? tn1 : tn0;
+    return (!(h0 || h1) || near > best) ? kPop : (go_right ? rref : lref);
+}
+// ... and this one takes the compares as lane masks (v_cmp into SGPR pairs), combines them with scalar ALU ops and hands
+// them back to the lanes as conditions (k_paths, k_trace_w<0>): written with &&/|| hipcc evaluates part of this under
+// temporary exec masks (fcmp predicates: 5 = ordered <=, 4 = ordered <, 2 = ordered >)
+template <class Push>
+__device__ __forceinline__ uint32_t choose_child_masks(float tn0, float tf0, float tn1, float tf1, uint32_t lref,
+                                                       uint32_t rref, float best, Push push) {
+    const unsigned long long m0 = __builtin_amdgcn_fcmpf(tn0, tf0, 5), m1 = __builtin_amdgcn_fcmpf(tn1, tf1, 5);
+    const unsigned long long m_right = m1 & (~m0 | __builtin_amdgcn_fcmpf(tn1, tn0, 4));
+    const bool both = __builtin_amdgcn_inverse_ballot_w64(m0 & m1);
+    const bool go_right = __builtin_amdgcn_inverse_ballot_w64(m_right);
+    if (both) push(make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1)));
+    const float near = go_right ? tn1 : tn0;
+    const bool popn = __builtin_amdgcn_inverse_ballot_w64(~(m0 | m1) | __builtin_amdgcn_fcmpf(near, best, 2));
+    return popn ? kPop : (go_right ? rref : lref);
+}
+
+// Pops until an entry passes `near > t` (bvh.cpp:69) and returns its reference.  Level 0 holds the bottom entry
+// (ref kBottom, near = -inf), which always passes: a finished ray falls out of the loop with kBottom.
+__device__ __forceinline__ uint32_t pop_to_next(const uint2 *stk, const uint2 *ovf, int lds_entries, int &sp, float best) {
+    uint2 e;
+    do {
+        --sp;
+        e = stack_pop(stk, ovf, lds_entries, sp);
+    } while (__uint_as_float(e.y) > best);
+    return e.x;
+}
+
+// Start of a ray's traversal above the bottom entry.  `limit` is 999999999.f (bvh.cpp:48) or a query's bound.
+// (The caller sets its `exact` flag itself, `!(finite3(1/d) && finite3(o))`: behind a call boundary hipcc merges the two
+// finite tests into one block, which changes the register allocation of k_trace_w<1> and k_query.)
+__device__ __forceinline__ void ray_start(float dx, float dy, float dz, uint32_t root_ref, float limit, float &ix, float &iy,
+                                          float &iz, float &best, int &slot, int &sp, uint32_t &cur) {
+    ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;  // Ray.h:10
+    best = limit;
+    slot = -1;
+    sp = 1;
+    cur = root_ref;  // its near value, -9999999 (bvh.cpp:59), passes `near > t` for any limit > 0
+}
+
+// ---------------------------------------------------------------------------
+// BVH::getIntersection, nearest hit (bvh.cpp:47-145) + Triangle::getIntersection
+// (triangle.cpp:4-54).  `stk` points at this lane's column of the wave's LDS stack.
+// ---------------------------------------------------------------------------
 template <bool COUNT>
 __device__ __forceinline__ void bvh_nearest(const SceneDev &sc, float ox, float oy, float oz, float dx,
                                             float dy, float dz, uint2 *stk, float &best_out,
@@ -299,22 +442,8 @@ __device__ __forceinline__ void bvh_nearest(const SceneDev &sc, float ox, float 
                 const uint32_t ti = (first + i) * 3;
                 const float4 a = tris[ti], b = tris[ti + 1], c = tris[ti + 2];
                 if (COUNT) cnt.tris++;
-                const float e1x = a.w, e1y = b.x, e1z = b.y, e2x = b.z, e2y = b.w, e2z = c.x;
-                float px, py, pz;
-                cross3(dx, dy, dz, e2x, e2y, e2z, px, py, pz);
-                const float det = dot3(e1x, e1y, e1z, px, py, pz);
-                // (det < 1e-8 && det > -1e-8) in double  <=>  |det| <= float(1e-8)  (float(1e-8) < 1e-8)
-                const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                const float inv_det = 1.0f / det;
-                const float tx = ox - a.x, ty = oy - a.y, tz = oz - a.z;
-                const float u = dot3(tx, ty, tz, px, py, pz) * inv_det;
-                const bool u_out = (u < 0.0f) || (u > 1.0f);
-                float qx, qy, qz;
-                cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                const float v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                const float dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
-                const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
+                float dist;
+                const bool hit = tri_test(a, b, c.x, ox, oy, oz, dx, dy, dz, dist);
                 if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                     best = dist;
                     slot = (int)(first + i);
@@ -1278,7 +1407,6 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
     // lane state
     // traversal state as in k_trace_w: `cur` = node reference, kIdle while the lane is not traversing
     // (no path, or traversal finished and the path waits for shading); stack level 0 = bottom entry
-    constexpr uint32_t kIdle = 0x7FFFFFFFu, kBottom = 0x7FFFFFFEu, kPop = 0x7FFFFFFDu;
     bool has = false, exact = false, is_ray = false;
     Path P;
     float ix = 0.f, iy = 0.f, iz = 0.f, best = 0.f;
@@ -1289,13 +1417,9 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
     Tally tl = {{0, 0}, {0, 0}, {0, 0}};
 
     auto start_traversal = [&]() {
-        ix = 1.0f / P.dx, iy = 1.0f / P.dy, iz = 1.0f / P.dz;  // Ray.h:10
+        ray_start(P.dx, P.dy, P.dz, sc.root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
         exact = !(finite3(ix, iy, iz) && finite3(P.ox, P.oy, P.oz));
         is_ray = (P.depth == 0) || finite3(P.dx, P.dy, P.dz);
-        best = 999999999.f;  // bvh.cpp:48
-        slot = -1;
-        sp = 1;
-        cur = sc.root_ref;  // its near value, -9999999 (bvh.cpp:59), passes `near > t`
     };
 
     for (;;) {
@@ -1397,6 +1521,10 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
         if (__builtin_amdgcn_ballot_w64(has) == 0) break;
         // ---- 3. 8 traversal steps (bvh.cpp:61-134), the step of k_trace_w (see there) with counters:
         //         every traversing lane does its triangle step or its inner-node step
+        auto push = [&](uint2 e) {
+            stack_push(stk, ovf, lds_entries, sp, e);
+            ++sp;
+        };
         auto step = [&](auto exact_tag) {
             constexpr bool EXACT = decltype(exact_tag)::value;
             // the node or triangle record of every traversing lane, fetched quad-cooperatively in one phase
@@ -1411,69 +1539,27 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                     if (P.depth == 0) c0.inner++;
                     else c1.inner++;
                 }
-                const float a0 = (q0.x - P.ox) * ix, a1 = (q0.y - P.oy) * iy, a2 = (q0.z - P.oz) * iz;
-                const float a3 = (q0.w - P.ox) * ix, a4 = (q1.x - P.oy) * iy, a5 = (q1.y - P.oz) * iz;
-                const float b0 = (q1.z - P.ox) * ix, b1 = (q1.w - P.oy) * iy, b2 = (q2.x - P.oz) * iz;
-                const float b3 = (q2.y - P.ox) * ix, b4 = (q2.z - P.oy) * iy, b5 = (q2.w - P.oz) * iz;
                 float tn0, tf0, tn1, tf1;
-                if (EXACT) {
-                    box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                } else {
-                    box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                }
-                const uint32_t lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
-                const unsigned long long m0 = __builtin_amdgcn_fcmpf(tn0, tf0, 5), m1 = __builtin_amdgcn_fcmpf(tn1, tf1, 5);
-                const unsigned long long m_right = m1 & (~m0 | __builtin_amdgcn_fcmpf(tn1, tn0, 4));
-                const bool both = __builtin_amdgcn_inverse_ballot_w64(m0 & m1);
-                const bool go_right = __builtin_amdgcn_inverse_ballot_w64(m_right);
-                if (both) {
-                    stack_push(stk, ovf, lds_entries, sp,
-                               make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1)));
-                    ++sp;
-                }
-                const float near = go_right ? tn1 : tn0;
-                const bool popn = __builtin_amdgcn_inverse_ballot_w64(~(m0 | m1) | __builtin_amdgcn_fcmpf(near, best, 2));
-                cur = popn ? kPop : (go_right ? rref : lref);
+                child_boxes<EXACT>(q0, q1, q2, P.ox, P.oy, P.oz, ix, iy, iz, tn0, tf0, tn1, tf1);
+                cur = choose_child_masks(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, push);
             } else if ((int)cur < 0) {
                 // one triangle (triangle.cpp:4-54); the leaf ref itself carries the progress
-                const float4 a = q0, b = q1;
-                const float e2z = q2.x;
                 if (COUNT) {
                     if (P.depth == 0) c0.tris++;
                     else c1.tris++;
                 }
-                const float e1x = a.w, e1y = b.x, e1z = b.y, e2x = b.z, e2y = b.w;
-                float pvx, pvy, pvz;
-                cross3(P.dx, P.dy, P.dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                const float det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                const float inv_det = 1.0f / det;
-                const float tx = P.ox - a.x, ty = P.oy - a.y, tz = P.oz - a.z;
-                const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                const bool u_out = (u < 0.0f) || (u > 1.0f);
-                float qx, qy, qz;
-                cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                const float v = dot3(P.dx, P.dy, P.dz, qx, qy, qz) * inv_det;
-                const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                const float dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
-                const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
+                float dist;
+                const bool hit = tri_test(q0, q1, q2.x, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, dist);
                 if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                     best = dist;
                     slot = (int)(cur & kLeafStartMask);
                 }
-                cur = (((cur >> kLeafCountShift) & 31u) == 1u) ? kPop : cur + (1u - (1u << kLeafCountShift));
+                cur = leaf_advance(cur);
             }
             if (cur == kPop) {
-                // pop until an entry passes `near > t` (bvh.cpp:69); the bottom entry always does and
-                // ends the traversal: the lane then waits for shading
-                uint2 e;
-                do {
-                    --sp;
-                    e = stack_pop(stk, ovf, lds_entries, sp);
-                } while (__uint_as_float(e.y) > best);
-                cur = e.x == kBottom ? kIdle : e.x;
+                // the bottom entry ends the traversal: the lane then waits for shading
+                const uint32_t ref = pop_to_next(stk, ovf, lds_entries, sp, best);
+                cur = ref == kBottom ? kIdle : ref;
             }
         };
         if (__builtin_amdgcn_ballot_w64(exact && cur != kIdle) != 0) {
@@ -1780,38 +1866,18 @@ k_trace_q(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa,
             if (__builtin_amdgcn_ballot_w64(has) == 0) break;
             bool need_next = false, carry = false;
             if (at_leaf) {
-                float det, inv_det, u, v, dist;
+                float dist;
+                bool hit;
                 if (SRC == 0) {
                     const uint32_t ti = (cur & kLeafStartMask) * 4;
                     const float4 a = tris[ti], b = tris[ti + 1], c = tris[ti + 2], e = tris[ti + 3];
-                    // a = (e1, e2.x)  b = (e2.yz, tvec.xy)  c = (tvec.z, qvec)  e.x = dot(e2, qvec)
-                    float pvx, pvy, pvz;
-                    cross3(dx, dy, dz, a.w, b.x, b.y, pvx, pvy, pvz);
-                    det = dot3(a.x, a.y, a.z, pvx, pvy, pvz);
-                    inv_det = 1.0f / det;
-                    u = dot3(b.z, b.w, c.x, pvx, pvy, pvz) * inv_det;
-                    v = dot3(dx, dy, dz, c.y, c.z, c.w) * inv_det;
-                    dist = e.x * inv_det;
+                    hit = tri_test_cam(a, b, c, e.x, dx, dy, dz, dist);
                 } else {
                     const uint32_t ti = (cur & kLeafStartMask) * 3;
                     const float4 a = tris[ti], b = tris[ti + 1], c = tris[ti + 2];
-                    const float e1x = a.w, e1y = b.x, e1z = b.y, e2x = b.z, e2y = b.w, e2z = c.x;
-                    float pvx, pvy, pvz;
-                    cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                    det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                    inv_det = 1.0f / det;
-                    const float tx = ox - a.x, ty = oy - a.y, tz = oz - a.z;
-                    u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                    float qx, qy, qz;
-                    cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                    v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                    dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
+                    hit = tri_test(a, b, c.x, ox, oy, oz, dx, dy, dz, dist);
                 }
                 if (COUNT && counted) cn.tris++;
-                const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                const bool u_out = (u < 0.0f) || (u > 1.0f);
-                const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
                 if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                     best = dist;
                     slot = (int)(cur & kLeafStartMask);
@@ -2069,7 +2135,8 @@ __device__ __forceinline__ uint32_t uniform_descent(int &sp, uint32_t &cur, floa
         // ---- uniform leaf (triangle.cpp:4-54 on the camera-relative records of k_camera_tables): every traversing lane
         // tests every triangle of the leaf, the record comes through the scalar cache into s[36:51]
         //   s36-38 e1   s39-41 e2   s42-44 tvec = o - v0   s45-47 qvec = cross(tvec, e1)   s48 dot(e2, qvec)
-        // same operations in the same order as the general step; then the uniform pop above
+        // same operations in the same order as the general step (tri_test_cam is the C++ statement of this arithmetic);
+        // then the uniform pop above
         "9:\n\t"
         "s_and_b32 %[sidx], %[scur], 0x3ffffff\n\t"         // leaf slot of the first triangle
         "s_bfe_u32 %[cnt], %[scur], 0x5001a\n\t"            // triangles in the leaf (5 bits at 26)
@@ -2193,7 +2260,6 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
     float2 *__restrict__ hit_out = (float2 *)pa.hit;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t kReserve = wk.reserve;
-    constexpr uint32_t kIdle = 0x7FFFFFFFu, kBottom = 0x7FFFFFFEu, kPop = 0x7FFFFFFDu;  // never valid inner indices
     const uint32_t nsrc = wk.nsrc, refill_min = wk.refill_min;
     const uint32_t band_slots = wk.band_slots, band_items = wk.band_items;
     const uint32_t root_ref = sc.root_ref;
@@ -2261,6 +2327,10 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
     // base of the node table the wave-uniform steps of this batch read: the wave's octant copy if its
     // rays share an octant (OCT), else the plain copy; records are addressed by a 32-bit byte offset
     const char *uni_base = (const char *)inner;
+    auto push = [&](uint2 e) {
+        stack_push(stk, ovf, lds_entries, sp, e);
+        ++sp;
+    };
     auto step = [&](auto exact_tag, auto oct_tag) {
         constexpr bool EXACT = decltype(exact_tag)::value;  // NaN-exact box form
         constexpr bool OCT = decltype(oct_tag)::value;      // uniform steps read near-plane-first records
@@ -2283,170 +2353,71 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                               lane, q0, q1, q2, q3);
             if (cur != kIdle) {
                 if (!leaf) {
-                    const float a0 = (q0.x - ox) * ix, a1 = (q0.y - oy) * iy, a2 = (q0.z - oz) * iz;
-                    const float a3 = (q0.w - ox) * ix, a4 = (q1.x - oy) * iy, a5 = (q1.y - oz) * iz;
-                    const float b0 = (q1.z - ox) * ix, b1 = (q1.w - oy) * iy, b2 = (q2.x - oz) * iz;
-                    const float b3 = (q2.y - ox) * ix, b4 = (q2.z - oy) * iy, b5 = (q2.w - oz) * iz;
                     float tn0, tf0, tn1, tf1;
-                    if (EXACT) {
-                        box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                        box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                    } else {
-                        box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                        box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                    }
-                    const uint32_t lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
-                    const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
-                    const bool both = h0 && h1;
-                    const bool go_right = h1 && (!h0 || tn1 < tn0);  // both: the strictly closer right child; one: that child
-                    if (both) {
-                        const uint2 e = make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1));
-                        stack_push(stk, ovf, lds_entries, sp, e);
-                        ++sp;
-                    }
-                    const float near = go_right ? tn1 : tn0;
-                    // no child hit, or the child taken directly fails `near > t` (bvh.cpp:69): pop
-                    cur = (!(h0 || h1) || near > best) ? kPop : (go_right ? rref : lref);
+                    child_boxes<EXACT>(q0, q1, q2, ox, oy, oz, ix, iy, iz, tn0, tf0, tn1, tf1);
+                    cur = choose_child(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, push);
                 } else {
-                    // one triangle of the leaf (triangle.cpp:4-54): q0 = (v0, e1.x) q1 = (e1.yz, e2.xy) q2.x = e2.z
-                    const float e1x = q0.w, e1y = q1.x, e1z = q1.y, e2x = q1.z, e2y = q1.w, e2z = q2.x;
-                    float pvx, pvy, pvz;
-                    cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                    const float det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                    const float inv_det = 1.0f / det;
-                    const float tx = ox - q0.x, ty = oy - q0.y, tz = oz - q0.z;
-                    const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                    float qx, qy, qz;
-                    cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                    const float v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                    const float dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
-                    const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                    const bool u_out = (u < 0.0f) || (u > 1.0f);
-                    const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                    const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
+                    // one triangle of the leaf (triangle.cpp:4-54)
+                    float dist;
+                    const bool hit = tri_test(q0, q1, q2.x, ox, oy, oz, dx, dy, dz, dist);
                     if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                         best = dist;
                         slot = (int)(cur & kLeafStartMask);
                     }
-                    cur = (((cur >> kLeafCountShift) & 31u) == 1u) ? kPop : cur + (1u - (1u << kLeafCountShift));
+                    cur = leaf_advance(cur);
                 }
             }
-        } else
-        // inner references are the values below kPop; leaf references have bit 31; kPop/kBottom/kIdle lie between
-        if (cur < kPop) {
-            // ---- inner node: both children boxes (bbox.cpp:70-83), nearer child first (bvh.cpp:103-132)
-            float tn0, tf0, tn1, tf1;
-            uint32_t lref, rref;
-            const uint32_t cur0 = __builtin_amdgcn_readfirstlane(cur);
-            if (SRC == 0 && !EXACT && __builtin_amdgcn_ballot_w64(cur != cur0) == 0) {
-                // every lane of this step is at the same node: one fetch through the scalar cache,
-                // and the products take the record straight from SGPRs
-                typedef float f32x4 __attribute__((ext_vector_type(4)));
-                typedef const __attribute__((address_space(4))) f32x4 *scalar_ptr;
-                const scalar_ptr rec = (scalar_ptr)(uintptr_t)(uni_base + (uint32_t)(cur0 << 6));
-                const f32x4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-                if (OCT) {  // near planes first in this octant's copy: no min/max pairs
-                    tn0 = vmax3(r0.x * ix, r0.y * iy, r0.z * iz);
-                    tf0 = vmin3(r0.w * ix, r1.x * iy, r1.y * iz);
-                    tn1 = vmax3(r1.z * ix, r1.w * iy, r2.x * iz);
-                    tf1 = vmin3(r2.y * ix, r2.z * iy, r2.w * iz);
+        } else {
+            // ---- camera rays: inner references are the values below kPop, leaf references have bit 31
+            if (cur < kPop) {
+                // ---- inner node: both children boxes (bbox.cpp:70-83), nearer child first (bvh.cpp:103-132)
+                float tn0, tf0, tn1, tf1;
+                uint32_t lref, rref;
+                const uint32_t cur0 = __builtin_amdgcn_readfirstlane(cur);
+                if (!EXACT && __builtin_amdgcn_ballot_w64(cur != cur0) == 0) {
+                    // every lane of this step is at the same node: one fetch through the scalar cache,
+                    // and the products take the record straight from SGPRs
+                    typedef float f32x4 __attribute__((ext_vector_type(4)));
+                    typedef const __attribute__((address_space(4))) f32x4 *scalar_ptr;
+                    const scalar_ptr rec = (scalar_ptr)(uintptr_t)(uni_base + (uint32_t)(cur0 << 6));
+                    const f32x4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                    if (OCT) {  // near planes first in this octant's copy: no min/max pairs
+                        tn0 = vmax3(r0.x * ix, r0.y * iy, r0.z * iz);
+                        tf0 = vmin3(r0.w * ix, r1.x * iy, r1.y * iz);
+                        tn1 = vmax3(r1.z * ix, r1.w * iy, r2.x * iz);
+                        tf1 = vmin3(r2.y * ix, r2.z * iy, r2.w * iz);
+                    } else {
+                        box_net(r0.x * ix, r0.y * iy, r0.z * iz, r0.w * ix, r1.x * iy, r1.y * iz, tn0, tf0);
+                        box_net(r1.z * ix, r1.w * iy, r2.x * iz, r2.y * ix, r2.z * iy, r2.w * iz, tn1, tf1);
+                    }
+                    lref = __float_as_uint(r3.x), rref = __float_as_uint(r3.y);
                 } else {
-                    box_net(r0.x * ix, r0.y * iy, r0.z * iz, r0.w * ix, r1.x * iy, r1.y * iz, tn0, tf0);
-                    box_net(r1.z * ix, r1.w * iy, r2.x * iz, r2.y * ix, r2.z * iy, r2.w * iz, tn1, tf1);
+                    // (32-bit byte offset from a scalar base: the record tables are < 4 GB, and an index scaled in 64 bits
+                    // costs two 64-bit VALU operations per fetch)
+                    const float4 *rec = (const float4 *)((const char *)inner + (uint32_t)(cur << 6));
+                    const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
+                    const float2 q3 = *(const float2 *)(rec + 3);
+                    child_boxes_rel<EXACT>(q0, q1, q2, ix, iy, iz, tn0, tf0, tn1, tf1);
+                    lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
                 }
-                lref = __float_as_uint(r3.x), rref = __float_as_uint(r3.y);
-            } else {
-                // (32-bit byte offset from a scalar base: the record tables are < 4 GB, and an index scaled in 64 bits
-                // costs two 64-bit VALU operations per fetch)
-                const float4 *rec = (const float4 *)((const char *)inner + (uint32_t)(cur << 6));
-                const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
-                const float2 q3 = *(const float2 *)(rec + 3);
-                float a0, a1, a2, a3, a4, a5, b0, b1, b2, b3, b4, b5;
-                if (SRC == 0) {
-                    a0 = q0.x * ix, a1 = q0.y * iy, a2 = q0.z * iz, a3 = q0.w * ix, a4 = q1.x * iy, a5 = q1.y * iz;
-                    b0 = q1.z * ix, b1 = q1.w * iy, b2 = q2.x * iz, b3 = q2.y * ix, b4 = q2.z * iy, b5 = q2.w * iz;
-                } else {
-                    a0 = (q0.x - ox) * ix, a1 = (q0.y - oy) * iy, a2 = (q0.z - oz) * iz;
-                    a3 = (q0.w - ox) * ix, a4 = (q1.x - oy) * iy, a5 = (q1.y - oz) * iz;
-                    b0 = (q1.z - ox) * ix, b1 = (q1.w - oy) * iy, b2 = (q2.x - oz) * iz;
-                    b3 = (q2.y - ox) * ix, b4 = (q2.z - oy) * iy, b5 = (q2.w - oz) * iz;
-                }
-                if (EXACT) {
-                    box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                } else {
-                    box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                }
-                lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
-            }
-            // the compares as lane masks (v_cmp into SGPR pairs), combined with scalar ALU ops and handed
-            // back to the lanes as conditions: written with &&/|| hipcc evaluates part of this under
-            // temporary exec masks (fcmp predicates: 5 = ordered <=, 4 = ordered <, 2 = ordered >)
-            const unsigned long long m0 = __builtin_amdgcn_fcmpf(tn0, tf0, 5), m1 = __builtin_amdgcn_fcmpf(tn1, tf1, 5);
-            const unsigned long long m_right = m1 & (~m0 | __builtin_amdgcn_fcmpf(tn1, tn0, 4));
-            const bool both = __builtin_amdgcn_inverse_ballot_w64(m0 & m1);
-            const bool go_right = __builtin_amdgcn_inverse_ballot_w64(m_right);  // both: the strictly closer right child; one: that child
-            if (both) {
-                const uint2 e = make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1));
-                stack_push(stk, ovf, lds_entries, sp, e);
-                ++sp;
-            }
-            const float near = go_right ? tn1 : tn0;
-            // no child hit, or the child taken directly fails `near > t` (bvh.cpp:69): pop
-            const bool popn = __builtin_amdgcn_inverse_ballot_w64(~(m0 | m1) | __builtin_amdgcn_fcmpf(near, best, 2));
-            cur = popn ? kPop : (go_right ? rref : lref);
-                } else if ((int)cur < 0) {
-            // ---- one triangle of the leaf (triangle.cpp:4-54); the ref itself carries the progress
-            float det, inv_det, u, v, dist;
-            if (SRC == 0) {
+                // (the lane-mask form of the choice: the &&/|| form is evaluated partly under temporary exec masks here)
+                cur = choose_child_masks(tn0, tf0, tn1, tf1, lref, rref, best, push);
+            } else if ((int)cur < 0) {
+                // ---- one triangle of the leaf (triangle.cpp:4-54) from its camera-relative record
                 const uint32_t ti = (cur & kLeafStartMask) * 4;
                 const float4 a = tris[ti], b = tris[ti + 1], c = tris[ti + 2];
                 const float cd = ((const float *)tris)[ti * 4 + 12];
-                // a = (e1, e2.x)  b = (e2.yz, tvec.xy)  c = (tvec.z, qvec)  cd = dot(e2, qvec)
-                float pvx, pvy, pvz;
-                cross3(dx, dy, dz, a.w, b.x, b.y, pvx, pvy, pvz);
-                det = dot3(a.x, a.y, a.z, pvx, pvy, pvz);
-                inv_det = 1.0f / det;
-                u = dot3(b.z, b.w, c.x, pvx, pvy, pvz) * inv_det;
-                v = dot3(dx, dy, dz, c.y, c.z, c.w) * inv_det;
-                dist = cd * inv_det;
-            } else {
-                const uint32_t ti = (cur & kLeafStartMask) * 3;
-                const float4 a = tris[ti], b = tris[ti + 1];
-                const float e2z = ((const float *)tris)[ti * 4 + 8];
-                const float e1x = a.w, e1y = b.x, e1z = b.y, e2x = b.z, e2y = b.w;
-                float pvx, pvy, pvz;
-                cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                inv_det = 1.0f / det;
-                const float tx = ox - a.x, ty = oy - a.y, tz = oz - a.z;
-                u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                float qx, qy, qz;
-                cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
+                float dist;
+                const bool hit = tri_test_cam(a, b, c, cd, dx, dy, dz, dist);
+                if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
+                    best = dist;
+                    slot = (int)(cur & kLeafStartMask);
+                }
+                cur = leaf_advance(cur);
             }
-            const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-            const bool u_out = (u < 0.0f) || (u > 1.0f);
-            const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-            const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
-            if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
-                best = dist;
-                slot = (int)(cur & kLeafStartMask);
-            }
-            // next triangle: start + 1, count - 1; after the last one the lane pops
-            cur = (((cur >> kLeafCountShift) & 31u) == 1u) ? kPop : cur + (1u - (1u << kLeafCountShift));
         }
         if (cur == kPop) {
-            // pop until an entry passes `near > t` (bvh.cpp:69); level 0 holds the bottom entry
-            // (near = -inf), which always passes and ends the ray
-            uint2 e;
-            do {
-                --sp;
-                e = stack_pop(stk, ovf, lds_entries, sp);
-            } while (__uint_as_float(e.y) > best);
-            cur = e.x;
+            cur = pop_to_next(stk, ovf, lds_entries, sp, best);
             if (cur == kBottom) {
                 if (SORT) rflags |= 0x80000000u;  // settled at the next refill (the lane keeps t, slot, direction until then)
                 else hit_out[pid] = make_float2(best, __int_as_float(slot));
@@ -2520,12 +2491,8 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         }
                     }
                     if (valid) {
-                        ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;  // Ray.h:10
+                        ray_start(dx, dy, dz, root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
                         exact = !(finite3(ix, iy, iz) && finite3(ox, oy, oz));
-                        best = 999999999.f;  // bvh.cpp:48
-                        slot = -1;
-                        sp = 1;
-                        cur = root_ref;  // its near value, -9999999 (bvh.cpp:59), passes `near > t`
                     }
                 }
             }
@@ -3481,43 +3448,42 @@ int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk
     return launch_status();
 }
 
+// The instantiation that traces a pass: the production form k_trace_w (sorted: k_trace_w<.., SORT>; live: the
+// ELIDE_DEAD list form of the camera kernel), with counters the first form k_trace_q (same tests per ray).
+// launch_trace_q launches what these name and query_trace_q_blocks_per_cu sizes the persistent grid and the record-list
+// padding from its occupancy: the figure is by construction that of the kernel launched.
+using TraceWKernel = void (*)(SceneDev, FrameDev, WorkDev, PathArrays);
+using TraceQKernel = void (*)(SceneDev, FrameDev, WorkDev, PixelStateDev, PathArrays, DevCounters *);
+static TraceWKernel trace_w_kernel(bool from_queue, bool sorted, bool live) {
+    if (from_queue) {
+        if (sorted) return k_trace_w<1, false, true>;
+        return k_trace_w<1>;
+    }
+    if (sorted) {
+        if (live) return k_trace_w<0, true, true>;
+        return k_trace_w<0, false, true>;
+    }
+    if (live) return k_trace_w<0, true>;
+    return k_trace_w<0>;
+}
+static TraceQKernel trace_q_kernel(bool from_queue) {
+    if (from_queue) return k_trace_q<true, 1>;
+    return k_trace_q<true, 0>;
+}
+
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
                    DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     dim3 g(cfg.grid), b(cfg.block);
-    // production form: k_trace_w; with counters: the first form k_trace_q (same tests per ray)
-    if (!count) {
-        if (from_queue) {
-            if (wk.out_rec) hipLaunchKernelGGL((k_trace_w<1, false, true>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-            else hipLaunchKernelGGL((k_trace_w<1>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-        } else if (wk.out_rec) {
-            if (wk.live_ids) hipLaunchKernelGGL((k_trace_w<0, true, true>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-            else hipLaunchKernelGGL((k_trace_w<0, false, true>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-        } else if (wk.live_ids) hipLaunchKernelGGL((k_trace_w<0, true>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-        else hipLaunchKernelGGL((k_trace_w<0>), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
-    } else {
-        if (from_queue) hipLaunchKernelGGL((k_trace_q<true, 1>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, pa, counters);
-        else hipLaunchKernelGGL((k_trace_q<true, 0>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, pa, counters);
-    }
+    if (count) hipLaunchKernelGGL(trace_q_kernel(from_queue), g, b, cfg.lds_bytes, s, sc, fr, wk, px, pa, counters);
+    else hipLaunchKernelGGL(trace_w_kernel(from_queue, wk.out_rec != nullptr, wk.live_ids != nullptr), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
     return launch_status();
 }
 
-// occupancy of the exact instantiation launch_trace_q selects (sorted: k_trace_w<.., SORT>; live: the ELIDE_DEAD list
-// form of the camera kernel): the persistent grid and the record-list padding are sized from it
 int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks) {
     int a = 0;
-    hipError_t e;
-#define VMX_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, K, (int)block, lds_bytes)
-    if (count) {
-        e = from_queue ? VMX_OCC((k_trace_q<true, 1>)) : VMX_OCC((k_trace_q<true, 0>));
-    } else if (from_queue) {
-        e = sorted ? VMX_OCC((k_trace_w<1, false, true>)) : VMX_OCC((k_trace_w<1>));
-    } else if (sorted) {
-        e = live ? VMX_OCC((k_trace_w<0, true, true>)) : VMX_OCC((k_trace_w<0, false, true>));
-    } else {
-        e = live ? VMX_OCC((k_trace_w<0, true>)) : VMX_OCC((k_trace_w<0>));
-    }
-#undef VMX_OCC
+    const hipError_t e = count ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, trace_q_kernel(from_queue), (int)block, lds_bytes)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, trace_w_kernel(from_queue, sorted, live), (int)block, lds_bytes);
     if (blocks) *blocks = a;
     return (int)e;
 }

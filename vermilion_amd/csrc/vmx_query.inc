@@ -1,6 +1,7 @@
 // vmx_query.inc — k_query: device ray queries of explicit ray batches (vmx_query_device / vmx_query).
-// Included by vmx_kernels.hip (inside its namespace) so that it uses box_net / box_net_exact, stack_push / stack_pop,
-// quad_fetch_record and SceneDev exactly as the bounce traversal k_trace_w<1> does.
+// Included by vmx_kernels.hip (inside its namespace): its step is made of that file's traversal primitives — tri_test,
+// leaf_advance, child_boxes, choose_child, pop_to_next, ray_start — with quad_fetch_record and the stack_push / stack_pop
+// stack, the same functions the bounce traversal k_trace_w<1> calls.
 //
 // Three modes, one traversal (BVH::getIntersection, bvh.cpp:47-145):
 //   NEAREST   (occlusion == false)  `best` starts at L = min(tmax, 999999999.f) instead of 999999999.f (bvh.cpp:48)
@@ -54,7 +55,6 @@ k_query(SceneDev sc, QueryDev q, Cast... cast) {
     const char *rec_base = (const char *)sc.inner;
     const float4 *__restrict__ tris = (const float4 *)sc.tris;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    constexpr uint32_t kIdle = 0x7FFFFFFFu, kBottom = 0x7FFFFFFEu, kPop = 0x7FFFFFFDu;  // never valid inner indices
     const uint32_t n = q.n, kReserve = q.reserve, refill_min = q.refill_min, root_ref = sc.root_ref;
 
     uint32_t res_lo = 0, res_hi = 0;
@@ -102,48 +102,17 @@ k_query(SceneDev sc, QueryDev q, Cast... cast) {
         if (cur != kIdle) {
             if (!leaf) {
                 // ---- inner node: both child boxes (bbox.cpp:70-83), nearer child first (bvh.cpp:103-132)
-                const float a0 = (q0.x - ox) * ix, a1 = (q0.y - oy) * iy, a2 = (q0.z - oz) * iz;
-                const float a3 = (q0.w - ox) * ix, a4 = (q1.x - oy) * iy, a5 = (q1.y - oz) * iz;
-                const float b0 = (q1.z - ox) * ix, b1 = (q1.w - oy) * iy, b2 = (q2.x - oz) * iz;
-                const float b3 = (q2.y - ox) * ix, b4 = (q2.z - oy) * iy, b5 = (q2.w - oz) * iz;
                 float tn0, tf0, tn1, tf1;
-                if (EXACT) {
-                    box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                } else {
-                    box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                    box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                }
-                const uint32_t lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
-                const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
-                const bool both = h0 && h1;
-                const bool go_right = h1 && (!h0 || tn1 < tn0);  // both: the strictly closer right child; one: that child
-                if (both) {
-                    const uint2 e = make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1));
-                    stack_push(stk, ovf, lds_entries, sp, e);  // farther first (bvh.cpp:120)
+                child_boxes<EXACT>(q0, q1, q2, ox, oy, oz, ix, iy, iz, tn0, tf0, tn1, tf1);
+                cur = choose_child(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, [&](uint2 e) {
+                    stack_push(stk, ovf, lds_entries, sp, e);
                     ++sp;
-                }
-                const float near = go_right ? tn1 : tn0;
-                // no child hit, or the child taken directly fails `near > t` (bvh.cpp:69): pop
-                cur = (!(h0 || h1) || near > best) ? kPop : (go_right ? rref : lref);
+                });
             } else {
-                // ---- one triangle of the leaf (triangle.cpp:4-54): q0 = (v0, e1.x) q1 = (e1.yz, e2.xy) q2.x = e2.z
-                const float e1x = q0.w, e1y = q1.x, e1z = q1.y, e2x = q1.z, e2y = q1.w, e2z = q2.x;
-                float pvx, pvy, pvz;
-                cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                const float det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                const float inv_det = 1.0f / det;
-                const float tx = ox - q0.x, ty = oy - q0.y, tz = oz - q0.z;
-                const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                float qx, qy, qz;
-                cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                const float v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                const float dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
-                const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                const bool u_out = (u < 0.0f) || (u > 1.0f);
-                const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
-                const bool last = ((cur >> kLeafCountShift) & 31u) == 1u;
+                // ---- one triangle of the leaf (triangle.cpp:4-54)
+                float dist;
+                const bool hit = tri_test(q0, q1, q2.x, ox, oy, oz, dx, dy, dz, dist);
+                const uint32_t at = cur;
                 if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                     slot = (int)(cur & kLeafStartMask);
                     if (MODE == kQueryAny) {
@@ -152,20 +121,10 @@ k_query(SceneDev sc, QueryDev q, Cast... cast) {
                         best = dist;
                     }
                 }
-                // next triangle: start + 1, count - 1; after the last one the lane pops
-                if (MODE != kQueryAny || cur != kBottom) cur = last ? kPop : cur + (1u - (1u << kLeafCountShift));
+                if (MODE != kQueryAny || cur != kBottom) cur = leaf_advance(at);
             }
         }
-        if (cur == kPop) {
-            // pop until an entry passes `near > t` (bvh.cpp:69); level 0 holds the bottom entry
-            // (near = -inf), which always passes and ends the ray
-            uint2 e;
-            do {
-                --sp;
-                e = stack_pop(stk, ovf, lds_entries, sp);
-            } while (__uint_as_float(e.y) > best);
-            cur = e.x;
-        }
+        if (cur == kPop) cur = pop_to_next(stk, ovf, lds_entries, sp, best);
         if (cur == kBottom) {
             write_out(ray, slot, best);
             cur = kIdle;
@@ -215,12 +174,8 @@ k_query(SceneDev sc, QueryDev q, Cast... cast) {
                     }
                     if (valid) {
                         ray = item;
-                        ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;  // Ray.h:10
+                        ray_start(dx, dy, dz, root_ref, lim, ix, iy, iz, best, slot, sp, cur);
                         exact = !(finite3(ix, iy, iz) && finite3(ox, oy, oz));
-                        best = lim;
-                        slot = -1;
-                        sp = 1;
-                        cur = root_ref;  // its near value, -9999999 (bvh.cpp:59), passes `near > t` for any L > 0
                     } else {
                         write_out(item, -1, lim);  // the lane stays idle and takes the next item
                     }
@@ -284,52 +239,50 @@ k_raycast_finish(SceneDev sc, FrameDev fr, const float *__restrict__ o, const fl
     }
 }
 
-int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream) {
-    const dim3 g(cfg.grid), b(cfg.block);
-    hipStream_t s = (hipStream_t)stream;
-#define VMX_Q(M)                                                                                   \
-    if (quad) hipLaunchKernelGGL((k_query<M, true>), g, b, cfg.lds_bytes, s, sc, q);              \
-    else hipLaunchKernelGGL((k_query<M, false>), g, b, cfg.lds_bytes, s, sc, q);
+// The instantiation of a (mode, fetch form): launch_query / launch_raycast_query launch it and
+// query_query_blocks_per_cu reports its occupancy, so the grid is sized from the kernel that runs.
+using QueryKernel = void (*)(SceneDev, QueryDev);
+using QueryCastKernel = void (*)(SceneDev, QueryDev, QueryCast);
+static QueryKernel query_kernel(uint32_t mode, bool quad) {
     if (mode == kQueryAny) {
-        VMX_Q(kQueryAny)
-    } else if (mode == kQueryCollision) {
-        VMX_Q(kQueryCollision)
-    } else {
-        VMX_Q(kQueryNearest)
+        if (quad) return k_query<kQueryAny, true>;
+        return k_query<kQueryAny, false>;
     }
-#undef VMX_Q
+    if (mode == kQueryCollision) {
+        if (quad) return k_query<kQueryCollision, true>;
+        return k_query<kQueryCollision, false>;
+    }
+    if (quad) return k_query<kQueryNearest, true>;
+    return k_query<kQueryNearest, false>;
+}
+static QueryCastKernel query_cast_kernel(bool camera, bool quad) {
+    if (camera) {
+        if (quad) return k_query<kQueryCastCamera, true, QueryCast>;
+        return k_query<kQueryCastCamera, false, QueryCast>;
+    }
+    if (quad) return k_query<kQueryCastRays, true, QueryCast>;
+    return k_query<kQueryCastRays, false, QueryCast>;
+}
+
+int launch_query(const SceneDev &sc, const QueryDev &q, uint32_t mode, bool quad, LaunchCfg cfg, void *stream) {
+    hipLaunchKernelGGL(query_kernel(mode, quad), dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, (hipStream_t)stream, sc, q);
     return launch_status();
 }
 
-// occupancy of the exact instantiation launch_query selects
 int query_query_blocks_per_cu(uint32_t block, uint32_t lds_bytes, uint32_t mode, bool quad, int *blocks) {
     int a = 0;
-    hipError_t e;
-#define VMX_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, K, (int)block, lds_bytes)
-    if (mode == kQueryAny) e = quad ? VMX_OCC((k_query<kQueryAny, true>)) : VMX_OCC((k_query<kQueryAny, false>));
-    else if (mode == kQueryCollision) e = quad ? VMX_OCC((k_query<kQueryCollision, true>)) : VMX_OCC((k_query<kQueryCollision, false>));
-    else if (mode == kQueryCastRays) e = quad ? VMX_OCC((k_query<kQueryCastRays, true, QueryCast>)) : VMX_OCC((k_query<kQueryCastRays, false, QueryCast>));
-    else if (mode == kQueryCastCamera) e = quad ? VMX_OCC((k_query<kQueryCastCamera, true, QueryCast>)) : VMX_OCC((k_query<kQueryCastCamera, false, QueryCast>));
-    else e = quad ? VMX_OCC((k_query<kQueryNearest, true>)) : VMX_OCC((k_query<kQueryNearest, false>));
-#undef VMX_OCC
+    const bool cast = mode == kQueryCastRays || mode == kQueryCastCamera;
+    const hipError_t e = cast ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, query_cast_kernel(mode == kQueryCastCamera, quad), (int)block, lds_bytes)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, query_kernel(mode, quad), (int)block, lds_bytes);
     if (blocks) *blocks = a;
     return (int)e;
 }
 
 int launch_raycast_query(const SceneDev &sc, const QueryDev &q, const FrameDev &fr, bool camera, bool quad, void *out,
                          LaunchCfg cfg, uint32_t finish_grid, void *stream) {
-    const dim3 g(cfg.grid), b(cfg.block);
     hipStream_t s = (hipStream_t)stream;
     const QueryCast c = {fr, (float *)out};
-#define VMX_QC(M)                                                                                   \
-    if (quad) hipLaunchKernelGGL((k_query<M, true, QueryCast>), g, b, cfg.lds_bytes, s, sc, q, c); \
-    else hipLaunchKernelGGL((k_query<M, false, QueryCast>), g, b, cfg.lds_bytes, s, sc, q, c);
-    if (camera) {
-        VMX_QC(kQueryCastCamera)
-    } else {
-        VMX_QC(kQueryCastRays)
-    }
-#undef VMX_QC
+    hipLaunchKernelGGL(query_cast_kernel(camera, quad), dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, s, sc, q, c);
     if (int e = launch_status()) return e;
     if (camera)
         hipLaunchKernelGGL(k_raycast_finish<1>, dim3(finish_grid), dim3(256), 0, s, sc, fr, nullptr, nullptr, q.n,

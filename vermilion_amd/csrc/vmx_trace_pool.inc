@@ -118,31 +118,15 @@ k_trace_pool(SceneDev sc, WorkDev wk, PathArrays pa) {
                 if (have) {
                     const float ox = a.x, oy = a.y, oz = a.z, best = a.w, ix = b.x, iy = b.y, iz = b.z;
                     int sp = (int)d.y;
-                    const float a0 = (q0.x - ox) * ix, a1 = (q0.y - oy) * iy, a2 = (q0.z - oz) * iz;
-                    const float a3 = (q0.w - ox) * ix, a4 = (q1.x - oy) * iy, a5 = (q1.y - oz) * iz;
-                    const float b0 = (q1.z - ox) * ix, b1 = (q1.w - oy) * iy, b2 = (q2.x - oz) * iz;
-                    const float b3 = (q2.y - ox) * ix, b4 = (q2.z - oy) * iy, b5 = (q2.w - oz) * iz;
                     float tn0, tf0, tn1, tf1;
-                    if (!(finite3(ix, iy, iz) && finite3(ox, oy, oz))) {
-                        box_net_exact(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                        box_net_exact(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                    } else {
-                        box_net(a0, a1, a2, a3, a4, a5, tn0, tf0);
-                        box_net(b0, b1, b2, b3, b4, b5, tn1, tf1);
-                    }
-                    const uint32_t lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
-                    const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
-                    const bool both = h0 && h1;
-                    const bool go_right = h1 && (!h0 || tn1 < tn0);
-                    if (both) {
-                        const uint2 e = make_uint2(go_right ? lref : rref, __float_as_uint(go_right ? tn0 : tn1));
+                    if (!(finite3(ix, iy, iz) && finite3(ox, oy, oz))) child_boxes<true>(q0, q1, q2, ox, oy, oz, ix, iy, iz, tn0, tf0, tn1, tf1);
+                    else child_boxes<false>(q0, q1, q2, ox, oy, oz, ix, iy, iz, tn0, tf0, tn1, tf1);
+                    uint32_t nxt = choose_child(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, [&](uint2 e) {
                         if (sp < L) stk[(size_t)sp * P + slot] = e;
                         else ovf[(size_t)slot * wk.overflow_entries + (sp - L)] = e;
                         ++sp;
-                    }
-                    const float near = go_right ? tn1 : tn0;
-                    uint32_t nxt = (!(h0 || h1) || near > best) ? kNone : (go_right ? rref : lref);
-                    if (nxt == kNone) nxt = pop(slot, sp, best);
+                    });
+                    if (nxt == kPop) nxt = pop(slot, sp, best);
                     ((float *)&sB[slot])[3] = __uint_as_float(nxt);
                     ((uint32_t *)&sD[slot])[1] = (uint32_t)sp;
                     const bool done = nxt == kNone;
@@ -165,28 +149,15 @@ k_trace_pool(SceneDev sc, WorkDev wk, PathArrays pa) {
                     const float ox = a.x, oy = a.y, oz = a.z, dx = cc.x, dy = cc.y, dz = cc.z;
                     float best = a.w;
                     int sp = (int)d.y;
-                    const float e1x = q0.w, e1y = q1.x, e1z = q1.y, e2x = q1.z, e2y = q1.w, e2z = q2.x;
-                    float pvx, pvy, pvz;
-                    cross3(dx, dy, dz, e2x, e2y, e2z, pvx, pvy, pvz);
-                    const float det = dot3(e1x, e1y, e1z, pvx, pvy, pvz);
-                    const float inv_det = 1.0f / det;
-                    const float tx = ox - q0.x, ty = oy - q0.y, tz = oz - q0.z;
-                    const float u = dot3(tx, ty, tz, pvx, pvy, pvz) * inv_det;
-                    float qx, qy, qz;
-                    cross3(tx, ty, tz, e1x, e1y, e1z, qx, qy, qz);
-                    const float v = dot3(dx, dy, dz, qx, qy, qz) * inv_det;
-                    const float dist = dot3(e2x, e2y, e2z, qx, qy, qz) * inv_det;
-                    const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
-                    const bool u_out = (u < 0.0f) || (u > 1.0f);
-                    const bool v_out = (v < 0.0f) || (u + v > 1.0f);
-                    const bool hit = !parallel && !u_out && !v_out && (dist > 0.0f);
+                    float dist;
+                    const bool hit = tri_test(q0, q1, q2.x, ox, oy, oz, dx, dy, dz, dist);
                     if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
                         best = dist;
                         ((float *)&sA[slot])[3] = best;
                         ((float *)&sC[slot])[3] = __int_as_float((int)(cur & kLeafStartMask));
                     }
-                    uint32_t nxt = (((cur >> kLeafCountShift) & 31u) == 1u) ? kNone : cur + (1u - (1u << kLeafCountShift));
-                    if (nxt == kNone) nxt = pop(slot, sp, best);
+                    uint32_t nxt = leaf_advance(cur);
+                    if (nxt == kPop) nxt = pop(slot, sp, best);
                     ((float *)&sB[slot])[3] = __uint_as_float(nxt);
                     ((uint32_t *)&sD[slot])[1] = (uint32_t)sp;
                     const bool done = nxt == kNone;
