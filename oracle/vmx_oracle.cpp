@@ -20,19 +20,17 @@
  *   Camera ctor / setPixelValue     core/camera/camera.cpp:34-81, 88-124
  * Each function below cites the lines it follows.
  *
- * PARITY UNPINNED.  The reference ships no tests, golden vectors or fixtures
- * (SURVEY.md §4), and its hot path cannot be compiled in this image: every
- * translation unit needs GLM (extern/glm is an empty, un-pinned submodule,
- * .gitmodules:7-9) and meshEngine/camera additionally need Assimp and
- * OpenImageIO headers; building it would need hand-written stand-ins for
- * those headers, which is not a reference build.  GLM's arithmetic is
- * therefore restated from its published generic (non-SIMD) code path
- * (0.9.9 series: dot = (x*x + y*y) + z*z, normalize = v * (1/sqrt(dot)),
- * cross, mat4*vec4 as (m0*x + m1*y) + (m2*z + m3*w), gtc rotate); libstdc++'s
- * <random> is used directly where the reference's RNG is wanted.  The only
- * reference-run observations available are the probe results recorded in
- * SURVEY.md (Appendix A-1/A-2/A-9, §8a-6); tests/test_oracle.py checks
- * this file against those.
+ * PINNED to the reference's own compiled code, GLM's arithmetic excepted.  The reference ships no tests, golden
+ * vectors or fixtures and none of its third-party headers (GLM is an empty, un-pinned submodule,
+ * .gitmodules:7-9; meshEngine/camera also need Assimp and OpenImageIO).  `make -C oracle ref` compiles its
+ * translation units unmodified against the stand-ins of oracle/ref_standin/ and tests/test_ref_pin.py compares
+ * this file with that build bit for bit (tree, getIntersection, RayCast, RayCastCollision, VermiTexture::Sample,
+ * Radiance, saveFrame).  GLM's arithmetic stays a reading, the same one in the stand-in and here: its published
+ * generic (non-SIMD) code path (0.9.9 series: dot = (x*x + y*y) + z*z, normalize = v * (1/sqrt(dot)), cross,
+ * mat4*vec4 as (m0*x + m1*y) + (m2*z + m3*w), gtc rotate); libstdc++'s <random> is used directly where the
+ * reference's RNG is wanted.  The two Render loops cannot be driven from outside (seeded from random_device /
+ * time(0)); for them the reference-run observations recorded in SURVEY.md (Appendix A-1/A-2/A-9, §8a-6) remain
+ * what tests/test_oracle.py checks this file against.
  *
  * Build: see oracle/Makefile.  The parity build is -O2 -ffp-contract=off
  * (every float operation rounds once, no FMA), which is what the HIP kernels
@@ -513,6 +511,7 @@ struct PathStats {
     uint64_t rays_primary = 0, rays_secondary = 0, tri_hits = 0, continued = 0;
     Counters cnt;
     ElisionAudit *audit = nullptr;
+    uint32_t branches = 0; /* ORC_BRANCH_* bits: which arms of Radiance this path took */
 };
 
 /* bit test, so that the -Ofast (finite-math-only) baseline build cannot fold it away */
@@ -685,6 +684,7 @@ V4 radiance(const orc_scene &sc, V3 rStart, V3 rDir, Rng &rng, uint32_t sampling
         CastOut c = ray_cast(sc, rStart, rDir, (st && count_nodes && is_ray) ? &st->cnt : nullptr);
         if (!c.hit) {
             if (audit) pred.check(sc, *audit, c, rStart, rDir, accumColour, true, rDir);
+            if (st) st->branches |= depth == 0 ? ORC_BRANCH_MISS_DEPTH0 : ORC_BRANCH_MISS_AFTER_HIT;
             return accumColour; /* :36-41 */
         }
         if (st && c.tri_id >= 0) st->tri_hits++;
@@ -692,12 +692,15 @@ V4 radiance(const orc_scene &sc, V3 rStart, V3 rDir, Rng &rng, uint32_t sampling
         if (depth == 0) accumColour.w = c.distance;                                            /* :44-47 */
         if (length(c.colour) > 1.f) {
             if (audit) pred.check(sc, *audit, c, rStart, rDir, accumColour, true, rDir);
+            if (st) st->branches |= depth == 0 ? ORC_BRANCH_LIGHT_DEPTH0 : ORC_BRANCH_LIGHT_DEEPER;
             return accumColour; /* :52 */
         }
         if (++depth > 5 && (rng.u01() > 0.95f || depth > 1000)) {
             if (audit) pred.check(sc, *audit, c, rStart, rDir, accumColour, true, rDir);
+            if (st) st->branches |= ORC_BRANCH_ROULETTE_EXIT;
             return accumColour; /* :56-59 */
         }
+        if (st && depth > 5) st->branches |= ORC_BRANCH_ROULETTE_SURVIVED;
         V4 sampleColour = {0.f, 0.f, 0.f, 0.f}; /* :62 */
         if (c.material && sc.n_textures > 0)
             texture_sample(sc, c.uv, &sampleColour); /* :63-66 */
@@ -709,10 +712,12 @@ V4 radiance(const orc_scene &sc, V3 rStart, V3 rDir, Rng &rng, uint32_t sampling
             (void)rng.u01();
             (void)rng.u01();
             (void)rng.u01(); /* :101-103, unused noise */
+            if (st) st->branches |= ORC_BRANCH_SPECULAR;
             rStart = c.location - rDir * 0.001f;
             next_dir = normalize(rDir - n * 2.f * dot(n, rDir));
         } else if (c.material) { /* :151-165 */
             accumRadiance = accumRadiance * sampleColour;
+            if (st) st->branches |= ORC_BRANCH_DIFFUSE_TRIANGLE;
             float r1 = (float)(2 * M_PI * rng.u01());
             float r2 = (float)(r2scale * rng.u01());
             float r2s = std::sqrt(r2);
@@ -732,6 +737,7 @@ V4 radiance(const orc_scene &sc, V3 rStart, V3 rDir, Rng &rng, uint32_t sampling
             (void)rng.u01();
             (void)rng.u01();
             (void)rng.u01(); /* :173-175, unused noise */
+            if (st) st->branches |= ORC_BRANCH_DIFFUSE_SPHERE;
             V3 w = dot(n, rDir) < 0.f ? n : n * -1.f;
             V3 u = normalize(cross(std::fabs(w.x) > .1 ? v3(0, 1, 0) : v3(1, 0, 0), w));
             V3 v = cross(w, u);
@@ -1213,6 +1219,84 @@ void orc_radiance_mt(const orc_scene *sc, const float *o, const float *d, uint32
         V4 r = radiance(*sc, v3(o[i * 3], o[i * 3 + 1], o[i * 3 + 2]),
                         v3(d[i * 3], d[i * 3 + 1], d[i * 3 + 2]), rng, sampling, nullptr, false);
         out4[i * 4] = r.x, out4[i * 4 + 1] = r.y, out4[i * 4 + 2] = r.z, out4[i * 4 + 3] = r.w;
+    }
+}
+
+/* orc_radiance_mt that also reports, per path, which arms of Radiance it took (ORC_BRANCH_* bits) */
+void orc_radiance_mt_branches(const orc_scene *sc, const float *o, const float *d, uint32_t n, const uint64_t *seeds,
+                              uint32_t sampling, float *out4, uint32_t *branches) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)n; ++i) {
+        MtRng rng;
+        rng.eng.seed(seeds[i]);
+        PathStats st;
+        V4 r = radiance(*sc, v3(o[i * 3], o[i * 3 + 1], o[i * 3 + 2]),
+                        v3(d[i * 3], d[i * 3 + 1], d[i * 3 + 2]), rng, sampling, &st, false);
+        out4[i * 4] = r.x, out4[i * 4 + 1] = r.y, out4[i * 4 + 2] = r.z, out4[i * 4 + 3] = r.w;
+        branches[i] = st.branches;
+    }
+}
+
+/* Seeds in [first, first + count) for which std::mt19937_64(seed) + uniform_real_distribution<double>(0, 1), the pair
+ * Radiance draws from, gives a value below `below` at every one of the 1-based draw positions pos[npos] (ascending).
+ * Found seeds are written in ascending order, at most max_out of them; returns how many were written.  A path survives a
+ * diffuse bounce only if its r2 draw is below 0.1 (r2 = 10 U, pathtracer.cpp:156,170), so a path that reaches the roulette
+ * of depth > 5 is a 1-in-10^5 event: the tests pick their seeds with this instead of waiting for it. */
+uint32_t orc_mt_find_seeds(uint64_t first, uint64_t count, const uint32_t *pos, uint32_t npos, double below, uint64_t *out,
+                           uint32_t max_out) {
+    std::vector<uint64_t> found;
+#pragma omp parallel
+    {
+        std::vector<uint64_t> mine;
+#pragma omp for schedule(static) nowait
+        for (int64_t k = 0; k < (int64_t)count; ++k) {
+            /* prefilter: the first-generation outputs of MT19937-64 at those positions, computed from the seeded words
+             * they depend on (x[i], x[i+1], x[i+156]) without a whole twist; anything it lets through is decided by
+             * the standard library's engine and distribution below */
+            if (npos && pos[npos - 1] <= 150) {
+                uint64_t x[312];
+                x[0] = first + (uint64_t)k;
+                const uint32_t last = pos[npos - 1] + 156;
+                for (uint32_t i = 1; i <= last; ++i) x[i] = 6364136223846793005ull * (x[i - 1] ^ (x[i - 1] >> 62)) + i;
+                bool maybe = true;
+                for (uint32_t j = 0; j < npos && maybe; ++j) {
+                    const uint32_t i = pos[j] - 1;
+                    const uint64_t y = (x[i] & 0xFFFFFFFF80000000ull) | (x[i + 1] & 0x7FFFFFFFull);
+                    uint64_t v = x[i + 156] ^ (y >> 1) ^ ((y & 1) ? 0xB5026F5AA96619E9ull : 0ull);
+                    v ^= (v >> 29) & 0x5555555555555555ull;
+                    v ^= (v << 17) & 0x71D67FFFEDA60000ull;
+                    v ^= (v << 37) & 0xFFF7EEE000000000ull;
+                    v ^= v >> 43;
+                    maybe = (double)v * 5.421010862427522e-20 < below * 1.000001 + 1e-12;
+                }
+                if (!maybe) continue;
+            }
+            MtRng rng;
+            rng.eng.seed(first + (uint64_t)k);
+            uint32_t drawn = 0;
+            bool ok = true;
+            for (uint32_t j = 0; j < npos && ok; ++j) {
+                double u = 0;
+                while (drawn < pos[j]) u = rng.u01(), ++drawn;
+                ok = u < below;
+            }
+            if (ok) mine.push_back(first + (uint64_t)k);
+        }
+#pragma omp critical
+        found.insert(found.end(), mine.begin(), mine.end());
+    }
+    std::sort(found.begin(), found.end());
+    const uint32_t n = (uint32_t)std::min<size_t>(found.size(), max_out);
+    std::copy(found.begin(), found.begin() + n, out);
+    return n;
+}
+
+/* VermiTexture::Sample (meshEngine.cpp:21-46) on its own; out4 is preset to -1 so a sample the switch leaves alone shows */
+void orc_texture_sample(const float *data, uint32_t w, uint32_t h, uint32_t c, const float *uv, uint32_t n, float *out4) {
+    for (uint32_t i = 0; i < n; ++i) {
+        V4 s = {-1.f, -1.f, -1.f, -1.f};
+        texture_sample_of(data, w, h, c, V2{uv[i * 2], uv[i * 2 + 1]}, &s);
+        out4[i * 4] = s.x, out4[i * 4 + 1] = s.y, out4[i * 4 + 2] = s.z, out4[i * 4 + 3] = s.w;
     }
 }
 

@@ -63,6 +63,25 @@ void orc_audit_elision(const orc_scene *, const float *o, const float *d, uint32
 void orc_radiance_mt(const orc_scene *, const float *o, const float *d, uint32_t n,
                      const uint64_t *seeds, uint32_t sampling, float *out4);
 
+/* the arms of Radiance (pathtracer.cpp:21-198) a path went through, for orc_radiance_mt_branches */
+#define ORC_BRANCH_LIGHT_DEPTH0 0x001u      /* :52 at depth 0: the camera ray hit an emitter */
+#define ORC_BRANCH_LIGHT_DEEPER 0x002u      /* :52 after at least one bounce */
+#define ORC_BRANCH_MISS_DEPTH0 0x004u       /* :36-41 on the first ray */
+#define ORC_BRANCH_MISS_AFTER_HIT 0x008u    /* :36-41 on a bounce ray */
+#define ORC_BRANCH_ROULETTE_EXIT 0x010u     /* :56-59 returned */
+#define ORC_BRANCH_ROULETTE_SURVIVED 0x020u /* depth > 5 and the path went on */
+#define ORC_BRANCH_SPECULAR 0x040u          /* :98-109 */
+#define ORC_BRANCH_DIFFUSE_TRIANGLE 0x080u  /* :151-165 */
+#define ORC_BRANCH_DIFFUSE_SPHERE 0x100u    /* :166-196, the no-material arm with its three unused draws */
+void orc_radiance_mt_branches(const orc_scene *, const float *o, const float *d, uint32_t n, const uint64_t *seeds,
+                              uint32_t sampling, float *out4, uint32_t *branches);
+/* seeds in [first, first + count) whose mt19937_64 + uniform_real_distribution<double>(0,1) draws at the 1-based,
+ * ascending positions pos[npos] are all below `below`; ascending, at most max_out; returns the number written */
+uint32_t orc_mt_find_seeds(uint64_t first, uint64_t count, const uint32_t *pos, uint32_t npos, double below, uint64_t *out,
+                           uint32_t max_out);
+/* VermiTexture::Sample (meshEngine.cpp:21-46) of a w x h x c float texture at uv[n*2]; out4[n*4], untouched components -1 */
+void orc_texture_sample(const float *data, uint32_t w, uint32_t h, uint32_t c, const float *uv, uint32_t n, float *out4);
+
 /* camera matrix (3x3 upper-left of the reference's mat4, column-major m[col*3+row]) */
 void orc_camera_matrix(const vmx_camera *cam, float m9[9]);
 /* primary ray of sample k of every pixel in [0, W*H): o[n*3], d[n*3] */

@@ -15,6 +15,10 @@ _ODIR = os.path.join(_ROOT, "oracle")
 
 ORC_RNG_XOSHIRO_KEYED = 0
 ORC_RNG_MT19937_64 = 1
+# ORC_BRANCH_* of vmx_oracle.h: the arms of Radiance a path went through (radiance_mt_branches)
+BRANCHES = {"light_depth0": 0x001, "light_deeper": 0x002, "miss_depth0": 0x004, "miss_after_hit": 0x008,
+            "roulette_exit": 0x010, "roulette_survived": 0x020, "specular": 0x040, "diffuse_triangle": 0x080,
+            "diffuse_sphere": 0x100}
 
 
 class TraceCounters(C.Structure):
@@ -53,6 +57,10 @@ def lib(fast=False):
     l.orc_raycast.argtypes = [P, P, P, C.c_uint32, P]
     l.orc_radiance.argtypes = [P, P, P, C.c_uint32, C.POINTER(L.Opts), P, C.POINTER(L.Stats)]
     l.orc_radiance_mt.argtypes = [P, P, P, C.c_uint32, P, C.c_uint32, P]
+    l.orc_radiance_mt_branches.argtypes = [P, P, P, C.c_uint32, P, C.c_uint32, P, P]
+    l.orc_texture_sample.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_uint32, P]
+    l.orc_mt_find_seeds.restype = C.c_uint32
+    l.orc_mt_find_seeds.argtypes = [C.c_uint64, C.c_uint64, P, C.c_uint32, C.c_double, P, C.c_uint32]
     l.orc_audit_elision.argtypes = [P, P, P, C.c_uint32, C.POINTER(L.Opts), P, P]
     l.orc_camera_matrix.argtypes = [C.POINTER(L.CameraDesc), P]
     l.orc_primary_rays.argtypes = [C.POINTER(L.CameraDesc), C.POINTER(L.Opts), C.c_uint32, P, P]
@@ -174,6 +182,16 @@ class OracleScene:
                                out.ctypes.data)
         return out
 
+    def radiance_mt_branches(self, o, d, seeds, sampling=0):
+        """radiance_mt plus, per path, the ORC_BRANCH_* bits of the arms of Radiance it took"""
+        o, d = _f32(o), _f32(d)
+        seeds = np.ascontiguousarray(seeds, np.uint64)
+        out = np.empty((o.shape[0], 4), np.float32)
+        br = np.zeros(o.shape[0], np.uint32)
+        self.l.orc_radiance_mt_branches(self.h, o.ctypes.data, d.ctypes.data, o.shape[0], seeds.ctypes.data, sampling,
+                                        out.ctypes.data, br.ctypes.data)
+        return out, br
+
     def render_bruteforce(self, cam, opts, flags=0, threads=0):
         """BruteForceTracer::Render restated (integrators.cpp:9-186), whole image [H, W, 5]"""
         W, H = cam.image_res[0], cam.image_res[1]
@@ -194,6 +212,25 @@ class OracleScene:
         st = L.Stats()
         self.l.orc_render(self.h, C.byref(cam), C.byref(opts), rng_mode, threads, out.ctypes.data, C.byref(st))
         return out, st.as_dict()
+
+
+def texture_sample(data, uv, fast=False):
+    """VermiTexture::Sample restated, of the [H, W(, C)] float texture at uv[n, 2]; untouched components read -1"""
+    data = np.ascontiguousarray(data, np.float32)
+    h, w = data.shape[0], data.shape[1]
+    c = 1 if data.ndim == 2 else data.shape[2]
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.empty((uv.shape[0], 4), np.float32)
+    lib(fast).orc_texture_sample(data.ctypes.data, w, h, c, uv.ctypes.data, uv.shape[0], out.ctypes.data)
+    return out
+
+
+def mt_find_seeds(first, count, positions, below, max_out=1 << 20):
+    """seeds in [first, first + count) whose mt19937_64 draws at the 1-based `positions` are all below `below`"""
+    pos = np.ascontiguousarray(sorted(positions), np.uint32)
+    out = np.empty(max_out, np.uint64)
+    n = lib().orc_mt_find_seeds(int(first), int(count), pos.ctypes.data, len(pos), float(below), out.ctypes.data, max_out)
+    return out[:n].copy()
 
 
 def primary_rays(cam, opts, k=0):

@@ -8,6 +8,7 @@ import pytest
 
 import oracle_lib as O
 import vermilion_amd as va
+from shared_inputs import random_soup as _random_soup, wall_rays
 from vermilion_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -312,18 +313,7 @@ def test_sphere_table_rays_starting_on_the_walls():
     """bounce rays start 0.001 off the surface they left, often one of the 5e7-radius wall spheres:
     there (B*B - C) + R2 cancels at the magnitude of C, the case every shortcut around the
     double-precision solve (kernels: sphere_hit) has to get right"""
-    rng = np.random.default_rng(7)
-    n = 60000
-    oo, dd = [], []
-    for ax, val in ((0, -2000), (0, 2000), (2, -2000), (2, 2000), (1, 0), (1, 1000)):
-        o = np.empty((n, 3), np.float32)
-        o[:, 0], o[:, 1], o[:, 2] = rng.uniform(-2000, 2000, n), rng.uniform(0, 1000, n), rng.uniform(-2000, 2000, n)
-        o[:, ax] = val + rng.uniform(-0.7, 0.7, n)
-        d = rng.normal(size=(n, 3))
-        d[: n // 4, ax] *= 1e-5  # grazing
-        d /= np.linalg.norm(d, axis=1, keepdims=True)
-        oo.append(o), dd.append(d.astype(np.float32))
-    oo, dd = np.concatenate(oo), np.concatenate(dd)
+    oo, dd = wall_rays()
     for gen in (scenes.cornell8, scenes.lattice):
         p = Pair(*gen())
         assert_raycast_equal(p.gpu.raycast(oo, dd), p.cpu.raycast(oo, dd))
@@ -718,37 +708,6 @@ def test_device_builders_are_deterministic_f1():
                 trees.append(sc.bvh())
         for k in trees[0]:
             assert np.array_equal(trees[0][k], trees[1][k]), (bld, k)
-
-
-def _random_soup(rng, n, kind):
-    """triangle soups that stress the tree and the traversal: flat axis-aligned sheets (zero-thickness boxes),
-    duplicated triangles (exact distance ties), slivers and degenerate (zero-area) triangles, huge + tiny mixed"""
-    if kind == "sheets":  # triangles lying in a few axis-aligned planes, shared edges
-        ax = rng.integers(0, 3, n)
-        plane = rng.choice(np.float32([-300, 0, 250, 600]), n)
-        c = rng.uniform(-800, 800, (n, 1, 3)).astype(np.float32)
-        p = c + rng.uniform(-120, 120, (n, 3, 3)).astype(np.float32)
-        p[np.arange(n), :, ax] = plane[:, None]
-    elif kind == "duplicates":
-        m = max(n // 3, 1)
-        base = (rng.uniform(-600, 600, (m, 1, 3)) + rng.uniform(-90, 90, (m, 3, 3))).astype(np.float32)
-        p = base[rng.integers(0, m, n)]  # every triangle several times: ties are resolved by test order
-    elif kind == "slivers":
-        c = rng.uniform(-700, 700, (n, 1, 3)).astype(np.float32)
-        p = c + rng.uniform(-200, 200, (n, 3, 3)).astype(np.float32)
-        k = rng.random(n) < 0.3
-        p[k, 2] = p[k, 0] + (p[k, 1] - p[k, 0]) * rng.uniform(0, 1, (int(k.sum()), 1)).astype(np.float32)  # collinear
-        z = rng.random(n) < 0.05
-        p[z, 1] = p[z, 0]  # two equal vertices
-    else:  # "scales": a few huge triangles over many tiny ones
-        c = rng.uniform(-500, 500, (n, 1, 3)).astype(np.float32)
-        s = np.where(rng.random((n, 1, 1)) < 0.03, 2500.0, 12.0).astype(np.float32)
-        p = c + rng.uniform(-1, 1, (n, 3, 3)).astype(np.float32) * s
-    p = np.ascontiguousarray(p, np.float32)
-    nr = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]).astype(np.float32)
-    ln = np.linalg.norm(nr, axis=1, keepdims=True)
-    nr = np.where(ln > 0, nr / np.maximum(ln, 1e-30), np.float32([0, 1, 0])).astype(np.float32)
-    return p, np.repeat(nr[:, None, :], 3, axis=1).copy(), None
 
 
 @pytest.mark.parametrize("kind", ["sheets", "duplicates", "slivers", "scales"])

@@ -8,6 +8,7 @@ import torch
 
 import oracle_lib as O
 import vermilion_amd as va
+from shared_inputs import special_rays
 from vermilion_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -149,17 +150,6 @@ def test_nearest_on_other_trees(builder):
 
 
 # ---- special rays, deep trees ---------------------------------------------------------------------------------
-def special_rays():
-    g = np.load(os.path.join(GOLD, "lattice.npz"))
-    o, d = [g["ray_o"][:60]], [g["ray_d"][:60]]
-    xs = np.float32([-600, -250, 0, 150, 600, -250.00002, 149.99998])
-    for x in xs:
-        for y in np.float32([1, 400, 900, 200]):
-            for dvec in ((0, 0, -1), (0, 0, 1), (0, -1, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0)):
-                o.append(np.float32([[x, y, 300.0], [x, y, 0.0]])), d.append(np.float32([dvec, dvec]))
-    return np.concatenate(o).astype(np.float32), np.concatenate(d).astype(np.float32)
-
-
 def test_special_rays_nan_slabs_ties_and_degenerates():
     o, d = special_rays()
     for gen in (scenes.cornell8, scenes.lattice):

@@ -1,9 +1,9 @@
 """Generates tests/golden/*.npz from the CPU oracle (parity build, this container).
 
-The reference ships no golden vectors and cannot be built here (DESIGN.md
-"Oracle"), so these fixtures pin the *oracle's* outputs: they guard it against
-regressions / cross-machine drift and give the GPU tests a second, committed
-checker.  Inputs are stored next to the expected outputs; geometry uses only
+The reference ships no golden vectors, so these fixtures pin the *oracle's*
+outputs: they guard it against regressions / cross-machine drift and give the
+GPU tests a second, committed checker (fixtures recorded from the reference's
+own compiled code are tools/make_ref_golden.py's).  Inputs are stored next to the expected outputs; geometry uses only
 small integers (exact in float32), no transcendental functions.
 
     python tools/make_golden.py
