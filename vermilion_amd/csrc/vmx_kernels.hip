@@ -622,10 +622,18 @@ constexpr uint32_t kLdsSpheres = 16;
 static_assert(kLdsSpheres >= kMaxSpheres, "every sphere of a scene has an LDS slot");
 // LDS_GEOM / CAM_OP: compile-time, so that the table reads are plain LDS reads (a pointer chosen at run time
 // between LDS and global memory makes them flat loads); the API admits at most kLdsSpheres spheres
-template <bool LDS_GEOM = false, bool CAM_OP = false>
+// BOUNDS (camera rays of ONE pixel in the wave, k_shade<0>): `lmax` is a row in LDS, lmax[i] = pixel_sphere_bound of the
+// wave's pixel for sphere i, lmax[kLdsSpheres] their minimum (!use_lmax: no bounds, every sphere is evaluated).  A lane
+// whose nearest distance on entry — the triangle's, +inf after a BVH miss — is <= lmax[i] cannot be changed by
+// sphere i (nearest only shrinks in the loop, so the decision holds); the comparison is false for a NaN distance and for
+// lmax = 0 ("no claim") against any positive one.  Per lane the decision, per wave the branch: no lane needs any
+// sphere — the common case, a pixel whose rays end on triangles inside the room — and the loop is not entered;
+// otherwise the spheres no lane needs are passed over one by one, and the others run sphere_hit_op as before
+template <bool LDS_GEOM = false, bool CAM_OP = false, bool BOUNDS = false>
 __device__ __forceinline__ void cast_finish(const SceneDev &sc, float ox, float oy, float oz, float dx,
                                             float dy, float dz, float best, int slot, CastResult &r,
-                                            const float4 *geom = nullptr, const float4 *cam_op = nullptr) {
+                                            const float4 *geom = nullptr, const float4 *cam_op = nullptr,
+                                            const float *lmax = nullptr, bool use_lmax = false) {
     r.nearest = kInf;
     r.nx = r.ny = r.nz = 0.f;
     r.cr = r.cg = r.cb = 0.f;
@@ -640,7 +648,13 @@ __device__ __forceinline__ void cast_finish(const SceneDev &sc, float ox, float 
         r.material = true;  // hitMeshIndex = 0 (meshEngine.cpp:370), never reset
     }
     const uint32_t ns = sc.nspheres;
+    const float entry = r.nearest;
+    const bool bounded = BOUNDS && use_lmax;
+    if (bounded && __builtin_amdgcn_ballot_w64(!(entry <= lmax[kLdsSpheres])) == 0) return;
     for (uint32_t i = 0; i < ns; ++i) {
+        if (bounded) {
+            if (__builtin_amdgcn_ballot_w64(!(entry <= lmax[i])) == 0) continue;
+        }
         float4 g;
         if (LDS_GEOM) {
             g = geom[i];
@@ -1050,17 +1064,32 @@ __device__ __forceinline__ void primary_ray(const FrameDev &fr, uint32_t p, uint
 // sphere (both roots negative).  "Cannot reach" is claimed only with max(m, 0)^2 (1 + 1e-4) + 1e-3 < 1 - r^2 / |op|^2:
 // a margin five orders of magnitude above the float rounding of b = dot(op, d), |op|^2 and r^2 that the per-ray test
 // (sphere_in_reach) computes with — a sphere within ~1.8 degrees of the cone is simply tested per ray as before.
+struct PixelCone {
+    float ax, ay, az, alen;  // the centre direction a (not normalised) and its length
+    float sphi, cphi;        // sine and cosine of the half-angle
+};
+struct FilmDev {  // the frame's film: FrameDev's width, height, sensor_x, sensor_y, film_dist
+    uint32_t width, height;
+    float sensor_x, sensor_y, film_dist;
+};
+__device__ __forceinline__ PixelCone pixel_cone(const FrameDev &fr, const FilmDev &fm, uint32_t p) {
+    const float fw = (float)fm.width, fh = (float)fm.height;
+    const float hx = ((float)(p % fm.width) - 0.25f) / fw - 0.5f;
+    const float hy = ((float)(p / fm.width) - 0.25f) / fh - 0.5f;
+    const float gx = hx * fm.sensor_x, gy = -(hy * fm.sensor_y), gz = -fm.film_dist;
+    PixelCone cn;
+    cn.ax = fr.m[0] * gx + fr.m[3] * gy + fr.m[6] * gz;
+    cn.ay = fr.m[1] * gx + fr.m[4] * gy + fr.m[7] * gz;
+    cn.az = fr.m[2] * gx + fr.m[5] * gy + fr.m[8] * gz;
+    cn.alen = sqrtf(cn.ax * cn.ax + cn.ay * cn.ay + cn.az * cn.az);
+    const float px = fm.sensor_x / fw, py = fm.sensor_y / fh;
+    cn.sphi = fminf(0.505f * sqrtf(px * px + py * py) / cn.alen, 1.0f);  // half the diagonal, +1 %
+    cn.cphi = sqrtf(fmaxf(1.0f - cn.sphi * cn.sphi, 0.0f));
+    return cn;
+}
 __device__ __forceinline__ bool pixel_may_reach_a_light(const SceneDev &sc, const FrameDev &fr, uint32_t p) {
-    const float hx = ((float)(p % fr.width) - 0.25f) / (float)fr.width - 0.5f;
-    const float hy = ((float)(p / fr.width) - 0.25f) / (float)fr.height - 0.5f;
-    const float gx = hx * fr.sensor_x, gy = -(hy * fr.sensor_y), gz = -fr.film_dist;
-    const float ax = fr.m[0] * gx + fr.m[3] * gy + fr.m[6] * gz;
-    const float ay = fr.m[1] * gx + fr.m[4] * gy + fr.m[7] * gz;
-    const float az = fr.m[2] * gx + fr.m[5] * gy + fr.m[8] * gz;
-    const float alen = sqrtf(ax * ax + ay * ay + az * az);
-    const float px = fr.sensor_x / (float)fr.width, py = fr.sensor_y / (float)fr.height;
-    const float sphi = fminf(0.505f * sqrtf(px * px + py * py) / alen, 1.0f);  // half the diagonal, +1 %
-    const float cphi = sqrtf(fmaxf(1.0f - sphi * sphi, 0.0f));
+    const PixelCone cn = pixel_cone(fr, FilmDev{fr.width, fr.height, fr.sensor_x, fr.sensor_y, fr.film_dist}, p);
+    const float ax = cn.ax, ay = cn.ay, az = cn.az, alen = cn.alen, sphi = cn.sphi, cphi = cn.cphi;
     bool may = !(alen > 0.0f);  // (a degenerate film: no claim)
     for (uint32_t i = 0; i < sc.emit_prefix; ++i) {
         const SphereDev &q = sc.spheres[i];
@@ -1074,6 +1103,66 @@ __device__ __forceinline__ bool pixel_may_reach_a_light(const SceneDev &sc, cons
         if (!(m * m * 1.0001f + 1e-3f < clear)) may = true;                      // (NaN / inf / origin inside: may)
     }
     return may;
+}
+
+// lmax(p, s): a distance such that for EVERY camera ray d of pixel p and every limit <= lmax, sphereIntersect(o, d, s)
+// (meshEngine.cpp:182-194, on the float B = dot(op, d), C = dot(op, op), R2 = rad * rad) is either 0 or >= limit — so
+// cast_finish's `th > 0 && th < nearest` is false for a ray whose nearest distance so far is <= lmax, whatever the
+// exact value, and the sphere is passed over for it without the per-ray tests of sphere_hit_op.  Four answers:
+//   +inf  never matters: the camera is outside the sphere by a margin and no ray of the cone reaches it, or it lies
+//         behind the cone — the test of pixel_may_reach_a_light (valid for a ray that hit no triangle, too)
+//   > 0   exit beyond: the camera is inside the sphere by a margin, D = R2 - C > 2^-18 (C + R2); D is exact in
+//         double for the floats C, R2 the per-ray code uses, while the reference's (b b - C) + R2 rounds by at most
+//         2^-52 max(b b, C), 2^-34 of D.  Its result is the larger root T(b) = b + sqrt(b b + D), which grows with b, so
+//         T(b_lo) bounds it for b_lo <= every float B of the cone:
+//           b_lo = |op| cos(theta + phi) - 2^-10 |op|      (cos = -1 once theta + phi >= pi)
+//         The margin stands against: the rounding of dot3 (3 x 2^-24 |op|), of the direction's three components and
+//         its length (5 x 2^-24 |op|), the direction's angle against the ideal film point (float film coordinates and
+//         matrix product, < 1e-6 rad, i.e. < 1e-6 |op| in b), and this function's own cosine (ct, st from a cross
+//         product, cphi with sphi <= 0.5: < 1e-6 absolute) — 2.5e-6 |op| in all, the margin is 400 times that.  For a
+//         wall sphere of the reference's room (|op| ~ 5e7, one ulp of B = 4, dT/db = T / sqrt(b b + D) ~ 1e-5) it
+//         moves T by 1e-3 of itself.  T is evaluated without cancellation (D / (s - b) for b < 0), 5 float
+//         operations of 2^-24 each, and is then shrunk by 2^-13: 250 times that and the 2^-24 of the reference's
+//         own (float) t.
+//   > 0   entry beyond: the camera is outside the sphere by the same margin, X = C - R2 > 2^-18 (C + R2), and the cone
+//         may reach it (in the reference's room: its floor and ceiling spheres, for nearly every pixel).  A ray that
+//         misses returns 0; one that hits returns the smaller root t(b) = b - sqrt(b b - X) = X / (b + sqrt(b b - X)),
+//         which falls as b grows, so t(b_hi) bounds it from below for
+//           b_hi = max(|op| max(cos(theta - phi), 0) + 2^-10 |op|, sqrt(X))    (the margin: as for b_lo)
+//         with the square root taken of b_hi b_hi (1 + 2^-20) - X (1 - 2^-20), 16 times the three roundings of that
+//         difference, so that it is not below the true one where the two terms cancel (a grazing cone); the
+//         reference's own rounding of (b b - C) + R2 moves its root by at most sqrt(2^-52 C), 2^-17 of sqrt(X), the
+//         least the bound can be compared with; then the same shrink by 2^-13
+//   0     no claim: the camera near the surface, a degenerate film, a half-angle
+//         above 30 degrees, any NaN or infinity (every comparison below is false on a NaN).  The ray is tested as before.
+// Checked against the reference's arithmetic in tests/test_pixel_sphere_bounds.py.
+__device__ __forceinline__ float pixel_sphere_bound(const PixelCone &cn, float opx, float opy, float opz, float C, float R2) {
+    constexpr float kMarginB = 9.765625e-04f;        // 2^-10
+    constexpr float kInsideRel = 3.814697265625e-06f;  // 2^-18
+    constexpr float kShrink = 1.0f - 1.220703125e-04f;  // 1 - 2^-13
+    constexpr float kRootRel = 9.5367431640625e-07f;    // 2^-20
+    const float len = sqrtf(C), norm = len * cn.alen;
+    const float ct = (opx * cn.ax + opy * cn.ay + opz * cn.az) / norm;
+    float kx, ky, kz;
+    cross3(opx, opy, opz, cn.ax, cn.ay, cn.az, kx, ky, kz);
+    const float st = sqrtf(kx * kx + ky * ky + kz * kz) / norm;
+    const bool cone_ok = cn.alen > 0.0f && cn.sphi <= 0.5f;
+    const float m = ct >= cn.cphi ? 1.0f : fmaxf(ct * cn.cphi + st * cn.sphi, 0.0f);  // cos(theta - phi); 1 inside the cone
+    const float clear = 1.0f - R2 / C;                                                // 1 - r^2 / |op|^2
+    const bool never = cone_ok && m * m * 1.0001f + 1e-3f < clear;
+    const float cmin = ct <= -cn.cphi ? -1.0f : fmaxf(ct * cn.cphi - st * cn.sphi, -1.0f);  // cos(theta + phi)
+    const float blo = len * cmin - kMarginB * len;
+    const float D = R2 - C;
+    const bool inside = cone_ok && D > kInsideRel * (C + R2);
+    const float s = sqrtf(blo * blo + D);
+    const float T = (blo < 0.0f ? D / (s - blo) : blo + s) * kShrink;
+    const float X = C - R2;
+    const bool outside = cone_ok && X > kInsideRel * (C + R2);
+    const float bhi = fmaxf(len * m + kMarginB * len, sqrtf(X));
+    const float s_up = sqrtf(fmaxf(bhi * bhi * (1.0f + kRootRel) - X * (1.0f - kRootRel), 0.0f));
+    const float E = X / (bhi + s_up) * kShrink;
+    const float lm = inside ? T : E;
+    return never ? kInf : ((inside || outside) && lm > 0.0f && lm < kInf ? lm : 0.0f);
 }
 
 // n / d for a launch constant d (vmx_device.h: FastDiv)
@@ -2600,7 +2689,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
 #endif
 // FROMQ: 0 every path of the generation; 1 the ordered list of positions k_shade_ends + launch_live_compact left
 // (wk.flat_ids); 2 the records k_trace_w<.., SORT> appended (wk.out_rec: ray, hit and position in one place)
-template <int SRC, bool TEX, bool ELIDE = false, int FROMQ = 0>
+template <int SRC, bool TEX, bool ELIDE = false, int FROMQ = 0, bool DENSE = false>
 __global__ void __launch_bounds__(256, VMX_SHADE_WPS)
 k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, IdQueue qout, uint32_t max_chunks,
         DevCounters *ctr) {
@@ -2608,6 +2697,10 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
     float4 *__restrict__ rad = (float4 *)pa.rad;
     __shared__ float4 s_geom[kLdsSpheres];
     __shared__ float4 s_cam_op[kLdsSpheres];  // SRC 0: (centre - camera position, squared length), same for every path
+    // the dense camera form, one row per wave: the wave's pixel's sphere bounds and their minimum (pixel_sphere_bound);
+    // its first sample index, the step between its samples and the pixel half of its stream key
+    __shared__ float s_lmax[4][kLdsSpheres + 1];
+    __shared__ uint32_t s_pix[4][6];
     if (threadIdx.x < min(sc.nspheres, kLdsSpheres)) {
         const SphereDev &q = sc.spheres[threadIdx.x];
         s_geom[threadIdx.x] = make_float4(q.cx, q.cy, q.cz, q.rad2);
@@ -2630,139 +2723,197 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
         live_n = *wk.live_count;
         if (FROMQ == 0) items = (live_n + blockDim.x - 1) / blockDim.x;
     }
-    for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
-        bool run;
-        uint32_t pid = 0, src = 0;
-        float2 hrec = make_float2(0.f, 0.f);  // FROMQ 2: the hit record came with the list entry
-        Path P;
-        if (SRC == 0) {
-            src = pid = item * blockDim.x + threadIdx.x;
-            float4 rec0 = make_float4(0.f, 0.f, 0.f, 0.f), rec1 = rec0;
-            if (FROMQ == 1) {
-                src = pid = src < flat_n ? wk.flat_ids[src] : 0xFFFFFFFFu;
-                if (listed) live_n = 0xFFFFFFFFu;  // (a listed position is a valid one)
+    // The dense camera form (every path of the pass, pixel-major ids, a multiple of 64 samples): a wave's 64 paths are 64
+    // samples of ONE pixel, and a wave takes a whole PIXEL per iteration, as k_raygen does — active[slot], the pixel's
+    // cursor, the pixel half of the stream key and the pixel's sphere bounds (pixel_sphere_bound, lane i = sphere i)
+    // once, then the pixel's chunks of 64 samples.  (rayA / hit of a chunk depend on the indices alone, but loading them
+    // ahead of that chain holds five registers across the set-up: measured, the kernel then spills its generator state
+    // inside the loop and loses the whole gain — profiles/pixel_sphere_bounds.txt — so they are loaded where they are used.)
+    // Path ids, the rad_mask word per 64 ids, the sub-queue of an id ((pid >> 8) % kSubQueues) and the tallies are
+    // those of the block-item loop, which every other form keeps (one unit = one block item of 256 positions).
+    static_assert(!DENSE || (SRC == 0 && FROMQ == 0 && !ELIDE), "the dense form is the plain camera pass");
+    constexpr bool dense = DENSE;  // (launch_shade: wk.pixel_major && wk.samples % 64 == 0)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t chunks = dense ? wk.samples >> 6 : 1u;
+    uint32_t unit = blockIdx.x, unit_step = gridDim.x, units = items;
+    if (dense) {
+        unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+        unit_step = gridDim.x * (blockDim.x >> 6), units = wk.n_pad;
+    }
+    for (; unit < units; unit += unit_step) {
+        const bool px_active = dense && unit < wk.n_active;
+        if (px_active) {
+            const uint32_t lp = wk.active[unit];
+            const uint32_t pixel = global_pixel(fr, lp);
+            const PixelKey pk = rng_pixel_key(fr.seed, pixel);
+            const uint32_t cur = px.cursor[lp];  // (sample_index, with the cursor fetched once)
+            // (the terms that depend on the frame or on the lane's sphere alone are formed here, per pixel, on purpose: kept
+            // in registers across the loop they would push the shading's own state out to scratch)
+            FilmDev fm = {fr.width, fr.height, fr.sensor_x, fr.sensor_y, fr.film_dist};
+            uint32_t si = lane;
+            asm volatile("" : "+s"(fm.width), "+s"(fm.height), "+s"(fm.sensor_x), "+s"(fm.sensor_y), "+s"(fm.film_dist), "+v"(si));
+            si &= kLdsSpheres - 1u;
+            const PixelCone cn = pixel_cone(fr, fm, pixel);
+            const float4 q = s_cam_op[si];
+            const float lm = si < sc.nspheres ? pixel_sphere_bound(cn, q.x, q.y, q.z, q.w, s_geom[si].w) : kInf;
+            float lmin = kInf;
+            for (uint32_t i = 0; i < sc.nspheres; ++i)
+                lmin = fminf(lmin, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lm), (int)i)));
+            // parked in the wave's LDS row, not in registers: the kernel sits at its register budget (VMX_SHADE_WPS)
+            if (lane < kLdsSpheres) s_lmax[wave][lane] = lm;
+            if (lane == 0) {
+                s_lmax[wave][kLdsSpheres] = lmin;
+                s_pix[wave][0] = cur & ~kCursorStrided, s_pix[wave][1] = (cur & kCursorStrided) ? fr.quarter : 1u;
+                s_pix[wave][2] = (uint32_t)pk.a, s_pix[wave][3] = (uint32_t)(pk.a >> 32);
+                s_pix[wave][4] = (uint32_t)pk.b, s_pix[wave][5] = (uint32_t)(pk.b >> 32);
             }
-            if (FROMQ == 2) {  // (direction, flag word)(t, leaf slot, position, -); position ~0: padding of a chunk
-                const bool in = src < flat_n;
-                if (in) rec0 = ((const float4 *)wk.out_rec)[(size_t)src * 2], rec1 = ((const float4 *)wk.out_rec)[(size_t)src * 2 + 1];
-                src = pid = in ? __float_as_uint(rec1.z) : 0xFFFFFFFFu;
-                hrec = make_float2(rec1.x, rec1.y);
-                if (listed) live_n = 0xFFFFFFFFu;
-            }
-            if (listed) pid = src < live_n ? wk.live_ids[src] : 0xFFFFFFFFu;  // (no such path: j >= samples below)
-            uint32_t j, s_idx;
-            if (wk.pixel_major) s_idx = fast_div(pid, wk.div_samples), j = pid - s_idx * wk.samples;
-            else j = pid / wk.n_pad, s_idx = pid - j * wk.n_pad;
-            uint32_t pixel = 0, k = 0, pid2;
-            run = j < wk.samples && s_idx < wk.n_pad && primary_item(fr, wk, px, j, s_idx, pid2, pixel, k);
-            if (run) {
-                // the ray comes from k_raygen; the stream is re-keyed and its two jitter draws skipped
-                const float4 a = FROMQ == 2 ? rec0 : ((const float4 *)pa.rayA)[src];
-                P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz, P.dx = a.x, P.dy = a.y, P.dz = a.z, P.depth = 0;
-                if (FROMQ == 0 && !listed && wk.pixel_major && (wk.samples & 63u) == 0) {
-                    // the wave's 64 paths are 64 samples of ONE pixel (path ids of an item are consecutive): the pixel
-                    // half of the key once per wave, on the scalar unit
-                    const uint32_t pu = (uint32_t)__builtin_amdgcn_readfirstlane((int)pixel);
-                    rng_init_keyed(P.rng, rng_pixel_key(fr.seed, pu), k);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (uint32_t ch = 0; ch < chunks; ++ch) {
+            const uint32_t pos0 = dense ? unit * wk.samples + ch * 64u + lane : unit * blockDim.x + threadIdx.x;
+            const uint32_t item = dense ? pos0 >> 8 : unit;  // the block item of these positions (blocks are 256 wide)
+            bool run;
+            uint32_t pid = 0, src = 0;
+            float2 hrec = make_float2(0.f, 0.f);  // FROMQ 2: the hit record came with the list entry
+            Path P;
+            if (SRC == 0) {
+                src = pid = pos0;
+                float4 rec0 = make_float4(0.f, 0.f, 0.f, 0.f), rec1 = rec0;
+                if (FROMQ == 1) {
+                    src = pid = src < flat_n ? wk.flat_ids[src] : 0xFFFFFFFFu;
+                    if (listed) live_n = 0xFFFFFFFFu;  // (a listed position is a valid one)
+                }
+                if (FROMQ == 2) {  // (direction, flag word)(t, leaf slot, position, -); position ~0: padding of a chunk
+                    const bool in = src < flat_n;
+                    if (in) rec0 = ((const float4 *)wk.out_rec)[(size_t)src * 2], rec1 = ((const float4 *)wk.out_rec)[(size_t)src * 2 + 1];
+                    src = pid = in ? __float_as_uint(rec1.z) : 0xFFFFFFFFu;
+                    hrec = make_float2(rec1.x, rec1.y);
+                    if (listed) live_n = 0xFFFFFFFFu;
+                }
+                if (listed) pid = src < live_n ? wk.live_ids[src] : 0xFFFFFFFFu;  // (no such path: j >= samples below)
+                uint32_t pixel = 0, k = 0, pid2;
+                if (dense) {  // (sample_index of the pixel's sample j, from the cursor fetched above)
+                    const uint32_t j = ch * 64u + lane;
+                    if (px_active) k = (fr.lead != 0 && j >= fr.lead) ? (j - fr.lead + 1u) * fr.quarter : s_pix[wave][0] + j * s_pix[wave][1];
+                    run = px_active && k < fr.kmax;
                 } else {
-                    rng_init(P.rng, fr.seed, pixel, k);
+                    uint32_t j, s_idx;
+                    if (wk.pixel_major) s_idx = fast_div(pid, wk.div_samples), j = pid - s_idx * wk.samples;
+                    else j = pid / wk.n_pad, s_idx = pid - j * wk.n_pad;
+                    run = j < wk.samples && s_idx < wk.n_pad && primary_item(fr, wk, px, j, s_idx, pid2, pixel, k);
                 }
-                (void)rng_next(P.rng);
-                (void)rng_next(P.rng);
-                P.ar = P.ag = P.ab = 0.f;
-                P.aw = -100.f;  // pathtracer.cpp:29
-                P.tr = P.tg = P.tb = P.tw = 1.f;  // :30
-            }
-        } else {
-            uint32_t sub = item % kSubQueues, chunk = item / kSubQueues;
-            uint32_t pos = chunk * blockDim.x + threadIdx.x;
-            if (FROMQ == 1) {  // a listed position = (block item of k_shade_ends) * 256 + lane
-                const uint32_t at = item * blockDim.x + threadIdx.x;
-                run = at < flat_n;
-                const uint32_t p = run ? wk.flat_ids[at] : 0u;
-                sub = (p >> 8) % kSubQueues, chunk = (p >> 8) / kSubQueues, pos = chunk * 256u + (p & 255u);
-            } else if (FROMQ == 2) {  // (t, leaf slot, path id, -); path id ~0: padding of a chunk
-                const uint32_t at = item * blockDim.x + threadIdx.x;
-                float4 r = make_float4(0.f, 0.f, __uint_as_float(0xFFFFFFFFu), 0.f);
-                if (at < flat_n) r = ((const float4 *)wk.out_rec)[at];
-                pid = __float_as_uint(r.z);
-                hrec = make_float2(r.x, r.y);
-                run = pid != 0xFFFFFFFFu;
+                if (run) {
+                    // the ray comes from k_raygen; the stream is re-keyed and its two jitter draws skipped
+                    const float4 a = FROMQ == 2 ? rec0 : ((const float4 *)pa.rayA)[src];
+                    P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz, P.dx = a.x, P.dy = a.y, P.dz = a.z, P.depth = 0;
+                    if (dense) {  // the pixel half of the key: once per pixel
+                        PixelKey pk;
+                        pk.a = (uint64_t)s_pix[wave][2] | ((uint64_t)s_pix[wave][3] << 32);
+                        pk.b = (uint64_t)s_pix[wave][4] | ((uint64_t)s_pix[wave][5] << 32);
+                        rng_init_keyed(P.rng, pk, k);
+                    } else {
+                        rng_init(P.rng, fr.seed, pixel, k);
+                    }
+                    (void)rng_next(P.rng);
+                    (void)rng_next(P.rng);
+                    P.ar = P.ag = P.ab = 0.f;
+                    P.aw = -100.f;  // pathtracer.cpp:29
+                    P.tr = P.tg = P.tb = P.tw = 1.f;  // :30
+                }
             } else {
-                run = pos < min(wk.qids.counts[sub * 32], wk.qids.sub_capacity);
+                uint32_t sub = item % kSubQueues, chunk = item / kSubQueues;
+                uint32_t pos = chunk * blockDim.x + threadIdx.x;
+                if (FROMQ == 1) {  // a listed position = (block item of k_shade_ends) * 256 + lane
+                    const uint32_t at = item * blockDim.x + threadIdx.x;
+                    run = at < flat_n;
+                    const uint32_t p = run ? wk.flat_ids[at] : 0u;
+                    sub = (p >> 8) % kSubQueues, chunk = (p >> 8) / kSubQueues, pos = chunk * 256u + (p & 255u);
+                } else if (FROMQ == 2) {  // (t, leaf slot, path id, -); path id ~0: padding of a chunk
+                    const uint32_t at = item * blockDim.x + threadIdx.x;
+                    float4 r = make_float4(0.f, 0.f, __uint_as_float(0xFFFFFFFFu), 0.f);
+                    if (at < flat_n) r = ((const float4 *)wk.out_rec)[at];
+                    pid = __float_as_uint(r.z);
+                    hrec = make_float2(r.x, r.y);
+                    run = pid != 0xFFFFFFFFu;
+                } else {
+                    run = pos < min(wk.qids.counts[sub * 32], wk.qids.sub_capacity);
+                }
+                if (run) {
+                    if (FROMQ != 2) pid = wk.qids.ids[(size_t)sub * wk.qids.sub_capacity + pos];
+                    path_load_arrays<TEX, false>(pa, pid, P);  // (accumColour: below, only where the step changes it)
+                }
             }
+            StepFlags fl = {false, false, false};
+            uint32_t depth0 = 0;
+            int st = kPathEnded;
+            ShadeMid mid;
+            CastResult c;
             if (run) {
-                if (FROMQ != 2) pid = wk.qids.ids[(size_t)sub * wk.qids.sub_capacity + pos];
-                path_load_arrays<TEX, false>(pa, pid, P);  // (accumColour: below, only where the step changes it)
-            }
-        }
-        StepFlags fl = {false, false, false};
-        uint32_t depth0 = 0;
-        int st = kPathEnded;
-        ShadeMid mid;
-        CastResult c;
-        if (run) {
-            P.dest = pid;
-            depth0 = P.depth == 0 ? 1u : 0u;
-            fl.was_ray = depth0 ? true : finite3(P.dx, P.dy, P.dz);
-            const float2 h = FROMQ == 2 ? hrec : hits[SRC == 0 ? src : pid];
-            cast_finish<true, SRC == 0>(sc, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, h.x, __float_as_int(h.y), c, s_geom,
-                                        s_cam_op);
-            // A bounce step changes accumColour only by += accumRadiance * hitColour (pathtracer.cpp:43) — nothing when no
-            // light coloured the hit (x + t * 0 == x for finite t; the sums are never -0) — and, at depth 0 (explicit rays
-            // of vmx_radiance), by its fourth component (:44-47).  Six steps in seven change nothing: their path's
-            // 16 bytes of a 64-byte line are neither fetched nor written back (a third of this kernel's HBM traffic).
-            bool touch = SRC == 0, had = true;
-            if (SRC != 0) {
-                touch = P.depth == 0 || c.cr != 0.f || c.cg != 0.f || c.cb != 0.f;
-                if (TEX) touch = touch || !(finite3(P.tr, P.tg, P.tb) && fabsf(P.tw) < kInf);
-                if (touch) {
-                    had = rad_has(pa, pid);
-                    const float4 acc = rad_fetch(pa, pid, had);
-                    P.ar = acc.x, P.ag = acc.y, P.ab = acc.z, P.aw = acc.w;
+                P.dest = pid;
+                depth0 = P.depth == 0 ? 1u : 0u;
+                fl.was_ray = depth0 ? true : finite3(P.dx, P.dy, P.dz);
+                const float2 h = FROMQ == 2 ? hrec : hits[SRC == 0 ? src : pid];
+                // (the pixel's sphere bounds: the dense camera form only — elsewhere lmax_min < 0, every sphere is evaluated)
+                cast_finish<true, SRC == 0, DENSE>(sc, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, h.x, __float_as_int(h.y), c,
+                                                                             s_geom, s_cam_op, s_lmax[wave], dense);
+                // A bounce step changes accumColour only by += accumRadiance * hitColour (pathtracer.cpp:43) — nothing when no
+                // light coloured the hit (x + t * 0 == x for finite t; the sums are never -0) — and, at depth 0 (explicit rays
+                // of vmx_radiance), by its fourth component (:44-47).  Six steps in seven change nothing: their path's
+                // 16 bytes of a 64-byte line are neither fetched nor written back (a third of this kernel's HBM traffic).
+                bool touch = SRC == 0, had = true;
+                if (SRC != 0) {
+                    touch = P.depth == 0 || c.cr != 0.f || c.cg != 0.f || c.cb != 0.f;
+                    if (TEX) touch = touch || !(finite3(P.tr, P.tg, P.tb) && fabsf(P.tw) < kInf);
+                    if (touch) {
+                        had = rad_has(pa, pid);
+                        const float4 acc = rad_fetch(pa, pid, had);
+                        P.ar = acc.x, P.ag = acc.y, P.ab = acc.z, P.aw = acc.w;
+                    }
+                }
+                st = path_shade_begin<TEX>(sc, fr.r2scale, P, c, fl, mid);
+                if (SRC != 0) {
+                    if (touch) rad_commit(pa, pid, make_float4(P.ar, P.ag, P.ab, P.aw), had);
+                } else if (!pa.rad_mask) {
+                    rad[pid] = make_float4(P.ar, P.ag, P.ab, P.aw);
                 }
             }
-            st = path_shade_begin<TEX>(sc, fr.r2scale, P, c, fl, mid);
-            if (SRC != 0) {
-                if (touch) rad_commit(pa, pid, make_float4(P.ar, P.ag, P.ab, P.aw), had);
-            } else if (!pa.rad_mask) {
-                rad[pid] = make_float4(P.ar, P.ag, P.ab, P.aw);
+            bool alive = st == kPathNextRay;
+            // (gathering the block's ~10 % of angles in LDS to evaluate cos/sin in full waves was measured:
+            // the three barriers it needs cost what it saves)
+            if (st == kPathNeedsTrig) {
+                float sn, cs;
+                shade_trig(mid, fr.libm_double, cs, sn);
+                alive = path_shade_end(P, c, fl, mid, cs, sn);
             }
-        }
-        bool alive = st == kPathNextRay;
-        // (gathering the block's ~10 % of angles in LDS to evaluate cos/sin in full waves was measured:
-        // the three barriers it needs cost what it saves)
-        if (st == kPathNeedsTrig) {
-            float sn, cs;
-            shade_trig(mid, fr.libm_double, cs, sn);
-            alive = path_shade_end(P, c, fl, mid, cs, sn);
-        }
-        if (ELIDE && alive &&
-            step_is_dead<TEX>(sc, fr.r2scale, P.rng, P.depth, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, P.tr, P.tg, P.tb))
-            alive = false, fl.continues = false;  // VMX_SAMPLING_ELIDE_DEAD: the next ray cannot change the path's colour
-        if (alive) {
-            uint32_t bits = 0;
-            if (fr.bounce_bits) bits = step_bits<TEX>(sc, fr.r2scale, P.rng, P.depth, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, P.tr, P.tg, P.tb);
-            ray_store(pa, pid, P, bits);
-            rng_store(pa, pid, P.rng);
-            if (TEX) ((float4 *)pa.thr)[pid] = make_float4(P.tr, P.tg, P.tb, P.tw);
-        }
-        if (SRC == 0 && pa.rad_mask) {
-            // camera paths: most end at their first hit with accumColour.rgb == 0 (no light sphere hit): nothing to store
-            // for them, k_resolve adds +0 (x + 0 == x bit for bit; the sums are never -0).  A wave's 64 paths are one
-            // aligned word of the mask (path ids of an item are consecutive, 256 per block)
-            // (a path that goes on black stores nothing either: the step that colours it later sets its bit, rad_commit)
-            const bool need = run && (P.ar != 0.f || P.ag != 0.f || P.ab != 0.f);
-            if (need) rad[pid] = make_float4(P.ar, P.ag, P.ab, P.aw);
-            if (listed || FROMQ != 0) {  // the mask was cleared for the pass / written by k_shade_ends; neighbours share words
-                if (need) atomicOr(&pa.rad_mask[pid >> 6], 1ull << (pid & 63u));
-            } else {
-                const unsigned long long word = __builtin_amdgcn_ballot_w64(need);
-                if ((threadIdx.x & 63u) == 0) pa.rad_mask[(item * blockDim.x + threadIdx.x) >> 6] = word;
+            if (ELIDE && alive &&
+                step_is_dead<TEX>(sc, fr.r2scale, P.rng, P.depth, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, P.tr, P.tg, P.tb))
+                alive = false, fl.continues = false;  // VMX_SAMPLING_ELIDE_DEAD: the next ray cannot change the path's colour
+            if (alive) {
+                uint32_t bits = 0;
+                if (fr.bounce_bits) bits = step_bits<TEX>(sc, fr.r2scale, P.rng, P.depth, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, P.tr, P.tg, P.tb);
+                ray_store(pa, pid, P, bits);
+                rng_store(pa, pid, P.rng);
+                if (TEX) ((float4 *)pa.thr)[pid] = make_float4(P.tr, P.tg, P.tb, P.tw);
             }
+            if (SRC == 0 && pa.rad_mask) {
+                // camera paths: most end at their first hit with accumColour.rgb == 0 (no light sphere hit): nothing to store
+                // for them, k_resolve adds +0 (x + 0 == x bit for bit; the sums are never -0).  A wave's 64 paths are one
+                // aligned word of the mask (path ids of an item are consecutive, 256 per block)
+                // (a path that goes on black stores nothing either: the step that colours it later sets its bit, rad_commit)
+                const bool need = run && (P.ar != 0.f || P.ag != 0.f || P.ab != 0.f);
+                if (need) rad[pid] = make_float4(P.ar, P.ag, P.ab, P.aw);
+                if (listed || FROMQ != 0) {  // the mask was cleared for the pass / written by k_shade_ends; neighbours share words
+                    if (need) atomicOr(&pa.rad_mask[pid >> 6], 1ull << (pid & 63u));
+                } else {
+                    const unsigned long long word = __builtin_amdgcn_ballot_w64(need);
+                    if (lane == 0) pa.rad_mask[pos0 >> 6] = word;
+                }
+            }
+            tally_add(tl, fl, run, depth0);
+            id_append(qout, item % kSubQueues, alive, pid);
         }
-        tally_add(tl, fl, run, depth0);
-        id_append(qout, item % kSubQueues, alive, pid);
     }
     const Cnt none = {0, 0};
     tally_flush<false>(ctr, tl, none, none);
@@ -3497,15 +3648,19 @@ int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
     // 7 blocks per CU are resident (VMX_SHADE_WPS); more blocks only add end-of-block counter atomics, which a small pass
     // feels (early-stop frame, first pass: 1.70 ms with 4096 blocks, 1.05 with 1792; the bench frame's 530.8 M paths: no change)
     constexpr uint32_t kShadeGrid = 256u * VMX_SHADE_WPS;
-    const uint64_t items = flat ? kShadeGrid : (from_queue ? (uint64_t)max_chunks * kSubQueues : ((uint64_t)wk.samples * wk.n_pad + 255) / 256);
+    // (k_shade<0>'s dense form: a wave per pixel, four pixels per block and iteration)
+    const bool dense = !from_queue && !flat && !wk.live_ids && wk.pixel_major && (wk.samples & 63u) == 0;
+    const uint64_t items = flat ? kShadeGrid
+                                : (from_queue ? (uint64_t)max_chunks * kSubQueues
+                                              : (dense ? ((uint64_t)wk.n_pad + 3) / 4 : ((uint64_t)wk.samples * wk.n_pad + 255) / 256));
     uint32_t grid = (uint32_t)std::min<uint64_t>(items, kShadeGrid);
     if (grid == 0) grid = 1;
-#define VMX_GO(S, T, E, Q) \
-    hipLaunchKernelGGL((k_shade<S, T, E, Q>), dim3(grid), dim3(256), 0, s, sc, fr, wk, px, pa, qout, max_chunks, counters)
-#define VMX_GO_T(S, E, Q)                \
-    do {                                 \
-        if (sc.tex) VMX_GO(S, true, E, Q); \
-        else VMX_GO(S, false, E, Q);     \
+#define VMX_GO(S, T, E, Q, D) \
+    hipLaunchKernelGGL((k_shade<S, T, E, Q, D>), dim3(grid), dim3(256), 0, s, sc, fr, wk, px, pa, qout, max_chunks, counters)
+#define VMX_GO_T(S, E, Q, ...)                       \
+    do {                                             \
+        if (sc.tex) VMX_GO(S, true, E, Q, (false __VA_ARGS__)); \
+        else VMX_GO(S, false, E, Q, (false __VA_ARGS__));     \
     } while (0)
     // camera paths are shaded from the live list exactly when render_impl built one (wk.live_ids)
     const bool elide = from_queue ? fr.elide_dead != 0 : wk.live_ids != nullptr;
@@ -3521,6 +3676,7 @@ int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
         else VMX_GO_T(0, false, 1);
     } else {
         if (elide) VMX_GO_T(0, true, 0);
+        else if (dense) VMX_GO_T(0, false, 0, || true);
         else VMX_GO_T(0, false, 0);
     }
 #undef VMX_GO_T
