@@ -404,6 +404,49 @@ int vmx_render(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *op
  * Blocks until the frame is complete (the early-stop loop needs the host). */
 int vmx_render_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts,
                       void *d_out_rgbaz, void *stream, vmx_stats *stats);
+/* ---- progressive rendering: the same frame in resumable steps, with previews -------------------
+ * vmx_render is one blocking call that shows nothing before the last sample.  A vmx_progressive handle renders the same
+ * frame — bit for bit, whatever the steps — a few samples at a time, and can show its unfinished state in between.
+ *
+ * begin: cam / opts as vmx_render takes them (same checks and messages; everything vmx_render accepts, including
+ *   rank / world / stripes and the tuning words).  The handle owns its per-pixel state, a buffer for the finished pixels
+ *   and the pass schedule; the per-pass scratch stays the scene's shared workspace.  `stream`: a hipStream_t, NULL = the
+ *   scene's stream.  The target spp of a handle cannot change (the 2x2 stratification maps a sample index to its
+ *   stratum through spp / 4): a longer frame is a new handle.
+ * step: issues more samples and blocks until they are resolved (the pass loop needs the host, as in vmx_render).
+ *   `samples` is the most samples any pixel takes in this step; every pixel that was active before the step takes at
+ *   least one; 0 = run to completion.  How a step is cut into passes is the library's choice.  A step of a complete
+ *   frame is VMX_OK and does nothing.  `stats` (may be NULL) and vmx_scene_timings report this step alone.
+ * preview: for each local pixel, in the layout vmx_render writes (W*H*5 floats, or this rank's packed rows):
+ *     a finished pixel     exactly what vmx_render writes for it
+ *     n >= 1 samples so far  vmx_render's pixel write applied to the sums so far: clamped mean, alpha 1.f, depth (float)n
+ *     no sample yet        (0, 0, 0, 1, 0)
+ *   and / or rgba8[p*4 + c] = (unsigned char)floor(that * 255), c = 0..3 (vmx_quantize_device's arithmetic), in the same
+ *   launch.  At least one of the two outputs must be non-NULL.  The device variant takes DEVICE pointers of the scene's
+ *   device (checked as vmx_query_device checks its pointers; 4-byte aligned), is enqueued on the handle's stream and
+ *   returns without synchronising; the host variant synchronises.  A preview never changes the state.
+ * Between steps the scene may serve any other call — queries, raycasts, vmx_render, other handles — and the handle's
+ * frames do not change.  A geometry update (vmx_scene_update[_device], refit or rebuild) after begin makes every later
+ * step fail with VMX_ERR_INVALID ("scene updated since vmx_progressive_begin"): the handle's tuning and stack sizing
+ * came from the tree it saw.  preview, info and end still work on such a handle.  vmx_scene_destroy with open handles
+ * fails with VMX_ERR_INVALID and leaves the scene intact.
+ */
+typedef struct vmx_progressive vmx_progressive;
+typedef struct vmx_progressive_info {
+    uint32_t width, rows;   /* rows = this (rank, world)'s local rows, as vmx_local_rows            */
+    uint32_t kmax;          /* 4 * (rays_per_pixel / 4): the most samples a pixel can take         */
+    uint32_t pixels_active; /* pixels that still take samples; 0 = the frame is complete           */
+    uint64_t samples;       /* samples accumulated into the image so far                           */
+    uint64_t passes, steps; /* sample batches processed; steps that issued any                     */
+} vmx_progressive_info;
+int vmx_progressive_begin(vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, void *stream,
+                          vmx_progressive **out);
+int vmx_progressive_step(vmx_progressive *p, uint32_t samples, vmx_stats *stats);
+int vmx_progressive_info_get(const vmx_progressive *p, vmx_progressive_info *out);
+int vmx_progressive_preview_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8);
+int vmx_progressive_preview(vmx_progressive *p, float *rgbaz, unsigned char *rgba8);
+int vmx_progressive_end(vmx_progressive *p);
+
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers
  * back to back, each padded to `rank_stride_floats`; writes the W*H*5 frame.

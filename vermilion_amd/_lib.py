@@ -160,6 +160,21 @@ class RayHit(C.Structure):
     ]
 
 
+class ProgressiveInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("rows", C.c_uint32),
+        ("kmax", C.c_uint32),
+        ("pixels_active", C.c_uint32),
+        ("samples", C.c_uint64),
+        ("passes", C.c_uint64),
+        ("steps", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/vermilion_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -190,6 +205,12 @@ SYMBOLS = {
     "vmx_local_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "vmx_render": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_render_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, _P, C.POINTER(Stats)]),
+    "vmx_progressive_begin": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(_P)]),
+    "vmx_progressive_step": (C.c_int, [_P, C.c_uint32, C.POINTER(Stats)]),
+    "vmx_progressive_info_get": (C.c_int, [_P, C.POINTER(ProgressiveInfo)]),
+    "vmx_progressive_preview_device": (C.c_int, [_P, _P, _P]),
+    "vmx_progressive_preview": (C.c_int, [_P, _P, _P]),
+    "vmx_progressive_end": (C.c_int, [_P]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

@@ -211,6 +211,10 @@ int launch_bruteforce(const SceneDev &sc, const FrameDev &fr, const unsigned int
 int launch_bruteforce_long(const SceneDev &sc, const FrameDev &fr, uint32_t flags, float *out, DevCounters *counters,
                            const void *longs, const unsigned int *long_count, uint32_t count, const WorkDev &stack,
                            LaunchCfg cfg, void *stream);
+// progressive rendering (vmx_progressive_preview*): the frame of per-pixel state that may be unfinished; `finished` is the
+// buffer k_resolve wrote the finished pixels to; out_rgbaz / rgba8: either may be NULL
+int launch_preview(PixelStateDev px, uint32_t npix, uint32_t kmax, const float *finished, float *out_rgbaz, void *rgba8,
+                   void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

@@ -3088,6 +3088,22 @@ __global__ void k_radiance_init_ids(const float *__restrict__ o, const float *__
     }
 }
 
+// the pixel write (pathtracer.cpp:318-324) from a pixel's sums and sample count: what k_resolve stores for a finished
+// pixel and k_preview (vmx_preview.inc) shows for an unfinished one
+__device__ __forceinline__ void resolved_pixel(const float4 &acc, uint32_t n, float *o5) {
+    const float fn = (float)n;  // accum / nTotalSamples (uint -> float)
+    // std::max(std::min(x, 1.f), 0.f) (pathtracer.cpp:318-320): std::min(a, b) is (b < a) ? b : a, so a NaN mean —
+    // an infinite throughput times a black hit, possible with a texture that holds an infinity — stays NaN
+    // (fminf / fmaxf would return the other operand: found by tools/fuzz_parity.py's random textures, round 3)
+    const float mx = acc.x / fn, my = acc.y / fn, mz = acc.z / fn;
+    const float cx = 1.f < mx ? 1.f : mx, cy = 1.f < my ? 1.f : my, cz = 1.f < mz ? 1.f : mz;
+    o5[0] = cx < 0.f ? 0.f : cx;
+    o5[1] = cy < 0.f ? 0.f : cy;
+    o5[2] = cz < 0.f ? 0.f : cz;
+    o5[3] = 1.f;
+    o5[4] = fn;
+}
+
 // per-pixel accumulation in sample order + early stop + pixel write (pathtracer.cpp:282-324)
 __global__ void k_resolve(FrameDev fr, const unsigned int *__restrict__ active, uint32_t n_active,
                           uint32_t n_pad, uint32_t samples, uint32_t pixel_major, const float4 *__restrict__ rad,
@@ -3193,18 +3209,7 @@ __global__ void k_resolve(FrameDev fr, const unsigned int *__restrict__ active, 
             }
         }
         if (next >= fr.kmax) {
-            const float fn = (float)n;  // accum / nTotalSamples (uint -> float)
-            float *o5 = out + (size_t)lp * 5;
-            // std::max(std::min(x, 1.f), 0.f) (pathtracer.cpp:318-320): std::min(a, b) is (b < a) ? b : a, so a NaN mean —
-            // an infinite throughput times a black hit, possible with a texture that holds an infinity — stays NaN
-            // (fminf / fmaxf would return the other operand: found by tools/fuzz_parity.py's random textures, round 3)
-            const float mx = acc.x / fn, my = acc.y / fn, mz = acc.z / fn;
-            const float cx = 1.f < mx ? 1.f : mx, cy = 1.f < my ? 1.f : my, cz = 1.f < mz ? 1.f : mz;
-            o5[0] = cx < 0.f ? 0.f : cx;
-            o5[1] = cy < 0.f ? 0.f : cy;
-            o5[2] = cz < 0.f ? 0.f : cz;
-            o5[3] = 1.f;
-            o5[4] = fn;
+            resolved_pixel(acc, n, out + (size_t)lp * 5);
             done = 1;
         } else {
             keep = true;
@@ -3472,17 +3477,22 @@ __global__ void k_assemble(const float *__restrict__ gathered, uint64_t rank_str
     }
 }
 
+// Camera::saveFrame's conversion (camera.cpp:159-162) of one pixel: floor(x*255) -> u8
+__device__ __forceinline__ uchar4 quantized_pixel(const float *f) {
+    uchar4 o;
+    o.x = (unsigned char)floorf(f[0] * 255.0f);
+    o.y = (unsigned char)floorf(f[1] * 255.0f);
+    o.z = (unsigned char)floorf(f[2] * 255.0f);
+    o.w = (unsigned char)floorf(f[3] * 255.0f);
+    return o;
+}
+
 // Camera::saveFrame's conversion loop (camera.cpp:159-163): floor(x*255) -> u8, depth plane
 __global__ void k_quantize(const float *__restrict__ frame, uint64_t npix, uchar4 *__restrict__ rgba8,
                            float *__restrict__ depth) {
     for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (uint64_t)gridDim.x * blockDim.x) {
         const float *f = frame + p * 5;
-        uchar4 o;
-        o.x = (unsigned char)floorf(f[0] * 255.0f);
-        o.y = (unsigned char)floorf(f[1] * 255.0f);
-        o.z = (unsigned char)floorf(f[2] * 255.0f);
-        o.w = (unsigned char)floorf(f[3] * 255.0f);
-        rgba8[p] = o;
+        rgba8[p] = quantized_pixel(f);
         if (depth) depth[p] = f[4];
     }
 }
@@ -3779,6 +3789,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 
 // in-place geometry updates: record rewrite and per-level refit
 #include "vmx_update.inc"
+
+// progressive rendering: the displayable frame of unfinished per-pixel state
+#include "vmx_preview.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

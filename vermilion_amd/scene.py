@@ -152,8 +152,9 @@ class Scene:
             raise L.VmxError(code, self._lib.vmx_last_error().decode("utf-8", "replace"))
 
     def close(self):
+        """vmx_scene_destroy; raises (and keeps the scene) while a progressive render of it is open"""
         if getattr(self, "_h", None):
-            self._lib.vmx_scene_destroy(self._h)
+            self._check(self._lib.vmx_scene_destroy(self._h))
             self._h = None
 
     def __del__(self):
@@ -421,6 +422,12 @@ class Scene:
         self._check(self._lib.vmx_render(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
+    def progressive(self, cam, opts, stream=None):
+        """vmx_progressive_begin: the frame `render(cam, opts)` returns, rendered in resumable steps with previews in
+        between (a context-managed Progressive).  stream: a torch stream the passes and previews run on (default: the
+        scene's own stream)."""
+        return Progressive(self, cam, opts, stream)
+
     def render_bruteforce(self, cam, opts, flags=0):
         """BruteForceTracer::Render (core/integrators/integrators.cpp:9-186) into a host array
         [local_rows, W, 5]: r, g, b, alpha = hit fraction, depth = last sample's hit distance."""
@@ -437,6 +444,86 @@ class Scene:
         self._check(self._lib.vmx_render_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(d_out_ptr),
                                           C.c_void_p(stream_ptr or 0), C.byref(st)))
         return st.as_dict()
+
+
+class Progressive:
+    """One vmx_progressive handle: `step` issues samples, `preview` shows the frame so far, and the frame a completed
+    handle previews is `Scene.render`'s, bit for bit, whatever the steps were."""
+
+    def __init__(self, scene, cam, opts, stream=None):
+        self._scene = scene  # (keeps the scene alive: it cannot be destroyed before its handles)
+        self._lib = scene._lib
+        self._h = None
+        self.device = scene.device
+        self._stream = stream
+        rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
+        self.shape = (rows, int(cam.image_res[0]))
+        h = C.c_void_p()
+        scene._check(self._lib.vmx_progressive_begin(scene._h, C.byref(cam), C.byref(opts),
+                                                     C.c_void_p(stream.cuda_stream if stream is not None else 0),
+                                                     C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._scene._check(self._lib.vmx_progressive_end(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def step(self, samples=0):
+        """up to `samples` more samples per pixel (0: run to completion); blocks; this step's vmx_stats as a dict"""
+        st = L.Stats()
+        self._scene._check(self._lib.vmx_progressive_step(self._h, int(samples), C.byref(st)))
+        return st.as_dict()
+
+    def info(self):
+        i = L.ProgressiveInfo()
+        self._scene._check(self._lib.vmx_progressive_info_get(self._h, C.byref(i)))
+        return i.as_dict()
+
+    def preview(self, rgba8=False):
+        """the frame so far as a host array [local_rows, W, 5] (RGBAZ, depth = samples taken); rgba8=True: also its
+        [local_rows, W, 4] uint8 form, from the same launch"""
+        out = np.empty(self.shape + (5,), np.float32)
+        q = np.empty(self.shape + (4,), np.uint8) if rgba8 else None
+        self._scene._check(self._lib.vmx_progressive_preview(self._h, out.ctypes.data, None if q is None else q.ctypes.data))
+        return (out, q) if rgba8 else out
+
+    def preview_device(self, rgbaz=None, rgba8=None):
+        """vmx_progressive_preview_device into torch tensors on the scene's device: rgbaz float32 [local_rows, W, 5]
+        and / or rgba8 uint8 [local_rows, W, 4], contiguous — anything else is a ValueError, never a copy through the
+        host.  Enqueued on the handle's stream, nothing synchronised; returns (rgbaz, rgba8)."""
+        import torch
+        if rgbaz is None and rgba8 is None:
+            raise ValueError("no output: rgbaz and rgba8 are both None")
+        dev = torch.device("cuda", self.device)
+        for x, name, dtype, last in ((rgbaz, "rgbaz", torch.float32, 5), (rgba8, "rgba8", torch.uint8, 4)):
+            if x is None:
+                continue
+            if not _is_tensor(x):
+                raise ValueError(f"{name} must be a torch tensor")
+            if x.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype} (got {x.dtype})")
+            if tuple(x.shape) != self.shape + (last,):
+                raise ValueError(f"{name} must be {list(self.shape + (last,))} (got {list(x.shape)})")
+            if not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if x.device != dev:
+                raise ValueError(f"{name} must be on {dev} (got {x.device})")
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        self._scene._check(self._lib.vmx_progressive_preview_device(self._h, ptr(rgbaz), ptr(rgba8)))
+        return rgbaz, rgba8
 
 
 class MultiScene:
