@@ -447,6 +447,67 @@ int vmx_progressive_preview_device(vmx_progressive *p, void *d_rgbaz, void *d_rg
 int vmx_progressive_preview(vmx_progressive *p, float *rgbaz, unsigned char *rgba8);
 int vmx_progressive_end(vmx_progressive *p);
 
+/* ---- G-buffer-guided denoising of frames and previews ---------------------------------------------
+ * A few-sample frame of the reference's sampling is salt-and-pepper (nine in ten diffuse
+ * bounces end the path, the lights are far brighter than 1 and the pixel write clamps).  This is the edge-avoiding
+ * a-trous filter of Dammertz et al. 2010, guided by a vmx_rayhit G-buffer (what vmx_raycast_camera_device writes): per
+ * pixel the guide is (normal, distance) where flags bit 0 is set and ((0, 0, 0), -1) elsewhere; "a hit" is z >= 0.
+ * Colour c = r, g, b of an RGBAZ pixel; alpha and depth pass through, bitwise.
+ *
+ * For iteration it = 0 .. iterations-1, all in float, one rounding per written operation, left to right:
+ *   s = 1 << it;  sc_0 = sigma_colour, sc_{it+1} = sc_it * 0.5f;  isc2 = 1.f / (sc_it * sc_it);  kz = sigma_depth * (float)s
+ *   per pixel p: isz = 1.f / (kz * z_p) (used where p is a hit); sum_c = (0, 0, 0), sum_w = 0
+ *   taps dy = -2..2 (outer), dx = -2..2 (inner), q = p + s * (dx, dy); a tap outside the image or with
+ *   (z_q >= 0) != (z_p >= 0) is skipped;  hh = h[dy+2] * h[dx+2], h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *     p a hit:  d = n_p.x*n_q.x + n_p.y*n_q.y + n_p.z*n_q.z;  d = d > 0 ? d : 0;  normal_squarings times d = d*d;
+ *               t = (z_p - z_q) * isz;  num = hh * d;  g = 1.f + t*t          p a miss:  num = hh;  g = 1.f
+ *     e = dr*dr + dg*dg + db*db, d. = c_p. - c_q. of this iteration's input;  w = num / (g * (1.f + e * isc2))
+ *     if w > 0 and finite:  sum_c. = sum_c. + w * c_q.;  sum_w = sum_w + w     (the centre tap is a tap like any other)
+ *   out. = sum_w > 0 ? sum_c. / sum_w : c_p.   (the fallback: a zero or NaN normal, a NaN colour, a z_p so small that
+ *   isz overflows).  Denormals are kept.  Iterations ping-pong between the filter's planes; the last one writes the
+ *   caller's RGBAZ buffer and / or rgba8 (vmx_quantize_device's arithmetic on that output pixel).
+ * The kernels hold to this restatement bit for bit (tests/filter_spec.py).
+ */
+typedef struct vmx_filter_params {
+    uint32_t iterations, normal_squarings; /* 1..10 (default 5); 0..8 (default 5)                 */
+    float sigma_colour, sigma_depth;       /* finite, > 0 (defaults 2.f, 0.1f)                    */
+    uint32_t reserved[4];                  /* must be 0                                           */
+} vmx_filter_params;
+
+typedef struct vmx_filter vmx_filter;
+
+int vmx_filter_default_params(vmx_filter_params *out);
+/* A filter for width x height frames on `device`.  It owns the guide (16 B per pixel) and two colour planes (16 B per
+ * pixel each); nothing is allocated after creation.  width or height 0, or a frame vmx_render would call too large, is
+ * VMX_ERR_INVALID; without a usable device VMX_ERR_NO_DEVICE. */
+int vmx_filter_create(int device, uint32_t width, uint32_t height, vmx_filter **out);
+int vmx_filter_destroy(vmx_filter *f);
+/* d_rayhit: width*height vmx_rayhit records in pixel order (what vmx_raycast_camera_device writes), packed into the
+ * filter's guide on `stream` (a hipStream_t; NULL = the legacy default stream).  The guide stays until the next call. */
+int vmx_filter_set_guide_device(vmx_filter *f, const void *d_rayhit, void *stream);
+/* Filters the W*H*5-float frame d_in_rgbaz into d_out_rgbaz (same layout) and / or d_rgba8 (W*H*4 bytes); at least one
+ * of the two must be non-NULL.  params == NULL selects the defaults; a field out of range or a non-zero reserved word
+ * is VMX_ERR_INVALID before any launch, as is a call before any guide was set.  d_out_rgbaz == d_in_rgbaz (in place)
+ * is allowed; any other overlap of the three buffers is VMX_ERR_INVALID.  Pointers are checked as vmx_query_device
+ * checks its own (DEVICE memory of the filter's device) and must be 4-byte aligned.  Enqueued on `stream`, no
+ * synchronisation.  Calls on one handle from different streams are ordered by enqueue (each waits on an event the
+ * previous one recorded), so they never share the guide and the planes while in flight. */
+int vmx_filter_apply_device(vmx_filter *f, const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8,
+                            const vmx_filter_params *params, void *stream);
+/* vmx_progressive_preview[_device]'s frame pushed through the filter, bit for bit, at any point of the frame (no sample
+ * yet, a complete frame); the outputs follow the plain previews' rules.  The first iteration reads the per-pixel state
+ * itself.  On its first filtered preview a handle builds its guide — sample 0's camera ray of every pixel from its own
+ * camera and seed, through vmx_raycast_camera_device's code path — and creates its filter; that call blocks until the
+ * guide is built.  Both are freed by vmx_progressive_end.  A filtered preview never changes the handle's state.
+ * VMX_ERR_INVALID: a handle begun with opts->world > 1 ("whole images only", vmx_raycast_camera_device's rule), and
+ * a first filtered preview after a geometry update ("scene updated since vmx_progressive_begin": the guide cannot be
+ * built from the tree the handle saw); a guide built before the update keeps working.  The device variant runs on
+ * the handle's stream and does not synchronise (after the first call); the host variant synchronises. */
+int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8,
+                                            const vmx_filter_params *params);
+int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8,
+                                     const vmx_filter_params *params);
+
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers
  * back to back, each padded to `rank_stride_floats`; writes the W*H*5 frame.

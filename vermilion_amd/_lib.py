@@ -175,6 +175,20 @@ class ProgressiveInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FilterParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("normal_squarings", C.c_uint32),
+        ("sigma_colour", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+    def as_dict(self):
+        return {"iterations": self.iterations, "normal_squarings": self.normal_squarings,
+                "sigma_colour": self.sigma_colour, "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
+
+
 # every symbol include/vermilion_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -211,6 +225,13 @@ SYMBOLS = {
     "vmx_progressive_preview_device": (C.c_int, [_P, _P, _P]),
     "vmx_progressive_preview": (C.c_int, [_P, _P, _P]),
     "vmx_progressive_end": (C.c_int, [_P]),
+    "vmx_filter_default_params": (C.c_int, [C.POINTER(FilterParams)]),
+    "vmx_filter_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "vmx_filter_destroy": (C.c_int, [_P]),
+    "vmx_filter_set_guide_device": (C.c_int, [_P, _P, _P]),
+    "vmx_filter_apply_device": (C.c_int, [_P, _P, _P, _P, C.POINTER(FilterParams), _P]),
+    "vmx_progressive_preview_filtered_device": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
+    "vmx_progressive_preview_filtered": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

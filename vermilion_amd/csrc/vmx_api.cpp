@@ -2037,6 +2037,183 @@ int vmx_render(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts
     return VMX_OK;
 }
 
+// ---- G-buffer-guided a-trous filter (k_filter_guide, k_atrous: vmx_filter.inc) ------------------------------------------
+struct vmx_filter {
+    int device = 0;
+    uint32_t width = 0, height = 0;
+    DevBuf<unsigned char> guide;   // float4 (n.xyz, z) per pixel
+    DevBuf<unsigned char> planes;  // two float4 colour planes, back to back (an in-place single iteration stages its
+                                   // 20-byte pixels here instead)
+    // `done` is recorded after each call's last kernel and waited on by the next one, whatever its stream: one call at a
+    // time uses the guide and the planes (the query workspace's scheme)
+    hipEvent_t done = nullptr;
+    bool recorded = false, guide_set = false;
+    std::mutex mu;
+};
+
+static void filter_release(vmx_filter *f) {
+    f->guide.release(), f->planes.release();
+    if (f->done) (void)hipEventDestroy(f->done);
+    delete f;
+}
+
+// buffers and event of a filter for width x height frames on `device`, the current device
+static int filter_make(int device, uint32_t width, uint32_t height, vmx_filter **out) {
+    vmx_filter *f = new (std::nothrow) vmx_filter;
+    if (!f) return fail(VMX_ERR_NOMEM, "out of host memory");
+    f->device = device, f->width = width, f->height = height;
+    const size_t npix = (size_t)width * height;
+    int rc = VMX_OK;
+    if (f->guide.ensure(npix * 16) || f->planes.ensure(npix * 32)) rc = fail(VMX_ERR_NOMEM, "hipMalloc failed for the filter's planes");
+    if (rc == VMX_OK && hipEventCreateWithFlags(&f->done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(VMX_ERR_HIP, "hipEventCreate failed");
+    }
+    if (rc) {
+        filter_release(f);
+        return rc;
+    }
+    *out = f;
+    return VMX_OK;
+}
+
+static const vmx_filter_params kFilterDefaults = {5u, 5u, 2.f, 0.1f, {0u, 0u, 0u, 0u}};
+
+// NULL selects the defaults; anything out of range is refused before any launch
+static int filter_params(const vmx_filter_params *in, vmx_filter_params &out) {
+    out = in ? *in : kFilterDefaults;
+    if (out.iterations < 1 || out.iterations > 10) return fail(VMX_ERR_INVALID, "vmx_filter_params: iterations must be 1..10");
+    if (out.normal_squarings > 8) return fail(VMX_ERR_INVALID, "vmx_filter_params: normal_squarings must be 0..8");
+    if (!(std::isfinite(out.sigma_colour) && out.sigma_colour > 0.f))
+        return fail(VMX_ERR_INVALID, "vmx_filter_params: sigma_colour must be finite and > 0");
+    if (!(std::isfinite(out.sigma_depth) && out.sigma_depth > 0.f))
+        return fail(VMX_ERR_INVALID, "vmx_filter_params: sigma_depth must be finite and > 0");
+    for (uint32_t r : out.reserved)
+        if (r) return fail(VMX_ERR_INVALID, "vmx_filter_params: reserved words must be 0");
+    return VMX_OK;
+}
+
+// a call's kernels on `s` run after the previous call on this handle
+static int filter_begin(vmx_filter *f, hipStream_t s) {
+    if (f->recorded) HIP_TRY(hipStreamWaitEvent(s, f->done, 0));
+    return VMX_OK;
+}
+
+static int filter_end(vmx_filter *f, hipStream_t s) {
+    HIP_TRY(hipEventRecord(f->done, s));
+    f->recorded = true;
+    return VMX_OK;
+}
+
+static int filter_guide_enqueue(vmx_filter *f, const void *d_rayhit, hipStream_t s) {
+    if (int rc = filter_begin(f, s)) return rc;
+    LAUNCH_TRY(launch_filter_guide(d_rayhit, f->width * f->height, f->guide.p, s));
+    f->guide_set = true;
+    return filter_end(f, s);
+}
+
+// the iterations of one call on `s`; the caller holds f->mu and has checked arguments and pointers
+static int filter_enqueue(vmx_filter *f, FilterSrc src, float *out, void *rgba8, const vmx_filter_params &prm, hipStream_t s) {
+    if (int rc = filter_begin(f, s)) return rc;
+    const size_t npix = (size_t)f->width * f->height;
+    // one iteration in place would read neighbours another block has already replaced: it filters a copy of the frame
+    if (prm.iterations == 1 && src.frame && src.frame == out) {
+        HIP_TRY(hipMemcpyAsync(f->planes.p, src.frame, npix * 20, hipMemcpyDeviceToDevice, s));
+        src.frame = (const float *)f->planes.p;
+    }
+    FilterPass a{};
+    a.width = f->width, a.height = f->height;
+    a.squarings = prm.normal_squarings;
+    a.guide = f->guide.p;
+    a.src = src;
+    unsigned char *plane[2] = {f->planes.p, f->planes.p + npix * 16};
+    float sc = prm.sigma_colour;
+    for (uint32_t it = 0; it < prm.iterations; ++it) {
+        a.step = 1u << it;
+        a.isc2 = 1.f / (sc * sc);
+        a.kz = prm.sigma_depth * (float)a.step;
+        sc = sc * 0.5f;
+        a.first = it == 0, a.last = it + 1 == prm.iterations;
+        a.in_plane = a.first ? nullptr : plane[(it - 1) & 1];
+        a.out_plane = a.last ? nullptr : plane[it & 1];
+        a.out_rgbaz = a.last ? out : nullptr;
+        a.rgba8 = a.last ? rgba8 : nullptr;
+        LAUNCH_TRY(launch_atrous(a, s));
+    }
+    return filter_end(f, s);
+}
+
+int vmx_filter_default_params(vmx_filter_params *out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    *out = kFilterDefaults;
+    return VMX_OK;
+}
+
+int vmx_filter_create(int device, uint32_t width, uint32_t height, vmx_filter **out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(VMX_ERR_INVALID, "image resolution must be non-zero");
+    if ((uint64_t)width * height > 0x7fffffffull / 8) return fail(VMX_ERR_INVALID, "image too large");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    return filter_make(device, width, height, out);
+}
+
+int vmx_filter_destroy(vmx_filter *f) {
+    if (!f) return fail(VMX_ERR_INVALID, "NULL handle");
+    (void)hipSetDevice(f->device);
+    if (f->recorded) (void)hipEventSynchronize(f->done);  // the last call may still use the planes
+    filter_release(f);
+    return VMX_OK;
+}
+
+int vmx_filter_set_guide_device(vmx_filter *f, const void *d_rayhit, void *stream) {
+    if (!d_rayhit) return fail(VMX_ERR_INVALID, "NULL d_rayhit");
+    if ((uintptr_t)d_rayhit & 15u) return fail(VMX_ERR_INVALID, "d_rayhit must be 16-byte aligned");
+    if (!f) return fail(VMX_ERR_INVALID, "NULL handle");
+    std::lock_guard<std::mutex> lock(f->mu);
+    HIP_TRY(hipSetDevice(f->device));
+    if (int rc = check_device_ptr(d_rayhit, f->device, "d_rayhit")) return rc;
+    return filter_guide_enqueue(f, d_rayhit, (hipStream_t)stream);
+}
+
+int vmx_filter_apply_device(vmx_filter *f, const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8,
+                            const vmx_filter_params *params, void *stream) {
+    // checks that need no device, in this order so that each can be seen alone; the handle comes last
+    vmx_filter_params prm;
+    if (int rc = filter_params(params, prm)) return rc;
+    if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
+    if (!d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
+    if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8) & 3u)
+        return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz and d_rgba8 must be 4-byte aligned");
+    if (!f) return fail(VMX_ERR_INVALID, "NULL handle");
+    std::lock_guard<std::mutex> lock(f->mu);
+    {
+        // in place (d_out_rgbaz == d_in_rgbaz) is the one overlap a call may have
+        const uintptr_t npix = (uintptr_t)f->width * f->height;
+        const uintptr_t lo[3] = {(uintptr_t)d_in_rgbaz, (uintptr_t)d_out_rgbaz, (uintptr_t)d_rgba8};
+        const uintptr_t len[3] = {npix * 20, npix * 20, npix * 4};
+        for (int i = 0; i < 3; ++i)
+            for (int j = i + 1; j < 3; ++j) {
+                if (!lo[i] || !lo[j] || (i == 0 && j == 1 && lo[0] == lo[1])) continue;
+                if (lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i])
+                    return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz and d_rgba8 overlap (only d_out_rgbaz == d_in_rgbaz may)");
+            }
+    }
+    if (!f->guide_set) return fail(VMX_ERR_INVALID, "no guide: call vmx_filter_set_guide_device first");
+    HIP_TRY(hipSetDevice(f->device));
+    const void *ptrs[3] = {d_in_rgbaz, d_out_rgbaz, d_rgba8};
+    const char *names[3] = {"d_in_rgbaz", "d_out_rgbaz", "d_rgba8"};
+    for (int i = 0; i < 3; ++i)
+        if (int rc = check_device_ptr(ptrs[i], f->device, names[i])) return rc;
+    FilterSrc src{};
+    src.frame = (const float *)d_in_rgbaz;
+    return filter_enqueue(f, src, (float *)d_out_rgbaz, d_rgba8, prm, (hipStream_t)stream);
+}
+
 // ---- progressive rendering: a frame in resumable runs of passes, previews of the unfinished state --------------------
 struct vmx_progressive {
     vmx_scene *sc = nullptr;
@@ -2045,6 +2222,8 @@ struct vmx_progressive {
     DevBuf<float> frame;            // k_resolve's output: the finished pixels
     DevBuf<float> host_rgbaz;       // vmx_progressive_preview: device side of the host buffers, on first use
     DevBuf<unsigned char> host_rgba8;
+    vmx_camera cam;                 // as begun: the filtered previews' guide is sample 0's camera ray of every pixel
+    vmx_filter *filter = nullptr;   // vmx_progressive_preview_filtered*: created, and its guide built, on first use
     uint64_t generation = 0;        // the scene's when the handle began
     uint64_t samples = 0, passes = 0, steps = 0;
     bool failed = false;            // a step stopped half way: the schedule and the device state may disagree
@@ -2052,6 +2231,7 @@ struct vmx_progressive {
 
 static void progressive_release(vmx_progressive *p) {
     p->pixels.release(), p->frame.release(), p->host_rgbaz.release(), p->host_rgba8.release();
+    if (p->filter) filter_release(p->filter);
     delete p;
 }
 
@@ -2070,6 +2250,7 @@ int vmx_progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *
     vmx_progressive *p = new (std::nothrow) vmx_progressive;
     if (!p) return fail(VMX_ERR_NOMEM, "out of host memory");
     p->sc = sc;
+    p->cam = *cam;
     p->generation = sc->generation;
     int rc = render_setup(sc, cam, opts, &p->pixels, nullptr, stream ? (hipStream_t)stream : sc->stream, p->job);
     if (rc == VMX_OK && p->job.npix) {
@@ -2156,6 +2337,78 @@ int vmx_progressive_preview(vmx_progressive *p, float *rgbaz, unsigned char *rgb
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the preview buffers");
     LAUNCH_TRY(launch_preview(PixelStateDev{p->pixels.accum.p, p->pixels.count.p, p->pixels.cursor.p}, job.npix, job.fr.kmax,
                               p->frame.p, rgbaz ? p->host_rgbaz.p : nullptr, rgba8 ? p->host_rgba8.p : nullptr, job.s));
+    if (rgbaz) HIP_TRY(hipMemcpyAsync(rgbaz, p->host_rgbaz.p, npix * 20, hipMemcpyDeviceToHost, job.s));
+    if (rgba8) HIP_TRY(hipMemcpyAsync(rgba8, p->host_rgba8.p, npix * 4, hipMemcpyDeviceToHost, job.s));
+    HIP_TRY(hipStreamSynchronize(job.s));
+    return VMX_OK;
+}
+
+// first filtered preview of a handle: its filter, and the guide from sample 0's camera ray of every pixel (the code path
+// of vmx_raycast_camera_device); blocks until the guide is built, because the G-buffer it is packed from is freed here
+static int progressive_filter_ensure(vmx_progressive *p) {
+    if (p->filter) return VMX_OK;
+    vmx_scene *sc = p->sc;
+    if (p->job.opts.world > 1) return fail(VMX_ERR_INVALID, "world > 1: a filtered preview is guided by the camera raycast (whole images only)");
+    if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
+    FrameDev fr;
+    if (int rc = make_frame(p->cam, p->job.opts, fr)) return rc;
+    const uint32_t npix = fr.width * fr.height;
+    vmx_filter *f = nullptr;
+    if (int rc = filter_make(sc->device, fr.width, fr.height, &f)) return rc;
+    DevBuf<unsigned char> gbuf;
+    int rc = gbuf.ensure((size_t)npix * sizeof(vmx_rayhit)) ? fail(VMX_ERR_NOMEM, "hipMalloc failed for the G-buffer") : VMX_OK;
+    if (rc == VMX_OK) rc = raycast_enqueue(sc, true, true, nullptr, nullptr, npix, fr, 0, gbuf.p, p->job.s);
+    if (rc == VMX_OK) rc = filter_guide_enqueue(f, gbuf.p, p->job.s);
+    const hipError_t e = hipStreamSynchronize(p->job.s);
+    gbuf.release();
+    if (rc == VMX_OK && e != hipSuccess) rc = fail(VMX_ERR_HIP, std::string("vmx_progressive_preview_filtered: ") + hipGetErrorString(e));
+    if (rc) {
+        filter_release(f);
+        return rc;
+    }
+    p->filter = f;
+    return VMX_OK;
+}
+
+static int progressive_filter_enqueue(vmx_progressive *p, float *d_rgbaz, void *d_rgba8, const vmx_filter_params &prm) {
+    if (int rc = progressive_filter_ensure(p)) return rc;
+    FilterSrc src{};
+    src.px = PixelStateDev{p->pixels.accum.p, p->pixels.count.p, p->pixels.cursor.p};
+    src.finished = p->frame.p;
+    src.kmax = p->job.fr.kmax;
+    std::lock_guard<std::mutex> lock(p->filter->mu);
+    return filter_enqueue(p->filter, src, d_rgbaz, d_rgba8, prm, p->job.s);
+}
+
+int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8, const vmx_filter_params *params) {
+    vmx_filter_params prm;
+    if (int rc = filter_params(params, prm)) return rc;
+    if (int rc = preview_args(p, d_rgbaz, d_rgba8)) return rc;
+    if (((uintptr_t)d_rgbaz | (uintptr_t)d_rgba8) & 3u) return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 must be 4-byte aligned");
+    vmx_scene *sc = p->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    if (int rc = check_device_ptr(d_rgbaz, sc->device, "d_rgbaz")) return rc;
+    if (int rc = check_device_ptr(d_rgba8, sc->device, "d_rgba8")) return rc;
+    if (d_rgbaz && d_rgba8) {
+        const uintptr_t a = (uintptr_t)d_rgbaz, b = (uintptr_t)d_rgba8, n = p->job.npix;
+        if (a < b + n * 4 && b < a + n * 20) return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 overlap");
+    }
+    return progressive_filter_enqueue(p, (float *)d_rgbaz, d_rgba8, prm);
+}
+
+int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8, const vmx_filter_params *params) {
+    vmx_filter_params prm;
+    if (int rc = filter_params(params, prm)) return rc;
+    if (int rc = preview_args(p, rgbaz, rgba8)) return rc;
+    vmx_scene *sc = p->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    const RenderJob &job = p->job;
+    const size_t npix = job.npix;
+    if ((rgbaz && p->host_rgbaz.ensure(npix * 5)) || (rgba8 && p->host_rgba8.ensure(npix * 4)))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the preview buffers");
+    if (int rc = progressive_filter_enqueue(p, rgbaz ? p->host_rgbaz.p : nullptr, rgba8 ? p->host_rgba8.p : nullptr, prm)) return rc;
     if (rgbaz) HIP_TRY(hipMemcpyAsync(rgbaz, p->host_rgbaz.p, npix * 20, hipMemcpyDeviceToHost, job.s));
     if (rgba8) HIP_TRY(hipMemcpyAsync(rgba8, p->host_rgba8.p, npix * 4, hipMemcpyDeviceToHost, job.s));
     HIP_TRY(hipStreamSynchronize(job.s));

@@ -1,0 +1,182 @@
+// vmx_filter.inc — G-buffer-guided edge-avoiding a-trous filter of frames and progressive previews (vmx_filter_*,
+// vmx_progressive_preview_filtered*).  Included by vmx_kernels.hip (inside its namespace).  The arithmetic is stated
+// in include/vermilion_hip.h and restated in tests/filter_spec.py; with -ffp-contract=off every operation below rounds
+// once, in the order written, and `/` is the correctly rounded division with denormals kept: bit for bit the restatement.
+//
+//   k_filter_guide  one lane per pixel: the 64-byte vmx_rayhit becomes the 16-byte guide record (n.xyz, z); z = -1 and
+//                   n = 0 where the ray missed ("a hit" is z >= 0 from here on).
+//   k_atrous        one iteration, one lane per pixel, blocks of 32 x 8 pixels: a wave is two image rows of 32 pixels, so
+//                   each of its tap loads is two runs of 32 consecutive 16-byte records at every step size.  The 25 taps
+//                   are unrolled; the centre's guide and colour stay in registers; hit / miss and every skip rule are
+//                   selects, not branches (a tap outside the image loads the centre's records and is selected away).
+//                   IN: where the colours come from — 0 a float4 plane (every iteration but the first), 1 the RGBAZ
+//                   frame, 2 the per-pixel state of a progressive render, shown as k_preview shows it.
+//                   LAST: the iteration that writes the caller's buffers.  Alpha and depth are read again from the first
+//                   input (own pixel only) and the block's 256 pixels — eight runs of 160 floats — leave through LDS as
+//                   dword stores of consecutive lanes to consecutive addresses, as in k_preview; rgba8 from the same
+//                   values.  Else the result goes to the other float4 plane.
+//                   M: normal_squarings as a constant (the default, 5) or -1: read from the pass.
+constexpr uint32_t kFilterBX = 32, kFilterBY = 8, kFilterBlock = kFilterBX * kFilterBY;
+
+__global__ void __launch_bounds__(256) k_filter_guide(const float4 *__restrict__ rayhit, uint32_t npix,
+                                                      float4 *__restrict__ guide) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const float4 *r = rayhit + (size_t)p * 4;  // (location, distance) (normal, tri_id) (uv, tri_t, flags) (colour, pad)
+    const float4 a = r[0], b = r[1], c = r[2];
+    const bool hit = (__float_as_uint(c.w) & 1u) != 0;
+    guide[p] = hit ? make_float4(b.x, b.y, b.z, a.w) : make_float4(0.f, 0.f, 0.f, -1.f);
+}
+
+// pixel q of the filter's first input: the five floats of the frame, or what k_preview shows for that pixel's state
+template <bool STATE>
+__device__ __forceinline__ void filter_src_pixel(const FilterSrc &s, uint32_t q, float *v) {
+    if (!STATE) {
+        const float *f = s.frame + (size_t)q * 5;
+        v[0] = f[0], v[1] = f[1], v[2] = f[2], v[3] = f[3], v[4] = f[4];
+    } else if ((s.px.cursor[q] & ~kCursorStrided) >= s.kmax) {
+        const float *f = s.finished + (size_t)q * 5;
+        v[0] = f[0], v[1] = f[1], v[2] = f[2], v[3] = f[3], v[4] = f[4];
+    } else {
+        const uint32_t n = s.px.count[q];
+        if (n == 0) {
+            v[0] = 0.f, v[1] = 0.f, v[2] = 0.f, v[3] = 1.f, v[4] = 0.f;
+        } else {
+            resolved_pixel(((const float4 *)s.px.accum)[q], n, v);
+        }
+    }
+}
+
+template <int IN>
+__device__ __forceinline__ void filter_colour(const FilterPass &a, uint32_t q, float *c) {
+    if (IN == 0) {
+        const float4 v = ((const float4 *)a.in_plane)[q];
+        c[0] = v.x, c[1] = v.y, c[2] = v.z;
+    } else {
+        float v[5];
+        filter_src_pixel<IN == 2>(a.src, q, v);
+        c[0] = v[0], c[1] = v[1], c[2] = v[2];
+    }
+}
+
+template <int IN, bool LAST, int M>
+__global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
+    __shared__ float s_px[LAST ? kFilterBlock * 5 : 1];
+    const uint32_t W = a.width, H = a.height;
+    // (a one-dimensional grid of blocks, row-major over the image: the second grid dimension ends at 65535)
+    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
+    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
+    const uint32_t x = bx * kFilterBX + (threadIdx.x & (kFilterBX - 1));
+    const uint32_t y = by * kFilterBY + threadIdx.x / kFilterBX;
+    const bool live = x < W && y < H;
+    const uint32_t p = y * W + x;  // (W * H <= 2^28: make_frame's size check)
+    float o[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        const float4 *guide = (const float4 *)a.guide;
+        const float4 gp = guide[p];
+        float cp[3];
+        filter_colour<IN>(a, p, cp);
+        const bool hitp = gp.w >= 0.f;
+        const float isc2 = a.isc2;
+        const float isz = 1.f / (a.kz * gp.w);
+        const int step = (int)a.step;
+        const uint32_t m = M >= 0 ? (uint32_t)M : a.squarings;
+        float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumw = 0.f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const float h5[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+                const float hh = h5[dy + 2] * h5[dx + 2];
+                const int qx = (int)x + dx * step, qy = (int)y + dy * step;
+                const bool inside = (uint32_t)qx < W && (uint32_t)qy < H;
+                const uint32_t q = inside ? (uint32_t)qy * W + (uint32_t)qx : p;
+                const float4 gq = guide[q];
+                float cq[3];
+                filter_colour<IN>(a, q, cq);
+                float d = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+                d = d > 0.f ? d : 0.f;
+                if (M >= 0) {
+#pragma unroll
+                    for (int i = 0; i < M; ++i) d = d * d;
+                } else {
+                    for (uint32_t i = 0; i < m; ++i) d = d * d;
+                }
+                const float t = (gp.w - gq.w) * isz;
+                const float num = hitp ? hh * d : hh;
+                const float g = hitp ? 1.f + t * t : 1.f;
+                const float dr = cp[0] - cq[0], dg = cp[1] - cq[1], db = cp[2] - cq[2];
+                const float e = dr * dr + dg * dg + db * db;
+                const float w = num / (g * (1.f + e * isc2));
+                // contributes only if positive and finite (a NaN fails both comparisons)
+                const bool ok = inside && ((gq.w >= 0.f) == hitp) && w > 0.f && w <= 3.402823466e+38f;
+                sum0 = ok ? sum0 + w * cq[0] : sum0;
+                sum1 = ok ? sum1 + w * cq[1] : sum1;
+                sum2 = ok ? sum2 + w * cq[2] : sum2;
+                sumw = ok ? sumw + w : sumw;
+            }
+        }
+        const bool any = sumw > 0.f;
+        o[0] = any ? sum0 / sumw : cp[0];
+        o[1] = any ? sum1 / sumw : cp[1];
+        o[2] = any ? sum2 / sumw : cp[2];
+    }
+    if (!LAST) {
+        if (live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], 0.f);
+        return;
+    } else {
+        if (live) {
+            float *v = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
+            float src[5];
+            if (a.src.frame)
+                filter_src_pixel<false>(a.src, p, src);
+            else
+                filter_src_pixel<true>(a.src, p, src);
+            v[0] = o[0], v[1] = o[1], v[2] = o[2], v[3] = src[3], v[4] = src[4];  // alpha, depth: the input's bits
+            if (a.rgba8) ((uchar4 *)a.rgba8)[p] = quantized_pixel(v);
+        }
+        if (!a.out_rgbaz) return;
+        __syncthreads();
+        // row r of the block is the run of 5 * (its pixels in the image) floats at ((y0 + r) * W + x0) * 5
+        const uint32_t x0 = bx * kFilterBX, y0 = by * kFilterBY;
+        const uint32_t run = min(kFilterBX, W - x0) * 5;
+#pragma unroll
+        for (uint32_t c = 0; c < 5; ++c) {
+            const uint32_t i = c * kFilterBlock + threadIdx.x;
+            const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
+            if (y0 + r < H && col < run) a.out_rgbaz[((size_t)(y0 + r) * W + x0) * 5 + col] = s_px[i];
+        }
+    }
+}
+
+int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *stream) {
+    if (npix == 0) return 0;
+    hipLaunchKernelGGL(k_filter_guide, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float4 *)rayhit,
+                       npix, (float4 *)guide);
+    return launch_status();
+}
+
+template <int IN, bool LAST>
+static void launch_atrous_m(const FilterPass &a, dim3 grid, hipStream_t s) {
+    if (a.squarings == 5)
+        hipLaunchKernelGGL((k_atrous<IN, LAST, 5>), grid, dim3(kFilterBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_atrous<IN, LAST, -1>), grid, dim3(kFilterBlock), 0, s, a);
+}
+
+int launch_atrous(const FilterPass &a, void *stream) {
+    if (a.width == 0 || a.height == 0) return 0;
+    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
+    hipStream_t s = (hipStream_t)stream;
+    const int in = !a.first ? 0 : (a.src.frame ? 1 : 2);
+    if (a.last) {
+        if (in == 0) launch_atrous_m<0, true>(a, grid, s);
+        else if (in == 1) launch_atrous_m<1, true>(a, grid, s);
+        else launch_atrous_m<2, true>(a, grid, s);
+    } else {
+        if (in == 0) launch_atrous_m<0, false>(a, grid, s);
+        else if (in == 1) launch_atrous_m<1, false>(a, grid, s);
+        else launch_atrous_m<2, false>(a, grid, s);
+    }
+    return launch_status();
+}

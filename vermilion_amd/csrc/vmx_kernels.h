@@ -215,6 +215,30 @@ int launch_bruteforce_long(const SceneDev &sc, const FrameDev &fr, uint32_t flag
 // buffer k_resolve wrote the finished pixels to; out_rgbaz / rgba8: either may be NULL
 int launch_preview(PixelStateDev px, uint32_t npix, uint32_t kmax, const float *finished, float *out_rgbaz, void *rgba8,
                    void *stream);
+// G-buffer-guided a-trous filter (vmx_filter.inc; the arithmetic is stated in include/vermilion_hip.h)
+// where the filter's first iteration reads its colours and its last one the alpha / depth it passes through: a W*H*5
+// RGBAZ frame, or (frame == nullptr) the per-pixel state of a progressive render as k_preview shows it
+struct FilterSrc {
+    const float *frame;
+    PixelStateDev px;
+    const float *finished;  // the buffer k_resolve wrote the finished pixels to
+    uint32_t kmax;
+};
+struct FilterPass {  // one iteration
+    uint32_t width, height;
+    uint32_t step;       // 1 << iteration
+    uint32_t squarings;  // normal_squarings
+    float isc2, kz;      // 1 / sigma_colour_it^2, sigma_depth * step
+    const void *guide;   // float4 (n.xyz, z) per pixel
+    FilterSrc src;
+    const void *in_plane;  // float4 (r, g, b, -) per pixel: the input of every iteration but the first
+    void *out_plane;       // ... and the output of every iteration but the last
+    float *out_rgbaz;      // the last iteration's outputs, either may be NULL
+    void *rgba8;
+    bool first, last;
+};
+int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *stream);
+int launch_atrous(const FilterPass &pass, void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

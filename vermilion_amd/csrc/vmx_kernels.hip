@@ -3793,6 +3793,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 // progressive rendering: the displayable frame of unfinished per-pixel state
 #include "vmx_preview.inc"
 
+// G-buffer-guided a-trous filter of frames and previews
+#include "vmx_filter.inc"
+
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product
 #include "vmx_kernels_ab.inc"

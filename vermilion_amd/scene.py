@@ -102,6 +102,36 @@ def make_opts(seed=1, early_stop=True, sampling=L.VMX_SAMPLING_PARITY, rank=0, w
     return o
 
 
+def make_filter_params(iterations=None, normal_squarings=None, sigma_colour=None, sigma_depth=None):
+    """vmx_filter_params: the library's defaults (vmx_filter_default_params) with the given fields replaced"""
+    p = L.FilterParams()
+    L.check(L.lib().vmx_filter_default_params(C.byref(p)))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if normal_squarings is not None:
+        p.normal_squarings = int(normal_squarings)
+    if sigma_colour is not None:
+        p.sigma_colour = float(sigma_colour)
+    if sigma_depth is not None:
+        p.sigma_depth = float(sigma_depth)
+    return p
+
+
+def _frame_tensor(x, name, dtype, shape, dev):
+    """an output or input of the device filter / previews as the ABI takes it, or a ValueError"""
+    if not _is_tensor(x):
+        raise ValueError(f"{name} must be a torch tensor")
+    if x.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype} (got {x.dtype})")
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {list(shape)} (got {list(x.shape)})")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if x.device != dev:
+        raise ValueError(f"{name} must be on {dev} (got {x.device})")
+    return x
+
+
 def spheres_array(spheres):
     """list of dicts/tuples -> ctypes array of vmx_sphere"""
     arr = (L.Sphere * len(spheres))()
@@ -524,6 +554,102 @@ class Progressive:
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
         self._scene._check(self._lib.vmx_progressive_preview_device(self._h, ptr(rgbaz), ptr(rgba8)))
         return rgbaz, rgba8
+
+    def preview_filtered(self, rgba8=False, params=None):
+        """vmx_progressive_preview_filtered: `preview`'s frame pushed through the G-buffer-guided filter (guide: sample
+        0's camera ray of every pixel, built on the first call), as host arrays like `preview`'s.  params:
+        make_filter_params(...), default the library's."""
+        out = np.empty(self.shape + (5,), np.float32)
+        q = np.empty(self.shape + (4,), np.uint8) if rgba8 else None
+        self._scene._check(self._lib.vmx_progressive_preview_filtered(self._h, out.ctypes.data,
+                                                                      None if q is None else q.ctypes.data,
+                                                                      None if params is None else C.byref(params)))
+        return (out, q) if rgba8 else out
+
+    def preview_filtered_device(self, rgbaz=None, rgba8=None, params=None):
+        """vmx_progressive_preview_filtered_device into torch tensors, checked as `preview_device` checks its own.
+        Enqueued on the handle's stream, nothing synchronised (but the first filtered preview of a handle builds its
+        guide and blocks until that is done); returns (rgbaz, rgba8)."""
+        import torch
+        if rgbaz is None and rgba8 is None:
+            raise ValueError("no output: rgbaz and rgba8 are both None")
+        dev = torch.device("cuda", self.device)
+        if rgbaz is not None:
+            _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if rgba8 is not None:
+            _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        self._scene._check(self._lib.vmx_progressive_preview_filtered_device(self._h, ptr(rgbaz), ptr(rgba8),
+                                                                             None if params is None else C.byref(params)))
+        return rgbaz, rgba8
+
+
+class Filter:
+    """One vmx_filter handle: the G-buffer-guided a-trous filter (include/vermilion_hip.h) for [height, width] frames on
+    `device`.  `set_guide` takes a camera raycast's records, `apply` filters RGBAZ frames with it."""
+
+    def __init__(self, width, height, device=0, lib=None):
+        self._lib = lib if lib is not None else L.lib()
+        self._h = None
+        self.device = int(device)
+        self.shape = (int(height), int(width))
+        h = C.c_void_p()
+        self._check(self._lib.vmx_filter_create(self.device, int(width), int(height), C.byref(h)))
+        self._h = h
+
+    def _check(self, code):
+        if code != L.VMX_OK:
+            raise L.VmxError(code, self._lib.vmx_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._check(self._lib.vmx_filter_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_guide(self, raw, stream=None):
+        """vmx_filter_set_guide_device: `raw` is the ["raw"] tensor of Scene.raycast_camera, or any contiguous float32
+        [height, width, 16] tensor of vmx_rayhit records on the filter's device — anything else is a ValueError.
+        Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        _frame_tensor(raw, "raw", torch.float32, self.shape + (16,), dev)
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_filter_set_guide_device(self._h, C.c_void_p(raw.data_ptr()),
+                                                              C.c_void_p(run.cuda_stream)))
+
+    def apply(self, rgbaz, out=None, rgba8=None, params=None, stream=None):
+        """vmx_filter_apply_device: filters the float32 [height, width, 5] frame `rgbaz` into `out` (same shape; may be
+        `rgbaz` itself) and / or `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is made.  All are
+        contiguous torch tensors on the filter's device: anything else is a ValueError, never a copy through the host.
+        params: make_filter_params(...), default the library's.  Enqueued on `stream` (default
+        torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if out is None and rgba8 is None:
+            out = torch.empty_like(rgbaz)
+        if out is not None:
+            _frame_tensor(out, "out", torch.float32, self.shape + (5,), dev)
+        if rgba8 is not None:
+            _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_filter_apply_device(self._h, ptr(rgbaz), ptr(out), ptr(rgba8),
+                                                          None if params is None else C.byref(params),
+                                                          C.c_void_p(run.cuda_stream)))
+        return out, rgba8
 
 
 class MultiScene:
