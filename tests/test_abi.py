@@ -134,7 +134,7 @@ def test_product_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "vermilion_amd")
     for dp, _, files in os.walk(pkg):
         for f in files:
-            if f.endswith((".py", ".cpp", ".h", ".hip", "Makefile")):
+            if f.endswith((".py", ".cpp", ".h", ".hip", ".inc", "Makefile")):
                 text = open(os.path.join(dp, f), errors="replace").read()
                 assert "oracle_lib" not in text and "vmx_oracle" not in text and "orc_" not in text, f
     syms = subprocess.run(["nm", "-D", L.LIB_PATH], capture_output=True, text=True, check=True).stdout

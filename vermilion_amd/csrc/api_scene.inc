@@ -1,0 +1,302 @@
+// api_scene.inc — part of vmx_api.cpp
+extern "C" {
+
+int vmx_abi_version(void) { return VMX_ABI_VERSION; }
+
+const char *vmx_last_error(void) { return g_err.c_str(); }
+
+int vmx_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+const vmx_sphere *vmx_default_spheres(uint32_t *count) {
+    if (count) *count = 8;
+    return kReferenceSpheres;
+}
+
+int vmx_scene_create(const float *pos, const float *nrm, const float *uv, uint32_t ntris,
+                     const vmx_sphere *spheres, uint32_t nspheres, uint32_t leaf_size, int device,
+                     vmx_scene **out) {
+    return vmx_scene_create_ex(pos, nrm, uv, ntris, spheres, nspheres, leaf_size, VMX_BVH_REFERENCE, device, out);
+}
+
+// the device records of a host-built tree, into `geom` (inner records, then the triangle records) and `attrs`
+static int upload_records(const HostBvh &b, DevBuf<unsigned char> &geom, DevBuf<AttrRecord> &attrs) {
+    const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
+    const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
+    // + 64: the quad-cooperative fetch reads 64 bytes from a 48-byte triangle record's start
+    if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "scene too large for 32-bit record offsets");
+    if (geom.ensure(inner_bytes + tri_bytes + 64) || attrs.ensure(b.attrs.size()))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
+    HIP_TRY(hipMemset(geom.p, 0, inner_bytes + tri_bytes + 64));
+    if (b.inner.size()) HIP_TRY(hipMemcpy(geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(attrs.p, b.attrs.data(), b.attrs.size() * sizeof(AttrRecord), hipMemcpyHostToDevice));
+    return VMX_OK;
+}
+
+// points the kernels' view of the scene (SceneDev) at its records; sizes what follows the tree's depth
+static void bind_records(vmx_scene *sc) {
+    if (sc->device_built) {
+        // records were written on the device (k_lbvh_emit_*): the scene takes the builder's buffers over
+        const LbvhDevice &l = sc->lbvh;
+        sc->dev.inner = l.geom;
+        sc->dev.tris = (const unsigned char *)l.geom + l.tri_off;
+        sc->dev.tri_off = l.tri_off;
+        sc->dev.attrs = l.attrs;
+        sc->dev.root_ref = l.root_ref;
+        sc->dev.stack_entries = l.height + 2;
+        sc->n_inner = l.n_inner;
+    } else {
+        const HostBvh &b = sc->bvh;
+        const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
+        sc->dev.inner = sc->d_geom.p;
+        sc->dev.tris = sc->d_geom.p + inner_bytes;
+        sc->dev.tri_off = (uint32_t)inner_bytes;
+        sc->dev.attrs = sc->d_attrs.p;
+        sc->dev.root_ref = b.root_ref;
+        sc->dev.stack_entries = b.max_depth + 2;
+        sc->n_inner = (uint32_t)b.inner.size();
+    }
+    // LDS budget: shrink the block until one block's stacks fit in 64 KiB
+    sc->block = 256;
+    while (sc->block > 64 && (sc->block / 64) * sc->dev.stack_entries * 512 > 65536) sc->block /= 2;
+}
+
+// device half of scene creation: uploads sc->bvh / sc->spheres to sc->device (used for the first scene
+// and for the replicas of a multi-device scene, which share one host-side build)
+static int scene_upload(vmx_scene *sc) {
+    const int device = sc->device;
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    sc->num_cus = prop.multiProcessorCount;
+    HIP_TRY(hipStreamCreateWithFlags(&sc->stream.s, hipStreamNonBlocking));
+
+    std::vector<SphereDev> sd(sc->spheres.size());
+    for (size_t i = 0; i < sd.size(); ++i) {
+        const vmx_sphere &s = sc->spheres[i];
+        SphereDev &d = sd[i];
+        std::memset(&d, 0, sizeof(d));
+        d.cx = s.centre[0], d.cy = s.centre[1], d.cz = s.centre[2];
+        d.rad = s.radius;
+        d.rad2 = s.radius * s.radius;  // float product (meshEngine.cpp:188)
+        d.colr = s.colour[0], d.colg = s.colour[1], d.colb = s.colour[2];
+        d.ncx = s.normal_centre[0], d.ncy = s.normal_centre[1], d.ncz = s.normal_centre[2];
+        d.nsign = s.normal_sign < 0.f ? -1.f : 1.f;
+        d.flags = s.flags;
+    }
+    if (sc->d_spheres.ensure(std::max<size_t>(sd.size(), 1))) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
+    if (sd.size()) HIP_TRY(hipMemcpy(sc->d_spheres.p, sd.data(), sd.size() * sizeof(SphereDev), hipMemcpyHostToDevice));
+    sc->dev.spheres = sc->d_spheres.p;
+    sc->dev.nspheres = (uint32_t)sd.size();
+    sc->dev.emit_prefix = 0;
+    for (size_t i = 0; i < sd.size(); ++i)
+        if (sd[i].flags & 1u) sc->dev.emit_prefix = (uint32_t)i + 1;
+    sc->dev.ntris = sc->ntris;
+    if (!sc->device_built)
+        if (int rc = upload_records(sc->bvh, sc->d_geom, sc->d_attrs)) return rc;
+    bind_records(sc);
+    return VMX_OK;
+}
+
+// vertex bounds (origin cells of the bounce reordering), at creation and after every update that moves vertices
+static void vertex_bounds(vmx_scene *sc, const float *pos) {
+    for (int a = 0; a < 3; ++a) sc->bounds_lo[a] = sc->bounds_hi[a] = pos[a];
+    for (size_t v = 0; v < (size_t)sc->ntris * 3; ++v)
+        for (int a = 0; a < 3; ++a) {
+            sc->bounds_lo[a] = std::min(sc->bounds_lo[a], pos[v * 3 + a]);
+            sc->bounds_hi[a] = std::max(sc->bounds_hi[a], pos[v * 3 + a]);
+        }
+    sc->upd.bounds_stale = false;
+}
+
+// a builder's error: the device builders report HIP failures as "LBVH builder: <call>: <hipGetErrorString>"
+static int build_error(const std::string &err) {
+    int code = VMX_ERR_INVALID;
+    if (err.find("deeper") != std::string::npos) code = VMX_ERR_DEPTH;
+    else if (err.rfind("LBVH builder: hip", 0) == 0)
+        code = (err.find("hipMalloc") != std::string::npos || err.find("out of memory") != std::string::npos) ? VMX_ERR_NOMEM : VMX_ERR_HIP;
+    return fail(code, err);
+}
+
+int vmx_scene_create_ex(const float *pos, const float *nrm, const float *uv, uint32_t ntris,
+                        const vmx_sphere *spheres, uint32_t nspheres, uint32_t leaf_size, uint32_t builder,
+                        int device, vmx_scene **out) {
+    if (!out) return fail(VMX_ERR_INVALID, "out is NULL");
+    if (builder > VMX_BVH_PLOC) return fail(VMX_ERR_INVALID, "unknown BVH builder");
+    *out = nullptr;
+    if (!pos || !nrm || ntris == 0) return fail(VMX_ERR_INVALID, "scene needs positions, normals, ntris > 0");
+    if (spheres == nullptr && nspheres != 0)
+        return fail(VMX_ERR_INVALID, "spheres is NULL but nspheres > 0 (NULL,0 selects the reference table)");
+    if (nspheres > kMaxSpheres) return fail(VMX_ERR_INVALID, "more than 16 spheres");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
+
+    vmx_scene *sc = new vmx_scene();
+    sc->device = device;
+    sc->ntris = ntris;
+    sc->leaf_size = leaf_size ? leaf_size : 4;
+    sc->builder = builder;
+    std::string err;
+    bool built;
+    if (builder == VMX_BVH_LBVH || builder == VMX_BVH_PLOC) {
+        sc->device_built = true, sc->flat_ready.store(false), sc->flat_topology = false;
+        built = builder == VMX_BVH_PLOC ? build_bvh_ploc_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err)
+                                        : build_bvh_lbvh_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err);
+    } else {
+        built = builder == VMX_BVH_SAH ? build_bvh_sah(pos, nrm, uv, ntris, sc->leaf_size, sc->bvh, err)
+                                       : build_bvh(pos, nrm, uv, ntris, sc->leaf_size, sc->bvh, err);
+    }
+    if (!built) {
+        delete sc;
+        return build_error(err);
+    }
+    if (spheres)
+        sc->spheres.assign(spheres, spheres + nspheres);
+    else
+        sc->spheres.assign(kReferenceSpheres, kReferenceSpheres + 8);
+    vertex_bounds(sc, pos);
+    const int rc = scene_upload(sc);
+    if (rc) {
+        const std::string keep = g_err;
+        vmx_scene_destroy(sc);
+        return fail(rc, keep);
+    }
+    *out = sc;
+    return VMX_OK;
+}
+
+int vmx_scene_destroy(vmx_scene *sc) {
+    if (!sc) return VMX_OK;
+    {
+        std::lock_guard<std::mutex> lock(sc->mu);
+        if (sc->progressive_open)
+            return fail(VMX_ERR_INVALID, "scene has " + std::to_string(sc->progressive_open) +
+                                             " open vmx_progressive handle(s): vmx_progressive_end them first");
+    }
+    (void)hipSetDevice(sc->device);
+    delete sc;
+    return VMX_OK;
+}
+
+int vmx_scene_bind_texture(vmx_scene *sc, const float *data, uint32_t width, uint32_t height, uint32_t channels) {
+    if (!sc || !data) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (width == 0 || height == 0 || channels == 0 || channels > 4 || width > 65535 || height > 65535)
+        return fail(VMX_ERR_INVALID, "texture must be 1..65535 texels wide/high with 1..4 channels");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    // only boundTextures[0] is sampled by PathTracer (pathtracer.cpp:65); boundTextures[1] is BruteForceTracer's albedo
+    // (integrators.cpp:141-147); further ones are counted and not kept
+    if (sc->n_textures < 2) {
+        const bool first = sc->n_textures == 0;
+        DevBuf<float> &tex = first ? sc->d_tex : sc->d_tex1;
+        const size_t n = (size_t)width * height * channels;
+        if (tex.ensure(n)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the texture");
+        HIP_TRY(hipMemcpy(tex.p, data, n * 4, hipMemcpyHostToDevice));
+        if (first) sc->dev.tex = tex.p, sc->dev.tex_w = width, sc->dev.tex_h = height, sc->dev.tex_c = channels;
+        else sc->dev.tex1 = tex.p, sc->dev.tex1_w = width, sc->dev.tex1_h = height, sc->dev.tex1_c = channels;
+    }
+    sc->n_textures++;
+    return VMX_OK;
+}
+
+// A refitted tree's boxes in the flat layout: one depth-first walk from root_ref over the downloaded records, left child
+// first — the export order of both kinds of builder (pre-order, left child = i + 1).  A node's box is its half of the
+// parent's record; the root's is the refit's root_box.  Topology and prim_order are the builder's and stay.
+static int export_refit_boxes(vmx_scene *sc) {
+    HostBvh &b = sc->bvh;
+    const size_t n_nodes = b.start.size();
+    std::vector<InnerRecord> rec(sc->n_inner);
+    if (sc->n_inner) HIP_TRY(hipMemcpy(rec.data(), sc->dev.inner, rec.size() * sizeof(InnerRecord), hipMemcpyDeviceToHost));
+    float root[6];
+    HIP_TRY(hipMemcpy(root, sc->upd.root_box.p, sizeof(root), hipMemcpyDeviceToHost));
+    struct Item {
+        uint32_t ref;
+        const float *box;  // six floats: min, max
+    };
+    std::vector<Item> work{{sc->dev.root_ref, root}};
+    size_t i = 0;
+    while (!work.empty()) {
+        const Item it = work.back();
+        work.pop_back();
+        const bool leaf = (it.ref & kLeafBit) != 0;
+        if (i >= n_nodes || leaf != (b.right_offset[i] == 0) || (!leaf && it.ref >= rec.size()))
+            return fail(VMX_ERR_HIP, "flat export: the device records do not match the tree's topology");
+        std::memcpy(&b.bbox[i * 6], it.box, 24);
+        ++i;
+        if (leaf) continue;
+        const InnerRecord &r = rec[it.ref];
+        work.push_back({r.right, r.rmin});  // rmin, rmax: six consecutive floats
+        work.push_back({r.left, r.lmin});
+    }
+    if (i != n_nodes) return fail(VMX_ERR_HIP, "flat export: the device records do not match the tree's topology");
+    return VMX_OK;
+}
+
+// device-built trees: the reference's flat layout is produced on the first request for it; after a REFIT the boxes are
+// read back from the records
+static int ensure_flat(const vmx_scene *csc) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (sc->flat_ready.load(std::memory_order_acquire)) return VMX_OK;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (sc->flat_ready.load(std::memory_order_relaxed)) return VMX_OK;
+    if (int rc = bind_device(sc)) return rc;
+    if (int rc = sc->upd.done.sync()) return rc;
+    std::string err;
+    if (!sc->flat_topology) {
+        if (!lbvh_export_flat(sc->lbvh, sc->device, sc->bvh, err)) return fail(VMX_ERR_HIP, err);
+        sc->flat_topology = true;
+    }
+    if (sc->upd.refitted)
+        if (int rc = export_refit_boxes(sc)) return rc;
+    sc->flat_ready.store(true, std::memory_order_release);
+    return VMX_OK;
+}
+
+int vmx_scene_describe(const vmx_scene *sc, vmx_scene_desc *out) {
+    if (!sc || !out) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = ensure_flat(sc)) return rc;
+    std::memset(out, 0, sizeof(*out));
+    out->ntris = sc->ntris;
+    out->nspheres = (uint32_t)sc->spheres.size();
+    out->leaf_size = sc->leaf_size;
+    out->n_nodes = (uint32_t)sc->bvh.start.size();
+    out->n_leaves = sc->bvh.n_leaves;
+    out->n_inner = sc->n_inner;
+    out->max_depth = sc->bvh.max_depth;
+    out->stack_entries = sc->dev.stack_entries;
+    out->device_bytes = (size_t)sc->n_inner * sizeof(InnerRecord) + (size_t)sc->ntris * sizeof(TriRecord) +
+                        (size_t)sc->ntris * sizeof(AttrRecord) + sc->spheres.size() * sizeof(SphereDev) +
+                        (sc->device_built ? sc->lbvh.arena_bytes : 0);  // device-built trees keep their hierarchy arrays
+    out->device = sc->device;
+    return VMX_OK;
+}
+
+int vmx_scene_timings(const vmx_scene *sc, vmx_timings *out) {
+    if (!sc || !out) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(const_cast<vmx_scene *>(sc)->mu);  // a render on another thread rewrites them
+    *out = sc->timings;
+    return VMX_OK;
+}
+
+int vmx_scene_bvh(const vmx_scene *sc, uint32_t *start, uint32_t *nprims, uint32_t *right_offset, float *bbox,
+                  uint32_t *prim_order) {
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    if (int rc = ensure_flat(sc)) return rc;
+    const HostBvh &b = sc->bvh;
+    const size_t n = b.start.size();
+    if (start) std::memcpy(start, b.start.data(), n * 4);
+    if (nprims) std::memcpy(nprims, b.nprims.data(), n * 4);
+    if (right_offset) std::memcpy(right_offset, b.right_offset.data(), n * 4);
+    if (bbox) std::memcpy(bbox, b.bbox.data(), n * 24);
+    if (prim_order) std::memcpy(prim_order, b.prim_order.data(), b.prim_order.size() * 4);
+    return VMX_OK;
+}
+
+} /* extern "C" */

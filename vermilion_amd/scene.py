@@ -97,7 +97,7 @@ def make_opts(seed=1, early_stop=True, sampling=L.VMX_SAMPLING_PARITY, rank=0, w
     o.reserved[2] = int(tail_threshold)
     o.reserved[3] = int(refill_min)    # k_paths: refill when this many lanes idle (0 -> 16)
     o.reserved[4] = int(shade_min)     # k_paths: shade when this many lanes finished (0 -> 16)
-    o.reserved[5] = int(reorder)       # bounce reordering key (vmx_api.cpp: Tuning::sort_mode); 0 = the library's default
+    o.reserved[5] = int(reorder)       # bounce reordering key (vmx_host.h: Tuning::sort_mode); 0 = the library's default
     o.reserved[6] = int(lds_entries)   # stack levels kept in LDS, all kernels (0 -> 8 camera / 13 bounce / 10 fused); deeper ones spill to HBM
     return o
 
