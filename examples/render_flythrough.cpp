@@ -1,0 +1,168 @@
+// render_flythrough.cpp — N frames of a few samples along a camera path, each pushed through the preview chain on the
+// device, through the C ABI only (include/vermilion_hip.h):
+//   vmx_render_device            the frame at 4 spp (by default), a new seed per frame
+//   vmx_raycast_camera_device    its G-buffer: sample 0's camera ray of every pixel
+//   vmx_temporal_accumulate_device  the frames so far, reprojected into this camera, blended with the new one
+//   vmx_filter_set_guide_device + vmx_filter_apply_device  the a-trous filter on the accumulated frame -> rgba8
+// Everything stays on one stream and in device memory; only the rgba8 form of the frames that are written comes back.
+// The library has no allocator of its own: a host application brings its device buffers.  This one takes the few HIP
+// runtime calls it needs from the runtime the library has loaded, so that it builds like the other examples; that
+// leans on the library's own link to the runtime.  A real application includes <hip/hip_runtime_api.h> and links
+// the HIP runtime itself.
+//
+//   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
+//       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
+//   ./examples/render_flythrough fly 256 256 [frames [spp [seed]]]
+//
+// Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
+// and prints the mean history length of each frame.
+#include <dlfcn.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "vermilion_hip.h"
+
+namespace {
+
+// the 8-triangle Cornell-like set of vermilion_amd/scenes.py: floor, back wall, block front + top
+void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &uv, const float a[3], const float b[3],
+          const float c[3], const float d[3], const float n[3]) {
+    const float *tri[2][3] = {{a, b, c}, {a, c, d}};
+    const float tuv[2][6] = {{0, 0, 1, 0, 1, 1}, {0, 0, 1, 1, 0, 1}};
+    for (int t = 0; t < 2; ++t) {
+        for (int v = 0; v < 3; ++v) {
+            pos.insert(pos.end(), tri[t][v], tri[t][v] + 3);
+            nrm.insert(nrm.end(), n, n + 3);
+        }
+        uv.insert(uv.end(), tuv[t], tuv[t] + 6);
+    }
+}
+
+// the HIP runtime's entries, as hip_runtime_api.h declares them (hipError_t is an int-sized enum, 0 = hipSuccess;
+// hipMemcpyDeviceToHost = 2)
+struct Hip {
+    int (*malloc_)(void **, size_t) = nullptr;
+    int (*free_)(void *) = nullptr;
+    int (*memcpy_)(void *, const void *, size_t, int) = nullptr;
+    int (*stream_create)(void **) = nullptr;
+    int (*stream_sync)(void *) = nullptr;
+    int (*stream_destroy)(void *) = nullptr;
+    bool load() {
+        malloc_ = (int (*)(void **, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
+        free_ = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipFree");
+        memcpy_ = (int (*)(void *, const void *, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
+        stream_create = (int (*)(void **))dlsym(RTLD_DEFAULT, "hipStreamCreate");
+        stream_sync = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipStreamSynchronize");
+        stream_destroy = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipStreamDestroy");
+        return malloc_ && free_ && memcpy_ && stream_create && stream_sync && stream_destroy;
+    }
+};
+
+bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, uint32_t W, uint32_t H) {
+    FILE *f = std::fopen(name.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "P6\n%u %u\n255\n", W, H);
+    for (size_t p = 0; p < (size_t)W * H; ++p) std::fwrite(&rgba[p * 4], 1, 3, f);
+    std::fclose(f);
+    return true;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    const std::string out = argc > 1 ? argv[1] : "fly";
+    const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
+    const uint32_t frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 8;
+    const uint32_t spp = argc > 5 ? (uint32_t)std::atoi(argv[5]) : 4;
+    const uint64_t seed = argc > 6 ? std::strtoull(argv[6], nullptr, 10) : 1;
+
+    std::vector<float> pos, nrm, uv;
+    const float up[3] = {0, 1, 0}, front[3] = {0, 0, 1};
+    const float f0[3] = {-600, 1, 600}, f1[3] = {600, 1, 600}, f2[3] = {600, 1, -800}, f3[3] = {-600, 1, -800};
+    quad(pos, nrm, uv, f0, f1, f2, f3, up);
+    const float b0[3] = {-600, 1, -800}, b1[3] = {600, 1, -800}, b2[3] = {600, 900, -800}, b3[3] = {-600, 900, -800};
+    quad(pos, nrm, uv, b0, b1, b2, b3, front);
+    const float k0[3] = {-250, 1, 0}, k1[3] = {150, 1, 0}, k2[3] = {150, 400, 0}, k3[3] = {-250, 400, 0};
+    quad(pos, nrm, uv, k0, k1, k2, k3, front);
+    const float t0[3] = {-250, 400, 0}, t1[3] = {150, 400, 0}, t2[3] = {150, 400, -400}, t3[3] = {-250, 400, -400};
+    quad(pos, nrm, uv, t0, t1, t2, t3, up);
+
+    vmx_scene *scene = nullptr;
+    if (vmx_scene_create(pos.data(), nrm.data(), uv.data(), (uint32_t)(pos.size() / 9), nullptr, 0, 4, 0, &scene) != VMX_OK) {
+        std::fprintf(stderr, "scene: %s\n", vmx_last_error());
+        return 1;
+    }
+    Hip hip;
+    if (!hip.load()) {
+        std::fprintf(stderr, "the HIP runtime's entries were not found\n");
+        vmx_scene_destroy(scene);
+        return 1;
+    }
+    const size_t npix = (size_t)W * H;
+    vmx_temporal *temporal = nullptr;
+    vmx_filter *filter = nullptr;
+    void *stream = nullptr, *d_frame = nullptr, *d_rec = nullptr, *d_acc = nullptr, *d_rgba8 = nullptr, *d_hist = nullptr;
+    std::vector<unsigned char> rgba(npix * 4);
+    std::vector<float> hist(npix);
+    int rc = VMX_OK;
+    bool io_ok = true;
+    bool hip_ok = hip.stream_create(&stream) == 0 && hip.malloc_(&d_frame, npix * 20) == 0 && hip.malloc_(&d_rec, npix * 64) == 0 &&
+                  hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, npix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
+    if (hip_ok) rc = vmx_temporal_create(0, W, H, &temporal);
+    if (hip_ok && rc == VMX_OK) rc = vmx_filter_create(0, W, H, &filter);
+    // rgba8 of a device frame (vmx_quantize_device), or of d_rgba8 as it stands, on the host
+    auto fetch = [&](const void *d_rgbaz) {
+        if (d_rgbaz && (rc = vmx_quantize_device(d_rgbaz, npix, d_rgba8, nullptr, 0, stream)) != VMX_OK) return false;
+        return (hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(rgba.data(), d_rgba8, npix * 4, 2) == 0);
+    };
+    for (uint32_t i = 0; hip_ok && rc == VMX_OK && i < frames; ++i) {
+        vmx_camera cam;
+        std::memset(&cam, 0, sizeof(cam));
+        cam.position[0] = 6.0f * (float)i, cam.position[1] = 420, cam.position[2] = 1900;  // a slow pan to the right ...
+        cam.rotation_deg[1] = 0.15f * (float)i;                                             // ... while turning
+        cam.back_distance = 6.0f;  // renderEngine.cpp:135
+        cam.back_size[0] = 3.6f, cam.back_size[1] = 3.6f * (float)H / (float)W;
+        cam.image_res[0] = W, cam.image_res[1] = H;
+        cam.rays_per_pixel = spp;
+        vmx_opts opts;
+        std::memset(&opts, 0, sizeof(opts));
+        opts.seed = seed + i;
+        opts.sampling = VMX_SAMPLING_CORRECTED;
+        vmx_stats st;
+        if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
+        if ((rc = vmx_raycast_camera_device(scene, &cam, &opts, 0, d_rec, 0, stream)) != VMX_OK) break;
+        if ((rc = vmx_temporal_accumulate_device(temporal, &cam, d_rec, d_frame, d_acc, nullptr, d_hist, nullptr, stream)) != VMX_OK)
+            break;
+        if ((rc = vmx_filter_set_guide_device(filter, d_rec, stream)) != VMX_OK) break;
+        if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+        if (!(hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(hist.data(), d_hist, npix * 4, 2) == 0)) break;
+        double mean = 0;
+        for (float n : hist) mean += n;
+        std::printf("frame %u: camera x %.0f, y-rotation %.2f deg, %.2f ms device, mean history %.2f frames\n", i,
+                    cam.position[0], cam.rotation_deg[1], st.ms_device, mean / (double)npix);
+        if (i + 1 == frames) {
+            const std::pair<const char *, const void *> files[3] = {{"_out.ppm", nullptr}, {"_acc.ppm", d_acc}, {"_raw.ppm", d_frame}};
+            for (const auto &f : files)
+                if (fetch(f.second) && !write_ppm(out + f.first, rgba, W, H)) {
+                    std::fprintf(stderr, "flythrough: cannot write %s%s\n", out.c_str(), f.first);
+                    io_ok = false;
+                }
+        }
+    }
+    if (rc != VMX_OK) std::fprintf(stderr, "flythrough: %s\n", vmx_last_error());
+    if (!hip_ok) std::fprintf(stderr, "flythrough: a HIP runtime call failed\n");
+    if (stream) hip.stream_sync(stream);
+    if (filter) vmx_filter_destroy(filter);
+    if (temporal) vmx_temporal_destroy(temporal);
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist})
+        if (p) hip.free_(p);
+    if (stream) hip.stream_destroy(stream);
+    vmx_scene_destroy(scene);
+    return rc != VMX_OK || !hip_ok ? 1 : io_ok ? 0 : 2;
+}

@@ -508,6 +508,71 @@ int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, v
 int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8,
                                      const vmx_filter_params *params);
 
+/* ---- temporal accumulation: frames over time, across camera moves -------------------------------------
+ * A few-sample frame per camera position flickers, although nearly every surface it shows was sampled a frame
+ * earlier.  A vmx_temporal handle keeps an accumulated frame and reprojects it into each new camera through that
+ * frame's G-buffer (vmx_rayhit records, what vmx_raycast_camera_device(scene, cam, opts, 0, ...) writes), rejects stale
+ * history by normal and plane distance, and blends the new frame in.  Per pixel the handle owns the accumulated colour
+ * c_h and history length n_h, the previous guide (n, z: the filter's rule, z = -1 and n = 0 where the ray missed), the
+ * previous hit location X and the previous call's camera; double-buffered, 2 x 48 B per pixel.
+ *
+ * Everything is float, one rounding per written operation, left to right; `/` is correctly rounded, denormals are kept.
+ * proj(X, cam), with m = the camera's 3x3 matrix (m[col*3 + row]), pos, d = back_distance, (sx, sy) = back_size:
+ *   v = X - pos;  c_k = (m[3k]*v.x + m[3k+1]*v.y) + m[3k+2]*v.z, k = 0, 1, 2;  t = d / (-c_2)
+ *   u = ((c_0*t)/sx + 0.5f) * (float)W;  w = ((-(c_1*t))/sy + 0.5f) * (float)H;  front = c_2 < 0
+ * (the transpose of the matrix a camera ray is made with: its inverse up to rounding).
+ * Per pixel p = (x, y) with its record's hit = flags bit 0, n_p = normal, z_p = distance, X = location, and c = the
+ * input frame's r, g, b:
+ *   the first call after create or reset, or !hit:  out = c, n' = 1.f.  Otherwise
+ *   (u_c, w_c, -) = proj(X, this call's cam);  (u_h, w_h, front) = proj(X, the previous call's cam)
+ *   gx = (float)x + (u_h - u_c);  gy = (float)y + (w_h - w_c)      (a camera that did not move: exactly x, y)
+ *   inrange = front && gx >= -1.f && gx < (float)W && gy >= -1.f && gy < (float)H      (false for NaN)
+ *   x0 = floorf(gx), fx = gx - x0;  y0 = floorf(gy), fy = gy - y0
+ *   four taps, dy = 0, 1 (outer), dx = 0, 1 (inner):  q = (x0 + dx, y0 + dy);  wx = dx ? fx : 1.f - fx, wy likewise,
+ *   wt = wx*wy.  A tap counts iff inrange, q is inside the image, z_q >= 0,
+ *     (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z >= normal_min,
+ *     pd*pd <= (plane_tol*plane_tol) * (z_p*z_p) with e = X - X_q, pd = (n_p.x*e.x + n_p.y*e.y) + n_p.z*e.z,
+ *     and wt > 0; then  sum_c. = sum_c. + wt*c_h(q).;  sum_n = sum_n + wt*n_h(q);  sum_w = sum_w + wt   (from 0)
+ *   sum_w > 0:  h. = sum_c./sum_w;  nh = sum_n/sum_w;  t = nh + 1.f;  n' = t < max_history ? t : max_history;
+ *               a = 1.f/n';  out. = h. + (c. - h.)*a            else:  out = c, n' = 1.f
+ * New state: c_h = out, n_h = n', guide, X (the record's location as it stands) and camera of this call.
+ * Outputs: d_out_rgbaz = out in r, g, b, alpha and depth the input's bits; d_rgba8 = vmx_quantize_device's arithmetic
+ * on that pixel; d_history_len[p] = n'.
+ * Limits: the world is taken as static between the two frames — after vmx_scene_update a moved surface fails the
+ * plane test and restarts at n' = 1; there are no motion vectors for refitted geometry.  A NaN colour passes into the
+ * history and stays until that pixel is invalidated or the handle is reset.
+ * The kernel holds to this restatement bit for bit (tests/temporal_spec.py).
+ */
+typedef struct vmx_temporal_params {
+    float normal_min;     /* finite, -1..1; default 0.9f                     */
+    float plane_tol;      /* finite, > 0;   default 0.01f                    */
+    float max_history;    /* finite, >= 1;  default 32.f                     */
+    uint32_t reserved[5]; /* must be 0                                       */
+} vmx_temporal_params;
+
+typedef struct vmx_temporal vmx_temporal;
+
+int vmx_temporal_default_params(vmx_temporal_params *out);
+/* An accumulator for width x height frames on `device`, checked and refused as vmx_filter_create does.  It owns its
+ * two state buffers (48 B per pixel each); nothing is allocated after creation. */
+int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_temporal **out);
+int vmx_temporal_destroy(vmx_temporal *t);
+/* Forgets the history: the next call is a first call.  A first call reads none of the state, so nothing is enqueued
+ * (`stream` is not used); like the calls themselves, resets take effect in the order they are made. */
+int vmx_temporal_reset(vmx_temporal *t, void *stream);
+int vmx_temporal_frames(const vmx_temporal *t, uint64_t *frames_since_reset);
+/* One frame: d_rayhit = W*H vmx_rayhit records in pixel order, 16-byte aligned (that frame's G-buffer); d_in_rgbaz the
+ * W*H*5-float frame; d_out_rgbaz (same layout) and / or d_rgba8 (W*H*4 bytes), at least one non-NULL; d_history_len
+ * W*H floats or NULL.  cam is checked as vmx_raycast_camera_device checks its camera and its image_res must be the
+ * handle's size; the call reads its matrix, position, back_distance and back_size only.  params == NULL selects the
+ * defaults; a field out of range or a non-zero reserved word is VMX_ERR_INVALID before any launch.  d_out_rgbaz ==
+ * d_in_rgbaz (in place) is allowed; any other overlap with a buffer the call writes is VMX_ERR_INVALID.  Pointers follow
+ * vmx_filter_apply_device's rules (DEVICE memory of the handle's device, 4-byte aligned).  Enqueued on `stream`, no
+ * synchronisation; calls on one handle from different streams are ordered by enqueue. */
+int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit,
+                                   const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                                   const vmx_temporal_params *params, void *stream);
+
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers
  * back to back, each padded to `rank_stride_floats`; writes the W*H*5 frame.

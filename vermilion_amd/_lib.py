@@ -189,6 +189,19 @@ class FilterParams(C.Structure):
                 "sigma_colour": self.sigma_colour, "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [
+        ("normal_min", C.c_float),
+        ("plane_tol", C.c_float),
+        ("max_history", C.c_float),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+    def as_dict(self):
+        return {"normal_min": self.normal_min, "plane_tol": self.plane_tol, "max_history": self.max_history,
+                "reserved": list(self.reserved)}
+
+
 # every symbol include/vermilion_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -232,6 +245,13 @@ SYMBOLS = {
     "vmx_filter_apply_device": (C.c_int, [_P, _P, _P, _P, C.POINTER(FilterParams), _P]),
     "vmx_progressive_preview_filtered_device": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
     "vmx_progressive_preview_filtered": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
+    "vmx_temporal_default_params": (C.c_int, [C.POINTER(TemporalParams)]),
+    "vmx_temporal_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "vmx_temporal_destroy": (C.c_int, [_P]),
+    "vmx_temporal_reset": (C.c_int, [_P, _P]),
+    "vmx_temporal_frames": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "vmx_temporal_accumulate_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, C.POINTER(TemporalParams),
+                                                 _P]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

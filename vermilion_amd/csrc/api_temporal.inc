@@ -1,0 +1,148 @@
+// api_temporal.inc — part of vmx_api.cpp
+extern "C" {
+
+// ---- temporal accumulation (k_temporal: vmx_temporal.inc) ---------------------------------------------------------------
+struct VMX_OPAQUE vmx_temporal {
+    int device = 0;
+    uint32_t width = 0, height = 0;
+    DevBuf<unsigned char> state[2];  // three float4 planes per buffer: (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -)
+    int cur = 0;                     // the buffer the last call wrote
+    bool has_history = false;        // false after create and reset: the next call is a first call
+    TemporalCam hist_cam{};          // the last call's camera
+    uint64_t frames = 0;             // calls since create or reset
+    Fence done;  // recorded after each call's kernel, waited on by the next: a call reads the state the previous one wrote
+    mutable std::mutex mu;
+};
+
+static const vmx_temporal_params kTemporalDefaults = {0.9f, 0.01f, 32.f, {0u, 0u, 0u, 0u, 0u}};
+
+// NULL selects the defaults; anything out of range is refused before any launch
+static int temporal_params(const vmx_temporal_params *in, vmx_temporal_params &out) {
+    out = in ? *in : kTemporalDefaults;
+    if (!(std::isfinite(out.normal_min) && out.normal_min >= -1.f && out.normal_min <= 1.f))
+        return fail(VMX_ERR_INVALID, "vmx_temporal_params: normal_min must be finite and -1..1");
+    if (!(std::isfinite(out.plane_tol) && out.plane_tol > 0.f))
+        return fail(VMX_ERR_INVALID, "vmx_temporal_params: plane_tol must be finite and > 0");
+    if (!(std::isfinite(out.max_history) && out.max_history >= 1.f))
+        return fail(VMX_ERR_INVALID, "vmx_temporal_params: max_history must be finite and >= 1");
+    for (uint32_t r : out.reserved)
+        if (r) return fail(VMX_ERR_INVALID, "vmx_temporal_params: reserved words must be 0");
+    return VMX_OK;
+}
+
+int vmx_temporal_default_params(vmx_temporal_params *out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    *out = kTemporalDefaults;
+    return VMX_OK;
+}
+
+int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_temporal **out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(VMX_ERR_INVALID, "image resolution must be non-zero");
+    if ((uint64_t)width * height > 0x7fffffffull / 8) return fail(VMX_ERR_INVALID, "image too large");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<vmx_temporal> t(new (std::nothrow) vmx_temporal);
+    if (!t) return fail(VMX_ERR_NOMEM, "out of host memory");
+    t->device = device, t->width = width, t->height = height;
+    const size_t npix = (size_t)width * height;
+    if (t->state[0].ensure(npix * 48) || t->state[1].ensure(npix * 48))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the temporal state");
+    *out = t.release();
+    return VMX_OK;
+}
+
+int vmx_temporal_destroy(vmx_temporal *t) {
+    if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
+    (void)hipSetDevice(t->device);
+    (void)t->done.sync();  // the last call may still use the state
+    delete t;
+    return VMX_OK;
+}
+
+int vmx_temporal_reset(vmx_temporal *t, void *stream) {
+    (void)stream;  // a first call reads none of the state: there is nothing to enqueue
+    if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
+    std::lock_guard<std::mutex> lock(t->mu);
+    t->has_history = false;
+    t->frames = 0;
+    return VMX_OK;
+}
+
+int vmx_temporal_frames(const vmx_temporal *t, uint64_t *frames_since_reset) {
+    if (!frames_since_reset) return fail(VMX_ERR_INVALID, "NULL frames_since_reset");
+    if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
+    std::lock_guard<std::mutex> lock(t->mu);
+    *frames_since_reset = t->frames;
+    return VMX_OK;
+}
+
+int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_in_rgbaz,
+                                   void *d_out_rgbaz, void *d_rgba8, void *d_history_len, const vmx_temporal_params *params,
+                                   void *stream) {
+    // checks that need no device, in the filter's order so that each can be seen alone; the handle comes last
+    vmx_temporal_params prm;
+    if (int rc = temporal_params(params, prm)) return rc;
+    if (!cam) return fail(VMX_ERR_INVALID, "NULL camera");
+    if (!d_rayhit) return fail(VMX_ERR_INVALID, "NULL d_rayhit");
+    if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
+    if (!d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
+    if ((uintptr_t)d_rayhit & 15u) return fail(VMX_ERR_INVALID, "d_rayhit must be 16-byte aligned");
+    if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8 | (uintptr_t)d_history_len) & 3u)
+        return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len must be 4-byte aligned");
+    FrameDev fr;
+    {
+        const vmx_opts none{};  // (make_frame reads a camera's opts too: the defaults of a zeroed struct)
+        if (int rc = make_frame(*cam, none, fr)) return rc;
+    }
+    if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
+    std::lock_guard<std::mutex> lock(t->mu);
+    if (fr.width != t->width || fr.height != t->height)
+        return fail(VMX_ERR_INVALID, "cam->image_res is " + std::to_string(fr.width) + " x " + std::to_string(fr.height) +
+                                         ", the handle's frames are " + std::to_string(t->width) + " x " + std::to_string(t->height));
+    {
+        // in place (d_out_rgbaz == d_in_rgbaz) is the one overlap a buffer the call writes may have
+        const uintptr_t npix = (uintptr_t)t->width * t->height;
+        const uintptr_t lo[5] = {(uintptr_t)d_rayhit, (uintptr_t)d_in_rgbaz, (uintptr_t)d_out_rgbaz, (uintptr_t)d_rgba8,
+                                 (uintptr_t)d_history_len};
+        const uintptr_t len[5] = {npix * 64, npix * 20, npix * 20, npix * 4, npix * 4};
+        for (int i = 0; i < 5; ++i)
+            for (int j = std::max(i + 1, 2); j < 5; ++j) {  // (j: the written ones)
+                if (!lo[i] || !lo[j] || (i == 1 && j == 2 && lo[1] == lo[2])) continue;
+                if (lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i])
+                    return fail(VMX_ERR_INVALID, "d_rayhit, d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len overlap (only d_out_rgbaz == d_in_rgbaz may)");
+            }
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    if (int rc = check_device_ptrs(t->device, {{d_rayhit, "d_rayhit"}, {d_in_rgbaz, "d_in_rgbaz"}, {d_out_rgbaz, "d_out_rgbaz"},
+                                               {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}}))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = t->done.wait(s)) return rc;  // after the previous call on this handle
+    TemporalPass a{};
+    a.width = t->width, a.height = t->height;
+    std::memcpy(a.cam.m, fr.m, sizeof(a.cam.m));
+    a.cam.px = fr.px, a.cam.py = fr.py, a.cam.pz = fr.pz;
+    a.cam.film_dist = fr.film_dist, a.cam.sensor_x = fr.sensor_x, a.cam.sensor_y = fr.sensor_y;
+    a.hist_cam = t->hist_cam;
+    a.normal_min = prm.normal_min, a.tol2 = prm.plane_tol * prm.plane_tol, a.max_history = prm.max_history;
+    a.rayhit = d_rayhit, a.in_rgbaz = (const float *)d_in_rgbaz;
+    a.old_state = t->state[t->cur].p, a.new_state = t->state[t->cur ^ 1].p;
+    a.out_rgbaz = (float *)d_out_rgbaz, a.rgba8 = d_rgba8, a.history_len = (float *)d_history_len;
+    a.first = !t->has_history;
+    LAUNCH_TRY(launch_temporal(a, s));
+    if (int rc = t->done.record(s)) {
+        // the next call could not be ordered after this kernel: wait for it here and leave the history as it was (the
+        // kernel wrote the other buffer only)
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    t->cur ^= 1, t->has_history = true, t->hist_cam = a.cam, t->frames += 1;
+    return VMX_OK;
+}
+
+} /* extern "C" */

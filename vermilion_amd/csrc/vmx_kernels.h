@@ -239,6 +239,26 @@ struct FilterPass {  // one iteration
 };
 int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *stream);
 int launch_atrous(const FilterPass &pass, void *stream);
+// temporal accumulation (vmx_temporal.inc; the arithmetic is stated in include/vermilion_hip.h)
+struct TemporalCam {  // what proj reads of a FrameDev
+    float m[9];       // m[col * 3 + row]
+    float px, py, pz;
+    float film_dist, sensor_x, sensor_y;
+};
+struct TemporalPass {  // one call
+    uint32_t width, height;
+    TemporalCam cam, hist_cam;  // this call's camera, the previous call's (not read by a first call)
+    float normal_min, tol2, max_history;  // tol2 = plane_tol * plane_tol
+    const void *rayhit;    // vmx_rayhit per pixel
+    const float *in_rgbaz;
+    const void *old_state;  // three float4 planes of W*H: (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -); not read by a first call
+    void *new_state;
+    float *out_rgbaz;      // outputs, any may be NULL
+    void *rgba8;
+    float *history_len;
+    bool first;
+};
+int launch_temporal(const TemporalPass &pass, void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

@@ -3796,6 +3796,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 // G-buffer-guided a-trous filter of frames and previews
 #include "vmx_filter.inc"
 
+// temporal accumulation: reprojected history blended with each new frame
+#include "vmx_temporal.inc"
+
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product
 #include "vmx_kernels_ab.inc"

@@ -1,0 +1,137 @@
+// vmx_temporal.inc — temporal accumulation: the previous accumulated frame reprojected into the new camera through the
+// new frame's G-buffer, stale history rejected by normal and plane distance, the new frame blended in (vmx_temporal_*).
+// Included by vmx_kernels.hip (inside its namespace, after vmx_filter.inc: it shares the filter's block shape).  The
+// arithmetic is stated in include/vermilion_hip.h and restated in tests/temporal_spec.py; with -ffp-contract=off every
+// operation below rounds once, in the order written, and `/` is the correctly rounded division with denormals kept: bit
+// for bit the restatement.
+//
+//   k_temporal  one call, one lane per pixel, blocks of 32 x 8 pixels like k_atrous: a wave is two image rows of 32
+//               pixels.  The block's input pixels — eight runs of 160 floats — come in through LDS and the output pixels
+//               leave through the same words (as in k_atrous<.., LAST> / k_preview: dword accesses of consecutive lanes to
+//               consecutive addresses instead of five of stride 20 per lane); alpha and depth are never touched there, so
+//               they pass through bitwise, and a call in place reads a run before any lane of the block replaces it.
+//               The record is read as three float4s (as k_filter_guide reads it).  The state is three float4 planes,
+//               (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -): each of the four taps is three loads of 16 bytes per lane from the
+//               old buffer, neighbouring lanes at neighbouring addresses wherever the reprojection is coherent; the new
+//               state goes to the other buffer.  Miss, out-of-range and every skip rule are selects, not branches (a tap
+//               that cannot count loads the lane's own pixel and is selected away); there are no transcendentals.
+//               FIRST: the call after create or reset — it reads no state and no history camera.
+struct TemporalProj {
+    float u, w;
+    bool front;
+};
+
+__device__ __forceinline__ TemporalProj temporal_proj(const TemporalCam &cam, float X, float Y, float Z, float fw, float fh) {
+    const float vx = X - cam.px, vy = Y - cam.py, vz = Z - cam.pz;
+    const float c0 = (cam.m[0] * vx + cam.m[1] * vy) + cam.m[2] * vz;
+    const float c1 = (cam.m[3] * vx + cam.m[4] * vy) + cam.m[5] * vz;
+    const float c2 = (cam.m[6] * vx + cam.m[7] * vy) + cam.m[8] * vz;
+    const float t = cam.film_dist / (-c2);
+    TemporalProj r;
+    r.u = ((c0 * t) / cam.sensor_x + 0.5f) * fw;
+    r.w = ((-(c1 * t)) / cam.sensor_y + 0.5f) * fh;
+    r.front = c2 < 0.f;
+    return r;
+}
+
+template <bool FIRST>
+__global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
+    __shared__ float s_px[kFilterBlock * 5];
+    const uint32_t W = a.width, H = a.height;
+    // (a one-dimensional grid of blocks, row-major over the image, as k_atrous)
+    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
+    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
+    const uint32_t bx0 = bx * kFilterBX, by0 = by * kFilterBY;
+    const uint32_t x = bx0 + (threadIdx.x & (kFilterBX - 1));
+    const uint32_t y = by0 + threadIdx.x / kFilterBX;
+    const bool live = x < W && y < H;
+    const uint32_t p = y * W + x;  // (W * H <= 2^28: make_frame's size check)
+    // row r of the block is the run of 5 * (its pixels in the image) floats at ((by0 + r) * W + bx0) * 5
+    const uint32_t run = min(kFilterBX, W - bx0) * 5;
+#pragma unroll
+    for (uint32_t c = 0; c < 5; ++c) {
+        const uint32_t i = c * kFilterBlock + threadIdx.x;
+        const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
+        if (by0 + r < H && col < run) s_px[i] = a.in_rgbaz[((size_t)(by0 + r) * W + bx0) * 5 + col];
+    }
+    __syncthreads();
+    if (live) {
+        float *v = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
+        const float c0 = v[0], c1 = v[1], c2 = v[2];
+        const float4 *r = (const float4 *)a.rayhit + (size_t)p * 4;  // (location, distance) (normal, tri_id) (uv, tri_t, flags)
+        const float4 ra = r[0], rb = r[1], rc = r[2];
+        const bool hit = (__float_as_uint(rc.w) & 1u) != 0;
+        const size_t npix = (size_t)W * H;
+        float o0 = c0, o1 = c1, o2 = c2, n_new = 1.f;
+        if (!FIRST) {
+            const float fw = (float)W, fh = (float)H;
+            const TemporalProj pc = temporal_proj(a.cam, ra.x, ra.y, ra.z, fw, fh);
+            const TemporalProj ph = temporal_proj(a.hist_cam, ra.x, ra.y, ra.z, fw, fh);
+            const float gx = (float)x + (ph.u - pc.u);
+            const float gy = (float)y + (ph.w - pc.w);
+            // (false for NaN; a miss takes no tap at all)
+            const bool inrange = hit && ph.front && gx >= -1.f && gx < fw && gy >= -1.f && gy < fh;
+            const float x0 = floorf(gx), y0 = floorf(gy);
+            const float fx = gx - x0, fy = gy - y0;
+            const int x0i = (int)(inrange ? x0 : 0.f), y0i = (int)(inrange ? y0 : 0.f);
+            const float zz = a.tol2 * (ra.w * ra.w);
+            const float4 *old_c = (const float4 *)a.old_state, *old_g = old_c + npix, *old_x = old_g + npix;
+            float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumn = 0.f, sumw = 0.f;
+#pragma unroll
+            for (int dy = 0; dy <= 1; ++dy) {
+#pragma unroll
+                for (int dx = 0; dx <= 1; ++dx) {
+                    const int qx = x0i + dx, qy = y0i + dy;
+                    const bool inside = (uint32_t)qx < W && (uint32_t)qy < H;
+                    const uint32_t q = inside ? (uint32_t)qy * W + (uint32_t)qx : p;
+                    const float4 hc = old_c[q], hg = old_g[q], hx = old_x[q];
+                    const float wx = dx ? fx : 1.f - fx, wy = dy ? fy : 1.f - fy;
+                    const float wt = wx * wy;
+                    const float d = (rb.x * hg.x + rb.y * hg.y) + rb.z * hg.z;
+                    const float ex = ra.x - hx.x, ey = ra.y - hx.y, ez = ra.z - hx.z;
+                    const float pd = (rb.x * ex + rb.y * ey) + rb.z * ez;
+                    const bool ok = inrange && inside && hg.w >= 0.f && d >= a.normal_min && pd * pd <= zz && wt > 0.f;
+                    sum0 = ok ? sum0 + wt * hc.x : sum0;
+                    sum1 = ok ? sum1 + wt * hc.y : sum1;
+                    sum2 = ok ? sum2 + wt * hc.z : sum2;
+                    sumn = ok ? sumn + wt * hc.w : sumn;
+                    sumw = ok ? sumw + wt : sumw;
+                }
+            }
+            const bool any = sumw > 0.f;
+            const float h0 = sum0 / sumw, h1 = sum1 / sumw, h2 = sum2 / sumw, nh = sumn / sumw;
+            const float t = nh + 1.f;
+            const float n1 = t < a.max_history ? t : a.max_history;
+            const float al = 1.f / n1;
+            o0 = any ? h0 + (c0 - h0) * al : c0;
+            o1 = any ? h1 + (c1 - h1) * al : c1;
+            o2 = any ? h2 + (c2 - h2) * al : c2;
+            n_new = any ? n1 : 1.f;
+        }
+        float4 *new_c = (float4 *)a.new_state, *new_g = new_c + npix, *new_x = new_g + npix;
+        new_c[p] = make_float4(o0, o1, o2, n_new);
+        new_g[p] = hit ? make_float4(rb.x, rb.y, rb.z, ra.w) : make_float4(0.f, 0.f, 0.f, -1.f);
+        new_x[p] = make_float4(ra.x, ra.y, ra.z, 0.f);
+        v[0] = o0, v[1] = o1, v[2] = o2;  // (v[3], v[4]: alpha and depth, the input's bits)
+        if (a.rgba8) ((uchar4 *)a.rgba8)[p] = quantized_pixel(v);
+        if (a.history_len) a.history_len[p] = n_new;
+    }
+    if (!a.out_rgbaz) return;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t c = 0; c < 5; ++c) {
+        const uint32_t i = c * kFilterBlock + threadIdx.x;
+        const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
+        if (by0 + r < H && col < run) a.out_rgbaz[((size_t)(by0 + r) * W + bx0) * 5 + col] = s_px[i];
+    }
+}
+
+int launch_temporal(const TemporalPass &a, void *stream) {
+    if (a.width == 0 || a.height == 0) return 0;
+    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
+    if (a.first)
+        hipLaunchKernelGGL(k_temporal<true>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(k_temporal<false>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+    return launch_status();
+}

@@ -117,6 +117,19 @@ def make_filter_params(iterations=None, normal_squarings=None, sigma_colour=None
     return p
 
 
+def make_temporal_params(normal_min=None, plane_tol=None, max_history=None):
+    """vmx_temporal_params: the library's defaults (vmx_temporal_default_params) with the given fields replaced"""
+    p = L.TemporalParams()
+    L.check(L.lib().vmx_temporal_default_params(C.byref(p)))
+    if normal_min is not None:
+        p.normal_min = float(normal_min)
+    if plane_tol is not None:
+        p.plane_tol = float(plane_tol)
+    if max_history is not None:
+        p.max_history = float(max_history)
+    return p
+
+
 def _frame_tensor(x, name, dtype, shape, dev):
     """an output or input of the device filter / previews as the ABI takes it, or a ValueError"""
     if not _is_tensor(x):
@@ -650,6 +663,80 @@ class Filter:
                                                           None if params is None else C.byref(params),
                                                           C.c_void_p(run.cuda_stream)))
         return out, rgba8
+
+
+class Temporal:
+    """One vmx_temporal handle: temporal accumulation (include/vermilion_hip.h) of [height, width] frames on `device`.
+    `accumulate` reprojects the frames accumulated so far into the new camera through the new frame's G-buffer and
+    blends the new frame in; `reset` forgets them."""
+
+    def __init__(self, width, height, device=0, lib=None):
+        self._lib = lib if lib is not None else L.lib()
+        self._h = None
+        self.device = int(device)
+        self.shape = (int(height), int(width))
+        h = C.c_void_p()
+        self._check(self._lib.vmx_temporal_create(self.device, int(width), int(height), C.byref(h)))
+        self._h = h
+
+    def _check(self, code):
+        if code != L.VMX_OK:
+            raise L.VmxError(code, self._lib.vmx_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._check(self._lib.vmx_temporal_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None):
+        """vmx_temporal_accumulate_device: one frame.  `cam` is that frame's camera (make_camera), `raw` its G-buffer —
+        the ["raw"] tensor of Scene.raycast_camera(cam, opts, 0), float32 [height, width, 16] — and `rgbaz` the float32
+        [height, width, 5] frame.  The accumulated frame goes to `out` (same shape; may be `rgbaz` itself) and / or
+        `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is made.  `history` (float32 [height, width])
+        receives each pixel's history length.  All are contiguous torch tensors on the handle's device: anything else is
+        a ValueError, never a copy through the host.  params: make_temporal_params(...), default the library's.
+        Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        _frame_tensor(raw, "raw", torch.float32, self.shape + (16,), dev)
+        _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if out is None and rgba8 is None:
+            out = torch.empty_like(rgbaz)
+        if out is not None:
+            _frame_tensor(out, "out", torch.float32, self.shape + (5,), dev)
+        if rgba8 is not None:
+            _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
+        if history is not None:
+            _frame_tensor(history, "history", torch.float32, self.shape, dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_temporal_accumulate_device(self._h, C.byref(cam), ptr(raw), ptr(rgbaz), ptr(out),
+                                                                 ptr(rgba8), ptr(history),
+                                                                 None if params is None else C.byref(params),
+                                                                 C.c_void_p(run.cuda_stream)))
+        return out, rgba8
+
+    def reset(self, stream=None):
+        """vmx_temporal_reset: forgets the history; the next `accumulate` is a first call"""
+        self._check(self._lib.vmx_temporal_reset(self._h, None if stream is None else C.c_void_p(stream.cuda_stream)))
+
+    def frames(self):
+        """vmx_temporal_frames: calls of `accumulate` since the handle was made or reset"""
+        n = C.c_uint64(0)
+        self._check(self._lib.vmx_temporal_frames(self._h, C.byref(n)))
+        return n.value
 
 
 class MultiScene:
