@@ -1,9 +1,12 @@
 // render_flythrough.cpp — N frames of a few samples along a camera path, each pushed through the preview chain on the
 // device, through the C ABI only (include/vermilion_hip.h):
+//   vmx_raycast_camera_device    the frame's G-buffer: sample 0's camera ray of every pixel
 //   vmx_render_device            the frame at 4 spp (by default), a new seed per frame
-//   vmx_raycast_camera_device    its G-buffer: sample 0's camera ray of every pixel
-//   vmx_temporal_accumulate_device  the frames so far, reprojected into this camera, blended with the new one
+//   vmx_temporal_accumulate_motion_device  the frames so far, reprojected into this camera, blended with the new one;
+//                                with no motion records (NULL) it is vmx_temporal_accumulate_device
 //   vmx_filter_set_guide_device + vmx_filter_apply_device  the a-trous filter on the accumulated frame -> rgba8
+// (the G-buffer comes first in both modes, because --moving needs it before the motion records; the two calls write
+// different buffers on one stream, so the order changes no result)
 // Everything stays on one stream and in device memory; only the rgba8 form of the frames that are written comes back.
 // The library has no allocator of its own: a host application brings its device buffers.  This one takes the few HIP
 // runtime calls it needs from the runtime the library has loaded, so that it builds like the other examples; that
@@ -12,10 +15,19 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
+//
+// --moving: the block moves by (30, 0, 40) every frame as well, and each frame becomes
+//   vmx_scene_update_device (refit)   the new positions, from a device buffer
+//   vmx_raycast_camera_device         the G-buffer of the moved scene
+//   vmx_motion_device                 where each pixel's surface point was before the update
+//   vmx_render_device
+//   vmx_temporal_accumulate_motion_device   the history looked up where the surface was: the block keeps its own
+//   vmx_filter_set_guide_device + vmx_filter_apply_device
+// A second accumulator takes the same frames without the motion records; the mean history length of both is printed.
 #include <dlfcn.h>
 
 #include <cmath>
@@ -53,6 +65,7 @@ struct Hip {
     int (*stream_create)(void **) = nullptr;
     int (*stream_sync)(void *) = nullptr;
     int (*stream_destroy)(void *) = nullptr;
+    int (*memcpy_async)(void *, const void *, size_t, int, void *) = nullptr;
     bool load() {
         malloc_ = (int (*)(void **, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
         free_ = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipFree");
@@ -60,7 +73,8 @@ struct Hip {
         stream_create = (int (*)(void **))dlsym(RTLD_DEFAULT, "hipStreamCreate");
         stream_sync = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipStreamSynchronize");
         stream_destroy = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipStreamDestroy");
-        return malloc_ && free_ && memcpy_ && stream_create && stream_sync && stream_destroy;
+        memcpy_async = (int (*)(void *, const void *, size_t, int, void *))dlsym(RTLD_DEFAULT, "hipMemcpyAsync");
+        return malloc_ && free_ && memcpy_ && stream_create && stream_sync && stream_destroy && memcpy_async;
     }
 };
 
@@ -76,6 +90,8 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 }  // namespace
 
 int main(int argc, char **argv) {
+    const bool moving = argc > 1 && std::strcmp(argv[1], "--moving") == 0;
+    if (moving) --argc, ++argv;
     const std::string out = argc > 1 ? argv[1] : "fly";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 8;
@@ -108,6 +124,11 @@ int main(int argc, char **argv) {
     vmx_temporal *temporal = nullptr;
     vmx_filter *filter = nullptr;
     void *stream = nullptr, *d_frame = nullptr, *d_rec = nullptr, *d_acc = nullptr, *d_rgba8 = nullptr, *d_hist = nullptr;
+    // --moving: the positions of this frame and of the one before, the motion records, the other accumulator and its outputs
+    const uint32_t ntris = (uint32_t)(pos.size() / 9);
+    vmx_temporal *plain = nullptr;
+    void *d_pos[2] = {nullptr, nullptr}, *d_motion = nullptr, *d_acc_plain = nullptr, *d_hist_plain = nullptr;
+    std::vector<float> moved = pos, hist_plain(moving ? (size_t)W * H : 0);
     std::vector<unsigned char> rgba(npix * 4);
     std::vector<float> hist(npix);
     int rc = VMX_OK;
@@ -116,6 +137,12 @@ int main(int argc, char **argv) {
                   hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, npix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
     if (hip_ok) rc = vmx_temporal_create(0, W, H, &temporal);
     if (hip_ok && rc == VMX_OK) rc = vmx_filter_create(0, W, H, &filter);
+    if (moving && hip_ok && rc == VMX_OK) {
+        hip_ok = hip.malloc_(&d_pos[0], pos.size() * 4) == 0 && hip.malloc_(&d_pos[1], pos.size() * 4) == 0 &&
+                 hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0 && hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
+                 hip.malloc_(&d_hist_plain, npix * 4) == 0 && hip.memcpy_(d_pos[0], pos.data(), pos.size() * 4, 1) == 0;
+        if (hip_ok) rc = vmx_temporal_create(0, W, H, &plain);
+    }
     // rgba8 of a device frame (vmx_quantize_device), or of d_rgba8 as it stands, on the host
     auto fetch = [&](const void *d_rgbaz) {
         if (d_rgbaz && (rc = vmx_quantize_device(d_rgbaz, npix, d_rgba8, nullptr, 0, stream)) != VMX_OK) return false;
@@ -135,17 +162,43 @@ int main(int argc, char **argv) {
         opts.seed = seed + i;
         opts.sampling = VMX_SAMPLING_CORRECTED;
         vmx_stats st;
-        if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
+        const bool update = moving && i > 0;  // (frame 0 shows the scene as it was made: d_pos[0])
+        if (update) {
+            // the block (triangles 4..7) by (30, 0, 40) per frame: a translation, so the previous normals are not needed
+            for (uint32_t t = 4; t < 8; ++t)
+                for (uint32_t v = 0; v < 3; ++v)
+                    moved[t * 9 + v * 3] = pos[t * 9 + v * 3] + 30.f * (float)i, moved[t * 9 + v * 3 + 2] = pos[t * 9 + v * 3 + 2] + 40.f * (float)i;
+            // (hipMemcpyHostToDevice = 1; d_pos[i & 1] was last read two frames ago, on this stream)
+            if (!(hip_ok = hip.memcpy_async(d_pos[i & 1], moved.data(), moved.size() * 4, 1, stream) == 0 && hip.stream_sync(stream) == 0))
+                break;
+            if ((rc = vmx_scene_update_device(scene, d_pos[i & 1], nullptr, nullptr, ntris, VMX_UPDATE_REFIT, stream)) != VMX_OK) break;
+        }
         if ((rc = vmx_raycast_camera_device(scene, &cam, &opts, 0, d_rec, 0, stream)) != VMX_OK) break;
-        if ((rc = vmx_temporal_accumulate_device(temporal, &cam, d_rec, d_frame, d_acc, nullptr, d_hist, nullptr, stream)) != VMX_OK)
+        if (update && (rc = vmx_motion_device(d_rec, (uint32_t)npix, d_pos[i & 1], d_pos[(i & 1) ^ 1], nullptr, ntris, d_motion, 0,
+                                              stream)) != VMX_OK)
+            break;
+        if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
+        if ((rc = vmx_temporal_accumulate_motion_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc, nullptr,
+                                                        d_hist, nullptr, stream)) != VMX_OK)
+            break;
+        if (moving && (rc = vmx_temporal_accumulate_device(plain, &cam, d_rec, d_frame, d_acc_plain, nullptr, d_hist_plain, nullptr,
+                                                           stream)) != VMX_OK)
             break;
         if ((rc = vmx_filter_set_guide_device(filter, d_rec, stream)) != VMX_OK) break;
         if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
         if (!(hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(hist.data(), d_hist, npix * 4, 2) == 0)) break;
         double mean = 0;
         for (float n : hist) mean += n;
-        std::printf("frame %u: camera x %.0f, y-rotation %.2f deg, %.2f ms device, mean history %.2f frames\n", i,
-                    cam.position[0], cam.rotation_deg[1], st.ms_device, mean / (double)npix);
+        if (moving) {
+            if (!(hip_ok = hip.memcpy_(hist_plain.data(), d_hist_plain, npix * 4, 2) == 0)) break;
+            double mean_plain = 0;
+            for (float n : hist_plain) mean_plain += n;
+            std::printf("frame %u: block at +%.0f x +%.0f z, camera x %.0f, %.2f ms device, mean history %.2f frames with motion "
+                        "records, %.2f without\n", i, 30.0 * i, 40.0 * i, cam.position[0], st.ms_device, mean / (double)npix,
+                        mean_plain / (double)npix);
+        } else
+            std::printf("frame %u: camera x %.0f, y-rotation %.2f deg, %.2f ms device, mean history %.2f frames\n", i,
+                        cam.position[0], cam.rotation_deg[1], st.ms_device, mean / (double)npix);
         if (i + 1 == frames) {
             const std::pair<const char *, const void *> files[3] = {{"_out.ppm", nullptr}, {"_acc.ppm", d_acc}, {"_raw.ppm", d_frame}};
             for (const auto &f : files)
@@ -160,7 +213,8 @@ int main(int argc, char **argv) {
     if (stream) hip.stream_sync(stream);
     if (filter) vmx_filter_destroy(filter);
     if (temporal) vmx_temporal_destroy(temporal);
-    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist})
+    if (plain) vmx_temporal_destroy(plain);
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain})
         if (p) hip.free_(p);
     if (stream) hip.stream_destroy(stream);
     vmx_scene_destroy(scene);

@@ -538,9 +538,11 @@ int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned 
  * New state: c_h = out, n_h = n', guide, X (the record's location as it stands) and camera of this call.
  * Outputs: d_out_rgbaz = out in r, g, b, alpha and depth the input's bits; d_rgba8 = vmx_quantize_device's arithmetic
  * on that pixel; d_history_len[p] = n'.
- * Limits: the world is taken as static between the two frames — after vmx_scene_update a moved surface fails the
- * plane test and restarts at n' = 1; there are no motion vectors for refitted geometry.  A NaN colour passes into the
- * history and stays until that pixel is invalidated or the handle is reset.
+ * Limits: without motion records (below) the world is taken as static between the two frames — after
+ * vmx_scene_update a moved surface fails the plane test and restarts at n' = 1, and a face that slid within its own
+ * plane keeps history of other surface points; vmx_motion_device and vmx_temporal_accumulate_motion_device follow
+ * refitted triangles.  The analytic spheres have no motion records.  A NaN colour passes into the history and stays
+ * until that pixel is invalidated or the handle is reset.
  * The kernel holds to this restatement bit for bit (tests/temporal_spec.py).
  */
 typedef struct vmx_temporal_params {
@@ -572,6 +574,56 @@ int vmx_temporal_frames(const vmx_temporal *t, uint64_t *frames_since_reset);
 int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit,
                                    const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
                                    const vmx_temporal_params *params, void *stream);
+
+/* ---- motion records: temporal accumulation that follows refitted geometry -------------------------------
+ * After vmx_scene_update[_device] a pixel's surface point was somewhere else a frame earlier.  vmx_motion_device is a
+ * pure function of a G-buffer and the two position arrays the caller of vmx_scene_update_device already holds (no scene
+ * handle): per record, the point its surface point occupied before the update and the normal the previous frame's
+ * G-buffer had there.  Everything is float, one rounding per written operation, left to right; `/` and sqrtf are
+ * correctly rounded, denormals are kept.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * For record r:  P = r.location, id = r.tri_id, a0 a1 a2 = the vertices at pos_now[id*9 ..], q0 q1 q2 = those at
+ * pos_prev[id*9 ..].
+ *   on = (r.flags & 1) && id >= 0 && id < ntris && r.distance == r.tri_t      (tri_id stays set when a sphere is nearer
+ *        than the triangle: the location then lies on the sphere and the distances differ); when !on no array is read
+ *   moved = any of the nine position words differs bitwise between pos_now and pos_prev
+ *   e1 = a1 - a0;  e2 = a2 - a0;  ep = P - a0
+ *   d11 = dot(e1,e1);  d12 = dot(e1,e2);  d22 = dot(e2,e2);  dp1 = dot(ep,e1);  dp2 = dot(ep,e2)
+ *   den = d11*d22 - d12*d12;  b1 = (d22*dp1 - d12*dp2)/den;  b2 = (d11*dp2 - d12*dp1)/den;  b0 = (1.f - b1) - b2
+ *   Xh. = (b0*q0. + b1*q1.) + b2*q2.  per component;  good = den > 0 && every component of Xh finite
+ *   with d_nrm_prev (n0 n1 n2 = the normals at nrm_prev[id*9 ..]):  m. = (b0*n0. + b1*n1.) + b2*n2.;
+ *     s = 1.f / sqrtf(dot(m, m));  nh. = -(m.*s)  (negated, as Triangle::getNormal negates);  nh = r.normal if any
+ *     component is not finite.  Without d_nrm_prev:  nh = r.normal  (right for translations).
+ *   on && moved && good:  the output is (Xh, VMX_MOTION_MOVED, nh, 0);  otherwise (r.location, 0, r.normal, 0), the
+ *   record's own bits — a triangle that did not move takes exactly the path without motion records.
+ * The kernel holds to this restatement bit for bit (tests/motion_spec.py).
+ */
+#define VMX_MOTION_MOVED 1u
+typedef struct vmx_motion {       /* 32 bytes, two float4 */
+    float prev_location[3];       /* where this pixel's surface point was before the update   */
+    uint32_t flags;               /* VMX_MOTION_MOVED or 0                                    */
+    float prev_normal[3];         /* the normal the previous frame's G-buffer had there       */
+    uint32_t pad;                 /* 0                                                        */
+} vmx_motion;
+/* d_rayhit: n vmx_rayhit records, 16-byte aligned; d_pos_now, d_pos_prev: ntris*9 floats each, the positions after and
+ * before the update (what vmx_scene_update_device takes); d_nrm_prev: the normals before it, or NULL; d_out: n vmx_motion
+ * records, 16-byte aligned, overlapping no input.  All DEVICE memory of `device`, checked as vmx_query_device checks its
+ * pointers; the arrays are 4-byte aligned.  ntris == 0, n > 2^31 - 1 or a NULL pointer other than d_nrm_prev is
+ * VMX_ERR_INVALID; n == 0 is VMX_OK and launches nothing.  Enqueued on `stream`, no synchronisation. */
+int vmx_motion_device(const void *d_rayhit, uint32_t n, const void *d_pos_now, const void *d_pos_prev,
+                      const void *d_nrm_prev /* or NULL */, uint32_t ntris, void *d_out, int device, void *stream);
+/* vmx_temporal_accumulate_device with motion records: d_motion = W*H vmx_motion records in pixel order, 16-byte aligned,
+ * read only (it may overlap no buffer the call writes), or NULL — then the call IS vmx_temporal_accumulate_device.
+ * Per pixel Xh, nh = prev_location, prev_normal of its record (X, n_p wherever the flag is clear), and the
+ * restatement above changes in exactly three places:
+ *   (u_h, w_h, front) = proj(Xh, the previous call's cam)      ((u_c, w_c) stays proj(X, this call's cam))
+ *   the normal test is  (nh.x*n_q.x + nh.y*n_q.y) + nh.z*n_q.z >= normal_min
+ *   e = Xh - X_q,  pd = (nh.x*e.x + nh.y*e.y) + nh.z*e.z
+ * zz stays (plane_tol*plane_tol) * (z_p*z_p); the new state stays this call's guide, X and camera.  A first call
+ * ignores the records. */
+int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit,
+                                          const void *d_motion, const void *d_in_rgbaz, void *d_out_rgbaz,
+                                          void *d_rgba8, void *d_history_len, const vmx_temporal_params *params,
+                                          void *stream);
 
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers

@@ -3,11 +3,7 @@
 # run of the C++ examples against it on the GPU box.   /usr/local/graft/bin/gpurun -- 'bash tools/host_asan.sh'
 set -e -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-cd $R/vermilion_amd/csrc
-mkdir -p $R/build
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -fPIC -ffp-contract=off -fno-slp-vectorize -Wno-unused-function \
-  -DVMX_TRACE_WAVES_PER_SIMD=7 -DVMX_TRACE_SGPRS=80 -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer \
-  -I$R/include -shared -o $R/build/libvermilion_hip_asan.so vmx_kernels.hip lbvh_build.hip path_compact.hip -x hip vmx_api.cpp bvh_build.cpp
+. $R/tools/host_asan_build.sh
 cd $R
 for ex in render_cornell render_multi; do
   /opt/rocm/lib/llvm/bin/clang++ -std=c++17 -g -fsanitize=address -fsanitize=undefined -I include examples/$ex.cpp build/libvermilion_hip_asan.so \

@@ -13,7 +13,13 @@ Everything is timed with torch CUDA event pairs on the stream the work runs on, 
     as tools/filter_bench.py counts it: the rate the temporal kernel is expected to reach at least.
 Achieved bytes per second are against the least traffic a call needs, per pixel: 64 B record + 20 B frame + 48 B old
 state read, 48 B new state + 20 B frame written (+ 4 B rgba8, + 4 B history length); a first call reads no state.  The
-four taps' re-reads are served by the caches and are not in the model."""
+four taps' re-reads are served by the caches and are not in the model.
+  - the motion leg: vmx_motion_device alone (k_motion) on the second camera's G-buffer, with and without previous normals,
+    the previous positions being the scene's own moved by (0.5, 0, 0.3) — every record on a triangle is flagged — and
+    vmx_temporal_accumulate_motion_device with those records (rgbaz + rgba8), the call without them timed beside it.
+    Models: the motion call reads 32 B per pixel more; k_motion reads the 64 B record and writes 32 B per record.  Its
+    gathers by tri_id (two or three times 36 B per record, neighbouring pixels mostly the same triangle: served by the
+    caches) are not in the model."""
 import argparse
 import os
 import sys
@@ -33,6 +39,11 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, as bench.py
 def model_bytes(npix, first=False, rgbaz=True, rgba8=False, history=False):
     per_pixel = 64 + 20 + (0 if first else 48) + 48 + (20 if rgbaz else 0) + (4 if rgba8 else 0) + (4 if history else 0)
     return npix * per_pixel
+
+
+def motion_model_bytes(npix):
+    """vmx_motion_device: the record read, the motion record written; the gathers by tri_id are not counted"""
+    return npix * (64 + 32)
 
 
 def filter_model_bytes(npix):
@@ -82,6 +93,8 @@ def main():
 
     pos, nrm, uv = scenes.sponza260k()
     c = scenes.sponza_camera()
+    d_pos, d_nrm = torch.from_numpy(pos).cuda(), torch.from_numpy(nrm).cuda()
+    d_prev = (d_pos.view(-1, 3) + torch.tensor([0.5, 0.0, 0.3], device="cuda")).view(-1, 9).contiguous()
     with va.Scene(pos, nrm, uv) as sc:
         for size in args.sizes.split(","):
             W, H = (int(v) for v in size.split("x"))
@@ -127,6 +140,21 @@ def main():
                 tm = timed(lambda i: f.apply(views[0][2], out=o5, rgba8=o4, params=one, stream=stream))
                 filt = row("filter apply, iterations 1, rgbaz + rgba8", tm, filter_model_bytes(npix))
                 emit(f"  accumulate (rgbaz + rgba8) reaches {rates[1] / filt:.2f} x the model rate of that filter call")
+                # the motion leg: the records of the second view, then calls that alternate as above, the second view's with them
+                mv = torch.empty((H, W, 8), dtype=torch.float32, device="cuda")
+                raw1 = views[1][1]
+                tm = timed(lambda i: va.motion_vectors(raw1, d_pos, d_prev, out=mv, stream=stream))
+                row("motion records (k_motion), no normals", tm, motion_model_bytes(npix))
+                tm = timed(lambda i: va.motion_vectors(raw1, d_pos, d_prev, d_nrm, out=mv, stream=stream))
+                row("motion records (k_motion), previous normals", tm, motion_model_bytes(npix))
+                emit(f"  {float((mv.view(torch.int32)[..., 3] & 1).float().mean()):.1%} of the records are flagged")
+                mvs = [va.motion_vectors(v[1], d_pos, d_prev, d_nrm, stream=stream) for v in views]
+                call(1, out=o5)
+                tm = timed(lambda i: call(i, out=o5, rgba8=o4))
+                plain = row("accumulate, rgbaz + rgba8 (again, beside the motion call)", tm, model_bytes(npix, False, True, True))
+                tm = timed(lambda i: call(i, out=o5, rgba8=o4, motion=mvs[i % 2]))
+                with_mv = row("accumulate with motion records, rgbaz + rgba8", tm, model_bytes(npix, False, True, True) + npix * 32)
+                emit(f"  the motion call reaches {with_mv / plain:.2f} x the model rate of the call without")
     if args.out:
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")

@@ -189,6 +189,15 @@ class FilterParams(C.Structure):
                 "sigma_colour": self.sigma_colour, "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
 
 
+class Motion(C.Structure):
+    _fields_ = [
+        ("prev_location", C.c_float * 3),
+        ("flags", C.c_uint32),
+        ("prev_normal", C.c_float * 3),
+        ("pad", C.c_uint32),
+    ]
+
+
 class TemporalParams(C.Structure):
     _fields_ = [
         ("normal_min", C.c_float),
@@ -252,6 +261,9 @@ SYMBOLS = {
     "vmx_temporal_frames": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "vmx_temporal_accumulate_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, C.POINTER(TemporalParams),
                                                  _P]),
+    "vmx_temporal_accumulate_motion_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P,
+                                                        C.POINTER(TemporalParams), _P]),
+    "vmx_motion_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_int, _P]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

@@ -84,6 +84,13 @@ int vmx_temporal_frames(const vmx_temporal *t, uint64_t *frames_since_reset) {
 int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_in_rgbaz,
                                    void *d_out_rgbaz, void *d_rgba8, void *d_history_len, const vmx_temporal_params *params,
                                    void *stream) {
+    return vmx_temporal_accumulate_motion_device(t, cam, d_rayhit, nullptr, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len,
+                                                 params, stream);
+}
+
+int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
+                                          const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                                          const vmx_temporal_params *params, void *stream) {
     // checks that need no device, in the filter's order so that each can be seen alone; the handle comes last
     vmx_temporal_params prm;
     if (int rc = temporal_params(params, prm)) return rc;
@@ -92,6 +99,7 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
     if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
     if (!d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
     if ((uintptr_t)d_rayhit & 15u) return fail(VMX_ERR_INVALID, "d_rayhit must be 16-byte aligned");
+    if ((uintptr_t)d_motion & 15u) return fail(VMX_ERR_INVALID, "d_motion must be 16-byte aligned");
     if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8 | (uintptr_t)d_history_len) & 3u)
         return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len must be 4-byte aligned");
     FrameDev fr;
@@ -110,6 +118,9 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
         const uintptr_t lo[5] = {(uintptr_t)d_rayhit, (uintptr_t)d_in_rgbaz, (uintptr_t)d_out_rgbaz, (uintptr_t)d_rgba8,
                                  (uintptr_t)d_history_len};
         const uintptr_t len[5] = {npix * 64, npix * 20, npix * 20, npix * 4, npix * 4};
+        for (int j = 2; j < 5 && d_motion; ++j)  // (the motion records are read only, like d_rayhit)
+            if (lo[j] && (uintptr_t)d_motion < lo[j] + len[j] && lo[j] < (uintptr_t)d_motion + npix * 32)
+                return fail(VMX_ERR_INVALID, "d_motion overlaps d_out_rgbaz, d_rgba8 or d_history_len");
         for (int i = 0; i < 5; ++i)
             for (int j = std::max(i + 1, 2); j < 5; ++j) {  // (j: the written ones)
                 if (!lo[i] || !lo[j] || (i == 1 && j == 2 && lo[1] == lo[2])) continue;
@@ -119,7 +130,7 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
     }
     HIP_TRY(hipSetDevice(t->device));
     if (int rc = check_device_ptrs(t->device, {{d_rayhit, "d_rayhit"}, {d_in_rgbaz, "d_in_rgbaz"}, {d_out_rgbaz, "d_out_rgbaz"},
-                                               {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}}))
+                                               {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}, {d_motion, "d_motion"}}))
         return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = t->done.wait(s)) return rc;  // after the previous call on this handle
@@ -134,6 +145,7 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
     a.old_state = t->state[t->cur].p, a.new_state = t->state[t->cur ^ 1].p;
     a.out_rgbaz = (float *)d_out_rgbaz, a.rgba8 = d_rgba8, a.history_len = (float *)d_history_len;
     a.first = !t->has_history;
+    a.motion = d_motion;
     LAUNCH_TRY(launch_temporal(a, s));
     if (int rc = t->done.record(s)) {
         // the next call could not be ordered after this kernel: wait for it here and leave the history as it was (the

@@ -43,6 +43,7 @@ using namespace vmx;
 #include "api_query.inc"       // vmx_trace, vmx_raycast*, vmx_query*, vmx_primary_ids, vmx_radiance, vmx_trig
 #include "api_filter.inc"      // vmx_filter_*
 #include "api_temporal.inc"    // vmx_temporal_*
+#include "api_motion.inc"      // vmx_motion_device
 #include "api_progressive.inc" // vmx_progressive_*
 #include "api_multi.inc"       // vmx_multi_*, vmx_assemble_device, vmx_quantize_device
 #include "api_update.inc"      // vmx_scene_update*, vmx_multi_update

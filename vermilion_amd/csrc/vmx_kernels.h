@@ -257,8 +257,13 @@ struct TemporalPass {  // one call
     void *rgba8;
     float *history_len;
     bool first;
+    const void *motion;    // vmx_motion per pixel or NULL (last, so that every other member is where it was); not read by a first call
 };
 int launch_temporal(const TemporalPass &pass, void *stream);
+// motion records for refitted geometry (vmx_motion.inc; the arithmetic is stated in include/vermilion_hip.h)
+constexpr uint32_t kMotionMoved = 1u;  // VMX_MOTION_MOVED
+int launch_motion(const void *rayhit, uint32_t n, const float *pos_now, const float *pos_prev, const float *nrm_prev,
+                  uint32_t ntris, void *out, void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

@@ -3798,6 +3798,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 
 // temporal accumulation: reprojected history blended with each new frame
 #include "vmx_temporal.inc"
+// motion records for refitted geometry: where each pixel's surface point was before an update
+#include "vmx_motion.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

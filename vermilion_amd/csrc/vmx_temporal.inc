@@ -16,6 +16,10 @@
 //               state goes to the other buffer.  Miss, out-of-range and every skip rule are selects, not branches (a tap
 //               that cannot count loads the lane's own pixel and is selected away); there are no transcendentals.
 //               FIRST: the call after create or reset — it reads no state and no history camera.
+//               MOTION: vmx_temporal_accumulate_motion_device with records — two more float4 loads per lane, (Xh, flags)
+//               (nh, -) of vmx_motion.inc: the history is looked up where the surface point was (proj of Xh in the
+//               previous camera) and tested against what was there (nh, Xh); without it Xh, nh are the record's own X, n_p
+//               and the instantiation is the one there was before motion records.  A first call ignores them.
 struct TemporalProj {
     float u, w;
     bool front;
@@ -34,7 +38,7 @@ __device__ __forceinline__ TemporalProj temporal_proj(const TemporalCam &cam, fl
     return r;
 }
 
-template <bool FIRST>
+template <bool FIRST, bool MOTION>
 __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
     __shared__ float s_px[kFilterBlock * 5];
     const uint32_t W = a.width, H = a.height;
@@ -64,9 +68,15 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
         const size_t npix = (size_t)W * H;
         float o0 = c0, o1 = c1, o2 = c2, n_new = 1.f;
         if (!FIRST) {
+            float Xhx = ra.x, Xhy = ra.y, Xhz = ra.z, mnx = rb.x, mny = rb.y, mnz = rb.z;
+            if (MOTION) {
+                const float4 *m = (const float4 *)a.motion + (size_t)p * 2;  // (prev_location, flags) (prev_normal, pad)
+                const float4 ma = m[0], mb = m[1];
+                Xhx = ma.x, Xhy = ma.y, Xhz = ma.z, mnx = mb.x, mny = mb.y, mnz = mb.z;
+            }
             const float fw = (float)W, fh = (float)H;
             const TemporalProj pc = temporal_proj(a.cam, ra.x, ra.y, ra.z, fw, fh);
-            const TemporalProj ph = temporal_proj(a.hist_cam, ra.x, ra.y, ra.z, fw, fh);
+            const TemporalProj ph = temporal_proj(a.hist_cam, Xhx, Xhy, Xhz, fw, fh);
             const float gx = (float)x + (ph.u - pc.u);
             const float gy = (float)y + (ph.w - pc.w);
             // (false for NaN; a miss takes no tap at all)
@@ -87,9 +97,9 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
                     const float4 hc = old_c[q], hg = old_g[q], hx = old_x[q];
                     const float wx = dx ? fx : 1.f - fx, wy = dy ? fy : 1.f - fy;
                     const float wt = wx * wy;
-                    const float d = (rb.x * hg.x + rb.y * hg.y) + rb.z * hg.z;
-                    const float ex = ra.x - hx.x, ey = ra.y - hx.y, ez = ra.z - hx.z;
-                    const float pd = (rb.x * ex + rb.y * ey) + rb.z * ez;
+                    const float d = (mnx * hg.x + mny * hg.y) + mnz * hg.z;
+                    const float ex = Xhx - hx.x, ey = Xhy - hx.y, ez = Xhz - hx.z;
+                    const float pd = (mnx * ex + mny * ey) + mnz * ez;
                     const bool ok = inrange && inside && hg.w >= 0.f && d >= a.normal_min && pd * pd <= zz && wt > 0.f;
                     sum0 = ok ? sum0 + wt * hc.x : sum0;
                     sum1 = ok ? sum1 + wt * hc.y : sum1;
@@ -130,8 +140,10 @@ int launch_temporal(const TemporalPass &a, void *stream) {
     if (a.width == 0 || a.height == 0) return 0;
     const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
     if (a.first)
-        hipLaunchKernelGGL(k_temporal<true>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((k_temporal<true, false>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+    else if (a.motion)
+        hipLaunchKernelGGL((k_temporal<false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(k_temporal<false>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((k_temporal<false, false>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
     return launch_status();
 }

@@ -145,6 +145,52 @@ def _frame_tensor(x, name, dtype, shape, dev):
     return x
 
 
+def motion_vectors(raw, pos_now, pos_prev, nrm_prev=None, out=None, stream=None):
+    """vmx_motion_device: the motion records of a G-buffer after a geometry update, for Temporal.accumulate(motion=...).
+    `raw` is the ["raw"] tensor of Scene.raycast_camera on the updated scene (float32 [..., 16]); `pos_now` and `pos_prev`
+    the [ntris, 9] positions after and before the update (what Scene.update took); `nrm_prev` the [ntris, 9] normals
+    before it, or None (right for translations).  Returns `out`, float32 [..., 8] words (MOTION_DTYPE's fields), made
+    if not given.  All are contiguous float32 torch tensors on raw's device: anything else is a ValueError, never a
+    copy through the host.  Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised."""
+    import torch
+    if not _is_tensor(raw):
+        raise ValueError("raw must be a torch tensor")
+    if raw.dtype != torch.float32:
+        raise ValueError(f"raw must be {torch.float32} (got {raw.dtype})")
+    if len(raw.shape) < 1 or raw.shape[-1] != 16:
+        raise ValueError(f"raw must be [..., 16] (got {list(raw.shape)})")
+    if not raw.is_contiguous():
+        raise ValueError("raw must be contiguous")
+    dev = raw.device
+    if dev.type != "cuda":
+        raise ValueError(f"raw must be on cuda (got {dev})")
+    if not _is_tensor(pos_now):
+        raise ValueError("pos_now must be a torch tensor")
+    if len(pos_now.shape) != 2 or pos_now.shape[0] == 0:
+        raise ValueError(f"pos_now must be [ntris, 9] (got {list(pos_now.shape)})")
+    ntris = int(pos_now.shape[0])
+    _frame_tensor(pos_now, "pos_now", torch.float32, (ntris, 9), dev)
+    _frame_tensor(pos_prev, "pos_prev", torch.float32, (ntris, 9), dev)
+    if nrm_prev is not None:
+        _frame_tensor(nrm_prev, "nrm_prev", torch.float32, (ntris, 9), dev)
+    lead = tuple(raw.shape[:-1])
+    n = 1
+    for d in lead:
+        n *= int(d)
+    if out is None:
+        out = torch.empty(lead + (8,), dtype=torch.float32, device=dev)
+    else:
+        _frame_tensor(out, "out", torch.float32, lead + (8,), dev)
+    if n == 0:
+        return out
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    with _SideStream(dev, stream) as run:
+        L.check(L.lib().vmx_motion_device(ptr(raw), n, ptr(pos_now), ptr(pos_prev), ptr(nrm_prev), ntris, ptr(out),
+                                          dev.index if dev.index is not None else torch.cuda.current_device(),
+                                          C.c_void_p(run.cuda_stream)))
+    return out
+
+
 def spheres_array(spheres):
     """list of dicts/tuples -> ctypes array of vmx_sphere"""
     arr = (L.Sphere * len(spheres))()
@@ -700,18 +746,22 @@ class Temporal:
     def __exit__(self, *a):
         self.close()
 
-    def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None):
+    def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None, motion=None):
         """vmx_temporal_accumulate_device: one frame.  `cam` is that frame's camera (make_camera), `raw` its G-buffer —
         the ["raw"] tensor of Scene.raycast_camera(cam, opts, 0), float32 [height, width, 16] — and `rgbaz` the float32
         [height, width, 5] frame.  The accumulated frame goes to `out` (same shape; may be `rgbaz` itself) and / or
         `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is made.  `history` (float32 [height, width])
         receives each pixel's history length.  All are contiguous torch tensors on the handle's device: anything else is
         a ValueError, never a copy through the host.  params: make_temporal_params(...), default the library's.
+        `motion` (vmx_temporal_accumulate_motion_device): what motion_vectors made of `raw` after a geometry update,
+        float32 [height, width, 8], read only — moved surfaces then keep their history; None is the call without.
         Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
         import torch
         dev = torch.device("cuda", self.device)
         _frame_tensor(raw, "raw", torch.float32, self.shape + (16,), dev)
         _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if motion is not None:
+            _frame_tensor(motion, "motion", torch.float32, self.shape + (8,), dev)
         if out is None and rgba8 is None:
             out = torch.empty_like(rgbaz)
         if out is not None:
@@ -722,10 +772,14 @@ class Temporal:
             _frame_tensor(history, "history", torch.float32, self.shape, dev)
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
         with _SideStream(dev, stream) as run:
-            self._check(self._lib.vmx_temporal_accumulate_device(self._h, C.byref(cam), ptr(raw), ptr(rgbaz), ptr(out),
-                                                                 ptr(rgba8), ptr(history),
-                                                                 None if params is None else C.byref(params),
-                                                                 C.c_void_p(run.cuda_stream)))
+            prm, s = None if params is None else C.byref(params), C.c_void_p(run.cuda_stream)
+            if motion is None:
+                self._check(self._lib.vmx_temporal_accumulate_device(self._h, C.byref(cam), ptr(raw), ptr(rgbaz), ptr(out),
+                                                                     ptr(rgba8), ptr(history), prm, s))
+            else:
+                self._check(self._lib.vmx_temporal_accumulate_motion_device(self._h, C.byref(cam), ptr(raw), ptr(motion),
+                                                                            ptr(rgbaz), ptr(out), ptr(rgba8), ptr(history),
+                                                                            prm, s))
         return out, rgba8
 
     def reset(self, stream=None):
@@ -838,6 +892,11 @@ RAYHIT_DTYPE = np.dtype([
     ("pad", np.uint32),
 ])
 assert RAYHIT_DTYPE.itemsize == 64
+
+MOTION_DTYPE = np.dtype([
+    ("prev_location", np.float32, 3), ("flags", np.uint32), ("prev_normal", np.float32, 3), ("pad", np.uint32),
+])
+assert MOTION_DTYPE.itemsize == 32
 
 
 def local_rows(height, stripe_rows, rank, world):
