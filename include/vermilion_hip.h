@@ -123,7 +123,8 @@ typedef struct vmx_opts {
                                    (instrumented kernels, slower; for roofline accounting) */
     uint32_t reserved[7];  /* 0 unless tuning: [0] pipeline form (bits 0-7: 0 default routing, 1 fused kernel for every
                               pass, 4 split wavefront for every pass; bit 8: plain one-phase shading; bit 9: two-phase
-                              shading through k_shade_ends instead of rays sorted by the traversal kernel),
+                              shading through k_shade_ends instead of rays sorted by the traversal kernel; bit 11: no
+                              per-pixel claims for the camera rays),
                               [1] max paths per pass, [2] tail threshold, [3] refill_min, [4] shade_min,
                               [5] bounce reordering key (A/B library only), [6] LDS stack levels — all forms and
                               settings produce the same frame (see api_render.inc: render_impl, make_tuning) */
@@ -166,7 +167,7 @@ typedef struct vmx_stats {
 #define VMX_K_FUSED 6         /* k_paths<0>: whole small passes in one fused kernel        */
 #define VMX_K_RESOLVE 7       /* k_resolve                                                 */
 #define VMX_K_BRUTEFORCE 8    /* k_bruteforce                                              */
-#define VMX_K_OTHER 9         /* first-generation kernels (pipeline forms 2, 3)            */
+#define VMX_K_OTHER 9         /* k_pixel_claims; first-generation kernels (pipeline forms 2, 3) */
 #define VMX_K_COUNT 10
 typedef struct vmx_timings {
     double ms[VMX_K_COUNT];          /* summed over the launches of the call */
@@ -375,6 +376,13 @@ int vmx_raycast_camera_device(const vmx_scene *scene, const vmx_camera *cam, con
  */
 int vmx_primary_ids(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t k,
                     int32_t *tri_id, float *t);
+
+/* Debug entry: the per-pixel claims a render of this camera would use for its camera rays (one 32-bit word per pixel of
+ * this rank's rows, packed as vmx_render packs them): 0xFFFFFFFF none, 0xFFFFFFFE "no camera ray of the pixel hits a
+ * triangle", else the leaf-order slot (vmx_scene_bvh's prim_order index) of the one triangle every camera ray of the
+ * pixel hits.  Built whatever the sample count; *n_claimed = pixels with a claim.  Either output may be NULL. */
+int vmx_pixel_claims(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                     uint32_t *n_claimed);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

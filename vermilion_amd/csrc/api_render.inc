@@ -248,7 +248,7 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     //   4 split wavefront for every pass (form 0 hands passes of fewer than 4 M paths to form 1's
     //     kernel, which needs no per-generation host round trip)
     const uint32_t pipeline = job.pipeline = opts->reserved[0] & 0xFFu;  // (bit 8: one-phase shading, see two_phase below)
-    if (pipeline > 4 || (opts->reserved[0] & ~0x7FFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");
+    if (pipeline > 4 || (opts->reserved[0] & ~0xFFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims)
     if ((rc = ab_check_forms(sc, pipeline))) return rc;
     if ((rc = ab_check_pool(opts))) return rc;  // (reserved[0] bit 10)
     const bool split_any = job.split_any = pipeline == 0 || pipeline == 4;
@@ -340,6 +340,11 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
         job.tbb = ab_bounce_blocks(job.tbb);
     }
     job.elide = split_any && fr.elide_dead;  // camera paths of the split passes: compacted live list
+    // per-pixel claims (pixel_claim.h) for the camera rays of the split passes, unless reserved[0] bit 11 switches them off.
+    // Not in the counting build (it traces every ray: its totals are the oracle's) nor on the live list of ELIDE_DEAD;
+    // form 0 runs its first pass split only from kHybridPaths path slots on.
+    job.claims_on = split_any && !count && !job.elide && !(opts->reserved[0] & 0x800u) &&
+                    (pipeline == 4 || (uint64_t)job.n_pad_max * smax >= kHybridPaths);
     job.live_words_max = ((size_t)job.n_pad_max * smax + 63) / 64;
     if (job.elide) job.live_tmp_bytes = live_compact_tmp_bytes((uint32_t)job.live_words_max);
     if (pixels->ensure(npix)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the per-pixel state");
@@ -364,7 +369,39 @@ int render_init_pixels(vmx_scene *sc, RenderJob &job) {
 }
 
 // the scene's workspace, sized for this job's passes and bound to it; the camera-relative tables of its origin
-int render_bind(vmx_scene *sc, RenderJob &job) {
+// Claims pay from this many samples per pixel on: below it a run builds none.  Measured on the 1080p headline frame,
+// claims on against off (profiles/pixel_claims.txt section 6): +1.17 ms at 16 samples, +0.11 at 32, -2.21 at 64, -5.99 at
+// 128 — 64 is the smallest of the swept values at which claims are not slower.
+constexpr uint32_t kClaimMinSamples = 64;
+uint32_t claim_min_samples() {
+#ifdef VMX_AB_KERNELS  // A/B library only: VMX_CLAIM_MIN_SPP overrides the threshold (tools/claim_sweep.py measures below it)
+    if (const char *e = std::getenv("VMX_CLAIM_MIN_SPP")) {
+        const unsigned long v = std::strtoul(e, nullptr, 10);
+        if (v) return (uint32_t)std::min<unsigned long>(v, 0xFFFFFFFFul);
+    }
+#endif
+    return kClaimMinSamples;
+}
+
+// the per-pixel claims of the frame `fr` from the camera tables in the workspace, into ws.claims[0, npix) and the number
+// of claimed pixels into ws.claims[npix]
+int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t npix, hipStream_t s) {
+    Workspace &ws = sc->ws;
+    if (ws.claims.ensure((size_t)npix + 1)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the pixel claims");
+    WorkDev wk;
+    std::memset(&wk, 0, sizeof(wk));
+    wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
+    const uint32_t tiles = ((fr.width + 7u) / 8u) * ((fr.local_rows + 7u) / 8u);
+    LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)tiles * 64, 8);
+    int rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)tiles * 64, wk);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ws.claims.p + npix, 0, 4, s));
+    LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, ws.claims.p + npix, cfg, s));
+    return VMX_OK;
+}
+
+// run_samples: the most samples a pixel takes in this run (0: the rest of the frame)
+int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
     Workspace &ws = sc->ws;
     const FrameDev &fr = job.fr;
     const Tuning &tn = job.tn;
@@ -418,6 +455,23 @@ int render_bind(vmx_scene *sc, RenderJob &job) {
         LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p,
                                         ws.cam_inner.p + n_inner * 64 * 8, s));
         job.launches++;
+    }
+    // the claims follow the camera tables: built with them for every run (the workspace is shared, and geometry may have
+    // been updated since a progressive handle's last step), reused by all its passes — when the run's samples per pixel
+    // pay for them (an early-stop frame: what most pixels take, the samples before the rule can fire and the first one
+    // of every later stratum)
+    job.claims = nullptr;
+    if (job.claims_on) {
+        uint32_t expect = fr.early_stop ? std::min(fr.kmax, fr.nmin + 1 + (fr.quarter ? fr.kmax / fr.quarter - 1u : 0u)) : fr.kmax;
+        if (run_samples) expect = std::min(expect, run_samples);
+        if (expect >= claim_min_samples()) {
+            int rc = timed_begin(ws, job.timed, s, -1, VMX_K_OTHER);
+            if (rc) return rc;
+            if ((rc = build_claims(sc, fr, tn, job.npix, s))) return rc;
+            if ((rc = timed_end(job.timed, s))) return rc;
+            job.claims = ws.claims.p;
+            job.launches++;
+        }
     }
     return VMX_OK;
 }
@@ -505,6 +559,7 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     if (split) {
         wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
         wk.cam_n_inner = sc->n_inner;
+        wk.claims = job.claims;
         LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)n_pad * S, job.tb);
         rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)n_pad * S, wk);
         if (rc) return rc;
@@ -594,7 +649,7 @@ int render_run(vmx_scene *sc, RenderJob &job, uint32_t samples, vmx_stats *stats
     hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
     if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(ev0, s));
-    if ((rc = render_bind(sc, job))) return rc;
+    if ((rc = render_bind(sc, job, samples))) return rc;
     HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
     if (!job.initialised && (rc = render_init_pixels(sc, job))) return rc;
     uint32_t left = samples ? samples : 0xFFFFFFFFu;
@@ -726,6 +781,31 @@ int vmx_render(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts
     rc = render_impl(sc, cam, opts, sc->ws.out.p, sc->stream, stats);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_rgbaz, sc->ws.out.p, nfloats * 4, hipMemcpyDeviceToHost));
+    return VMX_OK;
+}
+
+int vmx_pixel_claims(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                     uint32_t *n_claimed) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !cam || !opts) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    FrameDev fr;
+    if ((rc = make_frame(*cam, *opts, fr))) return rc;
+    const uint32_t npix = fr.width * fr.local_rows;
+    if (n_claimed) *n_claimed = 0;
+    if (npix == 0) return VMX_OK;
+    Workspace &ws = sc->ws;
+    hipStream_t s = sc->stream;
+    if ((rc = sc->upd.done.wait(s))) return rc;
+    const size_t n_inner = std::max<size_t>(sc->n_inner, 1);
+    if (ws.cam_inner.ensure(n_inner * 64 * 8 + (size_t)sc->ntris * 64)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the camera tables");
+    LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p, ws.cam_inner.p + n_inner * 64 * 8, s));
+    if ((rc = build_claims(sc, fr, make_tuning(sc, opts), npix, s))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (claims_out) HIP_TRY(hipMemcpy(claims_out, ws.claims.p, (size_t)npix * 4, hipMemcpyDeviceToHost));
+    if (n_claimed) HIP_TRY(hipMemcpy(n_claimed, ws.claims.p + npix, 4, hipMemcpyDeviceToHost));
     return VMX_OK;
 }
 

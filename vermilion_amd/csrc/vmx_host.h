@@ -140,6 +140,7 @@ struct Workspace {
     DevBuf<unsigned int> sort_keys[2], ids_sorted;      // bounce reordering (path_sort.hip)
     DevBuf<unsigned char> sort_tmp;
     DevBuf<unsigned char> cam_inner;                    // per-frame camera-relative scene tables: 8 node copies, then the triangles
+    DevBuf<unsigned int> claims;                        // per-pixel claims of the run's frame (pixel_claim.h) + the number of claimed pixels
     DevBuf<unsigned char> rad;          // float4 per path of a pass
     DevBuf<unsigned long long> rad_mask;  // split pipeline: one bit per path, "its radiance was stored" (PathArrays::rad_mask)
     // VMX_SAMPLING_ELIDE_DEAD: live bits per 64 paths; [popcounts | their exclusive scan | list length]; the list; scan scratch
@@ -413,6 +414,7 @@ struct RenderJob {
     Tuning tn;
     uint32_t npix = 0, pipeline = 0;
     bool count = false, split_any = false, legacy = false, elide = false;
+    bool claims_on = false;  // split passes may use per-pixel claims (pixel_claim.h): not counting, not eliding, reserved[0] bit 11 clear
     uint32_t smax = 0, smax_alloc = 0;  // samples per pixel and pass: the most a pass takes / what the buffers are sized for
     uint32_t n_pad_max = 0, sub_cap = 0;
     uint64_t mem_budget = 0;
@@ -426,6 +428,7 @@ struct RenderJob {
     PathArrays pa{};
     IdQueue qi[3];
     QueueDev q[2];  // first-generation kernels (A/B library) only
+    const unsigned int *claims = nullptr;  // this run's claim table, or NULL: none was built (render_bind)
     // the schedule's state between passes
     bool initialised = false;  // the tile-ordered pixel list is uploaded and the per-pixel state zeroed
     uint32_t n_active = 0;

@@ -92,6 +92,9 @@ struct WorkDev {
     const void *cam_inner;  // float4[8 * n_inner * 4]: one copy per direction octant, octant 0 = plain (lo, hi)
     uint32_t cam_n_inner;   // records per copy
     const void *cam_tris;   // float4[ntris * 4]
+    // camera rays: one claim word per local pixel (pixel_claim.h; k_pixel_claims) or NULL: a claimed pixel's rays take
+    // one triangle test in k_trace_w<0> instead of the BVH walk
+    const unsigned int *claims;
 };
 
 // explicit ray batch of k_query (vmx_query.inc): device pointers, any output may be NULL
@@ -183,6 +186,10 @@ int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, in
 // split wavefront: persistent trace kernel (per-lane refill) ...
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
                          void *cam_tris, void *stream);
+// the per-pixel claims of a frame (pixel_claim.h) from the camera tables in wk: claims[local pixel], *n_claimed += the
+// pixels with a slot or a miss claim; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
+int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *n_claimed,
+                        LaunchCfg cfg, void *stream);
 int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
 int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
 size_t live_compact_tmp_bytes(uint32_t nwords);

@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include "vmx_kernels.h"
+#include "pixel_claim.h"
 #include <type_traits>
 
 #ifndef VMX_CAM_BATCH
@@ -1715,6 +1716,51 @@ __global__ void k_camera_tables(SceneDev sc, uint32_t n_inner, float ox, float o
 }
 
 // ---------------------------------------------------------------------------
+// k_pixel_claims — the per-pixel claim of pixel_claim.h for every local pixel of a frame, from the camera tables of
+// its origin: one lane per pixel, a wave per 8 x 8 tile (neighbouring pixels walk the same nodes), the stack in LDS
+// levels plus the global slab as in k_bruteforce.  The walk itself is the header's, shared with the host program of
+// tests/cpp/pixel_claim_test.cpp: same arithmetic, same table.
+// ---------------------------------------------------------------------------
+struct ClaimStack {
+    uint2 *stk, *ovf;
+    int lds_entries;
+    __device__ __forceinline__ void put(int i, uint32_t ref, float near) { stack_push(stk, ovf, lds_entries, i, make_uint2(ref, __float_as_uint(near))); }
+    __device__ __forceinline__ void get(int i, uint32_t &ref, float &near) const {
+        const uint2 e = stack_pop(stk, ovf, lds_entries, i);
+        ref = e.x, near = __uint_as_float(e.y);
+    }
+};
+__global__ void __launch_bounds__(256)
+k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, const float *__restrict__ cam_tris,
+               unsigned int *__restrict__ claims, unsigned int *n_claimed, uint32_t lds_levels, uint32_t overflow_entries,
+               void *overflow_stack) {
+    extern __shared__ uint2 lds_stack[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    ClaimStack stk;
+    stk.stk = lds_stack + (size_t)wave * (lds_levels + 1) * 64 + lane;
+    stk.ovf = (uint2 *)overflow_stack + ((size_t)(blockIdx.x * (blockDim.x >> 6) + wave) * overflow_entries) * 64 + lane;
+    stk.lds_entries = (int)lds_levels;
+    PcFilm fm;
+    for (int i = 0; i < 9; ++i) fm.m[i] = fr.m[i];
+    fm.width = fr.width, fm.height = fr.height, fm.sensor_x = fr.sensor_x, fm.sensor_y = fr.sensor_y, fm.film_dist = fr.film_dist;
+    const uint32_t tiles_x = (fr.width + 7u) / 8u, tiles = tiles_x * ((fr.local_rows + 7u) / 8u);
+    uint32_t n = 0;
+    for (uint32_t tile = blockIdx.x * (blockDim.x >> 6) + wave; tile < tiles; tile += gridDim.x * (blockDim.x >> 6)) {
+        const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+        if (x < fr.width && y < fr.local_rows) {
+            const uint32_t lp = y * fr.width + x;
+            const uint32_t c = pc_pixel_claim(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk,
+                                              (int)(lds_levels + overflow_entries));
+            claims[lp] = c;
+            n += c != kClaimNone ? 1u : 0u;
+        }
+    }
+    n = wave_sum(n);
+    if (lane == 0 && n) atomicAdd(n_claimed, n);
+}
+
+// ---------------------------------------------------------------------------
 // k_raygen — camera rays of one pass (pathtracer.cpp:251-280), written to rayA[pid] as
 // (direction, flag word): all camera rays share the frame's origin, so 16 bytes per ray suffice.
 // Slots without a sample (past the pixel's last one, padding) get the word ~0 and are skipped downstream;
@@ -2551,6 +2597,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                 res_lo = __builtin_amdgcn_readfirstlane(res_lo + min((uint32_t)__popcll(want), avail));
                 if (take) {
                     bool valid = true;
+                    uint32_t claim = kClaimNone;  // (camera rays: the pixel's claim, pixel_claim.h)
                     if (LIVE) {
                         pid = src * live_band(*wk.live_count) + item;  // list position
                     } else if (SRC == 0) {
@@ -2563,6 +2610,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         }
                         valid = s_idx < wk.n_active;
                         pid = path_id(wk, j, s_idx);
+                        if (wk.claims && valid) claim = wk.claims[wk.active[s_idx]];
                     } else {
                         pid = wk.qids.ids[(size_t)src * wk.qids.sub_capacity + item];
                     }
@@ -2579,10 +2627,27 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                             if (SORT && valid) rflags = __float_as_uint(b.w) & 7u;  // k_shade: step_bits of this step
                         }
                     }
+                    if (SRC == 0 && !LIVE && valid && claim != kClaimNone) {
+                        // the pixel's claim settles this ray's BVH query: the claimed triangle's own test (the t the walk
+                        // would have found, bit for bit), or no hit; the lane stays idle and takes the next item
+                        best = 999999999.f, slot = -1;
+                        if (claim != kClaimMiss) {
+                            const float4 a = tris[claim * 4], b = tris[claim * 4 + 1], c = tris[claim * 4 + 2];
+                            const float cd = ((const float *)tris)[claim * 16 + 12];
+                            float dist;
+                            if (tri_test_cam(a, b, c, cd, dx, dy, dz, dist) && dist < best) best = dist, slot = (int)claim;
+                        }
+                        if (SORT) rflags |= 0x80000000u;  // settled below, before the lane takes another item
+                        else hit_out[pid] = make_float2(best, __int_as_float(slot));
+                        valid = false;
+                    }
                     if (valid) {
                         ray_start(dx, dy, dz, root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
                         exact = !(finite3(ix, iy, iz) && finite3(ox, oy, oz));
                     }
+                }
+                if (SRC == 0 && !LIVE && SORT && wk.claims) {
+                    if (__builtin_amdgcn_ballot_w64((rflags >> 31) != 0) != 0) sort_finished();
                 }
             }
         }
@@ -3597,6 +3662,14 @@ int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pix
     if (grid == 0) grid = 1;
     if (wk.live_mask) hipLaunchKernelGGL(k_raygen<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
     else hipLaunchKernelGGL(k_raygen<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
+    return launch_status();
+}
+
+int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *n_claimed,
+                        LaunchCfg cfg, void *stream) {
+    hipLaunchKernelGGL(k_pixel_claims, dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, (hipStream_t)stream, sc, fr,
+                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, claims, n_claimed, wk.lds_entries, wk.overflow_entries,
+                       wk.overflow_stack);
     return launch_status();
 }
 
