@@ -15,7 +15,7 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough [--moving] fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] [--textured] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
@@ -28,6 +28,12 @@
 //   vmx_temporal_accumulate_motion_device   the history looked up where the surface was: the block keeps its own
 //   vmx_filter_set_guide_device + vmx_filter_apply_device
 // A second accumulator takes the same frames without the motion records; the mean history length of both is printed.
+//
+// --textured: a procedural checker is bound (vmx_scene_bind_texture), and the filter step becomes
+//   vmx_albedo_camera_device             the frame's albedo plane: 4 samples of what the integrator multiplies by
+//   vmx_filter_apply_demodulated_device  the filter on colour / albedo, the albedo multiplied back
+// The accumulator is untouched: reprojection follows surface points, so textured history is valid.  fly_plain.ppm is
+// the same accumulated frame through vmx_filter_apply_device, where the checker on the flat walls is averaged away.
 #include <dlfcn.h>
 
 #include <cmath>
@@ -90,8 +96,15 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 }  // namespace
 
 int main(int argc, char **argv) {
-    const bool moving = argc > 1 && std::strcmp(argv[1], "--moving") == 0;
-    if (moving) --argc, ++argv;
+    bool moving = false, textured = false;
+    for (; argc > 1 && std::strncmp(argv[1], "--", 2) == 0; --argc, ++argv) {
+        if (std::strcmp(argv[1], "--moving") == 0) moving = true;
+        else if (std::strcmp(argv[1], "--textured") == 0) textured = true;
+        else {
+            std::fprintf(stderr, "flythrough: unknown option %s\n", argv[1]);
+            return 1;
+        }
+    }
     const std::string out = argc > 1 ? argv[1] : "fly";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 8;
@@ -114,6 +127,21 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "scene: %s\n", vmx_last_error());
         return 1;
     }
+    if (textured) {
+        // 64 x 64 x 3: 8-texel checks in red and green, 4-texel stripes in blue
+        std::vector<float> tex(64 * 64 * 3);
+        for (uint32_t y = 0; y < 64; ++y)
+            for (uint32_t x = 0; x < 64; ++x) {
+                const float chk = (float)((x / 8 + y / 8) & 1u);
+                float *t = &tex[(y * 64 + x) * 3];
+                t[0] = 0.25f + 0.7f * chk, t[1] = 0.9f - 0.6f * chk, t[2] = 0.3f + 0.5f * (float)((x / 4) & 1u);
+            }
+        if (vmx_scene_bind_texture(scene, tex.data(), 64, 64, 3) != VMX_OK) {
+            std::fprintf(stderr, "texture: %s\n", vmx_last_error());
+            vmx_scene_destroy(scene);
+            return 1;
+        }
+    }
     Hip hip;
     if (!hip.load()) {
         std::fprintf(stderr, "the HIP runtime's entries were not found\n");
@@ -128,6 +156,7 @@ int main(int argc, char **argv) {
     const uint32_t ntris = (uint32_t)(pos.size() / 9);
     vmx_temporal *plain = nullptr;
     void *d_pos[2] = {nullptr, nullptr}, *d_motion = nullptr, *d_acc_plain = nullptr, *d_hist_plain = nullptr;
+    void *d_albedo = nullptr;  // --textured: the frame's albedo plane, float4 per pixel
     std::vector<float> moved = pos, hist_plain(moving ? (size_t)W * H : 0);
     std::vector<unsigned char> rgba(npix * 4);
     std::vector<float> hist(npix);
@@ -137,6 +166,7 @@ int main(int argc, char **argv) {
                   hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, npix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
     if (hip_ok) rc = vmx_temporal_create(0, W, H, &temporal);
     if (hip_ok && rc == VMX_OK) rc = vmx_filter_create(0, W, H, &filter);
+    if (textured && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_albedo, npix * 16) == 0;
     if (moving && hip_ok && rc == VMX_OK) {
         hip_ok = hip.malloc_(&d_pos[0], pos.size() * 4) == 0 && hip.malloc_(&d_pos[1], pos.size() * 4) == 0 &&
                  hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0 && hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
@@ -185,7 +215,20 @@ int main(int argc, char **argv) {
                                                            stream)) != VMX_OK)
             break;
         if ((rc = vmx_filter_set_guide_device(filter, d_rec, stream)) != VMX_OK) break;
-        if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+        if (textured) {
+            const uint32_t albedo_samples = spp < 8 ? 4 * (spp / 4) : 4;  // (at most the frame's own samples)
+            if ((rc = vmx_albedo_camera_device(scene, &cam, &opts, 0, albedo_samples, d_albedo, stream)) != VMX_OK) break;
+            if (i + 1 == frames) {  // the plain filter's picture of the same frame, for comparison
+                if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+                if (fetch(nullptr) && !write_ppm(out + "_plain.ppm", rgba, W, H)) {
+                    std::fprintf(stderr, "flythrough: cannot write %s_plain.ppm\n", out.c_str());
+                    io_ok = false;
+                }
+                if (!hip_ok) break;
+            }
+            if ((rc = vmx_filter_apply_demodulated_device(filter, d_acc, d_albedo, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+        } else if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK)
+            break;
         if (!(hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(hist.data(), d_hist, npix * 4, 2) == 0)) break;
         double mean = 0;
         for (float n : hist) mean += n;
@@ -214,7 +257,7 @@ int main(int argc, char **argv) {
     if (filter) vmx_filter_destroy(filter);
     if (temporal) vmx_temporal_destroy(temporal);
     if (plain) vmx_temporal_destroy(plain);
-    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain})
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo})
         if (p) hip.free_(p);
     if (stream) hip.stream_destroy(stream);
     vmx_scene_destroy(scene);

@@ -516,6 +516,60 @@ int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, v
 int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8,
                                      const vmx_filter_params *params);
 
+/* ---- albedo-demodulated denoising: textured surfaces keep their texture ------------------------------
+ * With a bound texture (vmx_scene_bind_texture) the integrator multiplies a path's throughput by the texel at every
+ * diffuse triangle hit (pathtracer.cpp:63-66).  A texture on a flat wall has no edge in the filter's guide, so the
+ * filter above averages it away with the noise.  The remedy is to filter colour / albedo and multiply the albedo back:
+ * a per-pixel albedo plane, and a filter call that divides by it on the way in and multiplies by it on the way out.
+ * It pays on resolved textures on surfaces wider than the filter's footprint; on thin geometry with a minified texture
+ * it is no better than the plain call.
+ *
+ * The albedo plane.  d_albedo holds W*H float4 in pixel order, 16-byte aligned, DEVICE memory of the scene's device.
+ * cam / opts are checked exactly as vmx_raycast_camera_device checks them (only opts->seed is used; opts->world > 1 is
+ * VMX_ERR_INVALID); nsamples >= 1 and first_sample + nsamples <= 4 * (rays_per_pixel / 4).  Per pixel p, in float, one
+ * rounding per written operation:
+ *   sum = (0, 0, 0), cnt = 0
+ *   for k = first_sample .. first_sample + nsamples - 1, ascending:
+ *     r = the MeshEngine::RayCast record of sample k's camera ray — what vmx_raycast_camera_device(.., k, ..) writes for p
+ *     mat = (r.flags & 2) != 0
+ *     t = mat ? VermiTexture::Sample(r.uv).xyz : (1, 1, 1)   texture 0 as the integrator samples it (meshEngine.cpp:21-46:
+ *         wrap x - floor(x), nearest round(x * (W - 1)), 1-4 channels — one channel is (v, v, v), two are (a, b, 0) —
+ *         the texel index clamped), with the reference's stale uv and a material hit hidden behind a nearer sphere,
+ *         because that is what the integrator multiplies by; a scene with no bound texture gives t = (1, 1, 1)
+ *         (pathtracer.cpp:75-79)
+ *     sum. = sum. + t.;  cnt += mat
+ *   out = (sum.x / (float)n, sum.y / (float)n, sum.z / (float)n, (float)cnt / (float)n),  n = nsamples
+ * Enqueued on `stream` (NULL = the scene's stream), no synchronisation; ordered with the scene's queries and updates as
+ * vmx_raycast_camera_device is (same workspace, same event).  Its scratch (64 bytes per pixel) is allocated on first
+ * use and then reused.  Served by the camera-ray query of the G-buffer path and a dense finish kernel that computes
+ * only uv and the material bit, samples the texture and accumulates: no 64-byte record per sample leaves the library. */
+#define VMX_ALBEDO_FLOOR 0.0009765625f /* 2^-10 */
+int vmx_albedo_camera_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts,
+                             uint32_t first_sample, uint32_t nsamples, void *d_albedo, void *stream);
+/* vmx_filter_apply_device with demodulation: the same rules for arguments, order of checks, overlaps, in place, guide
+ * and stream ordering.  In addition d_albedo (W*H float4, what vmx_albedo_camera_device writes; .w is not read) is read
+ * only, non-NULL, 16-byte aligned, DEVICE memory of the filter's device, and may overlap no written buffer.  Per pixel
+ * q and channel:
+ *   am_q. = (a_q. > VMX_ALBEDO_FLOOR && a_q. <= 3.402823466e+38f) ? a_q. : VMX_ALBEDO_FLOOR
+ *           (NaN, zero, negative and infinite albedo all take the floor)
+ *   the first iteration's input colour of every pixel q, centre and taps:  c_q. = frame_q. / am_q.
+ *   the last iteration's result:  out. = o. * am_p.,  o what the restatement above would have written, fallback included
+ * and everything between is that restatement unchanged.  Alpha and depth pass through bitwise; rgba8 is computed from
+ * the multiplied result.  A dense pre-pass writes frame / albedo into the filter's plane, which the first iteration then
+ * reads (so an in-place single iteration needs no copy of the frame).  tests/demod_spec.py restates it. */
+int vmx_filter_apply_demodulated_device(vmx_filter *f, const void *d_in_rgbaz, const void *d_albedo,
+                                        void *d_out_rgbaz, void *d_rgba8, const vmx_filter_params *params,
+                                        void *stream);
+/* The filtered previews with the demodulated call's arithmetic.  The handle builds its albedo plane once, on its first
+ * demodulated preview, from its own camera and seed — samples 0 .. albedo_samples - 1, albedo_samples in
+ * 1 .. 4 * (rays_per_pixel / 4) — under the guide's refusals (opts->world > 1, scene updated since begin); a later call
+ * with a different albedo_samples builds it again.  The plane is freed by vmx_progressive_end.  A demodulated preview
+ * never changes the handle's render state. */
+int vmx_progressive_preview_demodulated_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8,
+                                               const vmx_filter_params *params, uint32_t albedo_samples);
+int vmx_progressive_preview_demodulated(vmx_progressive *p, float *rgbaz, unsigned char *rgba8,
+                                        const vmx_filter_params *params, uint32_t albedo_samples);
+
 /* ---- temporal accumulation: frames over time, across camera moves -------------------------------------
  * A few-sample frame per camera position flickers, although nearly every surface it shows was sampled a frame
  * earlier.  A vmx_temporal handle keeps an accumulated frame and reprojects it into each new camera through that

@@ -33,6 +33,7 @@ VMX_QUERY_NEAREST = 0
 VMX_QUERY_ANY = 1
 VMX_QUERY_COLLISION = 2
 VMX_QUERY_FETCH_PER_LANE = 0x100
+VMX_ALBEDO_FLOOR = 2.0 ** -10  # the demodulated filter's lower clamp of an albedo channel
 VMX_UPDATE_REFIT = 0
 VMX_UPDATE_REBUILD = 1
 
@@ -255,6 +256,10 @@ SYMBOLS = {
     "vmx_filter_apply_device": (C.c_int, [_P, _P, _P, _P, C.POINTER(FilterParams), _P]),
     "vmx_progressive_preview_filtered_device": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
     "vmx_progressive_preview_filtered": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams)]),
+    "vmx_albedo_camera_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, C.c_uint32, _P, _P]),
+    "vmx_filter_apply_demodulated_device": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(FilterParams), _P]),
+    "vmx_progressive_preview_demodulated_device": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams), C.c_uint32]),
+    "vmx_progressive_preview_demodulated": (C.c_int, [_P, _P, _P, C.POINTER(FilterParams), C.c_uint32]),
     "vmx_temporal_default_params": (C.c_int, [C.POINTER(TemporalParams)]),
     "vmx_temporal_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "vmx_temporal_destroy": (C.c_int, [_P]),

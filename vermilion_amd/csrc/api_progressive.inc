@@ -11,6 +11,8 @@ struct VMX_OPAQUE vmx_progressive {
     DevBuf<unsigned char> host_rgba8;
     vmx_camera cam;                 // as begun: the filtered previews' guide is sample 0's camera ray of every pixel
     std::unique_ptr<vmx_filter> filter;  // vmx_progressive_preview_filtered*: created, and its guide built, on first use
+    DevBuf<unsigned char> albedo;   // vmx_progressive_preview_demodulated*: the albedo plane (float4 per pixel) of samples
+    uint32_t albedo_samples = 0;    // 0 .. albedo_samples - 1, built on first use (0: none yet)
     uint64_t generation = 0;        // the scene's when the handle began
     uint64_t samples = 0, passes = 0, steps = 0;
     bool failed = false;            // a step stopped half way: the schedule and the device state may disagree
@@ -146,21 +148,44 @@ static int progressive_filter_ensure(vmx_progressive *p) {
     return VMX_OK;
 }
 
-static int progressive_filter_enqueue(vmx_progressive *p, float *d_rgbaz, void *d_rgba8, const vmx_filter_params &prm) {
+// the handle's albedo plane: built on the first demodulated preview, and again when `samples` changes, from the handle's
+// own camera and seed on its stream — under the guide's refusals
+static int progressive_albedo_ensure(vmx_progressive *p, uint32_t samples) {
+    if (p->albedo_samples == samples) return VMX_OK;
+    vmx_scene *sc = p->sc;
+    if (p->job.opts.world > 1) return fail(VMX_ERR_INVALID, "world > 1: a demodulated preview needs the camera's albedo plane (whole images only)");
+    if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
+    FrameDev fr;
+    if (int rc = make_frame(p->cam, p->job.opts, fr)) return rc;
+    if (p->albedo.ensure((size_t)fr.width * fr.height * 16)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the albedo plane");
+    p->albedo_samples = 0;
+    if (int rc = albedo_enqueue(sc, fr, 0, samples, p->albedo.p, p->job.s)) return rc;
+    p->albedo_samples = samples;
+    return VMX_OK;
+}
+
+// albedo_samples == 0: the plain filtered preview
+static int progressive_filter_enqueue(vmx_progressive *p, float *d_rgbaz, void *d_rgba8, const vmx_filter_params &prm,
+                                      uint32_t albedo_samples = 0) {
     if (int rc = progressive_filter_ensure(p)) return rc;
+    if (albedo_samples)
+        if (int rc = progressive_albedo_ensure(p, albedo_samples)) return rc;
     FilterSrc src{};
     src.px = PixelStateDev{p->pixels.accum.p, p->pixels.count.p, p->pixels.cursor.p};
     src.finished = p->frame.p;
     src.kmax = p->job.fr.kmax;
     std::lock_guard<std::mutex> lock(p->filter->mu);
-    return filter_enqueue(p->filter.get(), src, d_rgbaz, d_rgba8, prm, p->job.s);
+    return filter_enqueue(p->filter.get(), src, d_rgbaz, d_rgba8, prm, p->job.s, albedo_samples ? p->albedo.p : nullptr);
 }
 
-int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8, const vmx_filter_params *params) {
+// demod: vmx_progressive_preview_demodulated_device, whose albedo_samples must be 1 .. kmax
+static int progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8, const vmx_filter_params *params,
+                                               bool demod, uint32_t albedo_samples) {
     vmx_filter_params prm;
     if (int rc = filter_params(params, prm)) return rc;
     if (int rc = preview_args(p, d_rgbaz, d_rgba8)) return rc;
     if (((uintptr_t)d_rgbaz | (uintptr_t)d_rgba8) & 3u) return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 must be 4-byte aligned");
+    if (demod && (albedo_samples < 1 || albedo_samples > p->job.fr.kmax)) return fail(VMX_ERR_INVALID, "albedo_samples must be 1 .. 4 * (rays_per_pixel / 4)");
     vmx_scene *sc = p->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
     if (int rc = bind_device(sc)) return rc;
@@ -169,13 +194,24 @@ int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, v
         const uintptr_t a = (uintptr_t)d_rgbaz, b = (uintptr_t)d_rgba8, n = p->job.npix;
         if (a < b + n * 4 && b < a + n * 20) return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 overlap");
     }
-    return progressive_filter_enqueue(p, (float *)d_rgbaz, d_rgba8, prm);
+    return progressive_filter_enqueue(p, (float *)d_rgbaz, d_rgba8, prm, demod ? albedo_samples : 0);
 }
 
-int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8, const vmx_filter_params *params) {
+int vmx_progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8, const vmx_filter_params *params) {
+    return progressive_preview_filtered_device(p, d_rgbaz, d_rgba8, params, false, 0);
+}
+
+int vmx_progressive_preview_demodulated_device(vmx_progressive *p, void *d_rgbaz, void *d_rgba8, const vmx_filter_params *params,
+                                               uint32_t albedo_samples) {
+    return progressive_preview_filtered_device(p, d_rgbaz, d_rgba8, params, true, albedo_samples);
+}
+
+static int progressive_preview_filtered_host(vmx_progressive *p, float *rgbaz, unsigned char *rgba8, const vmx_filter_params *params,
+                                             bool demod, uint32_t albedo_samples) {
     vmx_filter_params prm;
     if (int rc = filter_params(params, prm)) return rc;
     if (int rc = preview_args(p, rgbaz, rgba8)) return rc;
+    if (demod && (albedo_samples < 1 || albedo_samples > p->job.fr.kmax)) return fail(VMX_ERR_INVALID, "albedo_samples must be 1 .. 4 * (rays_per_pixel / 4)");
     vmx_scene *sc = p->sc;
     std::lock_guard<std::mutex> lock(sc->mu);
     if (int rc = bind_device(sc)) return rc;
@@ -183,11 +219,21 @@ int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned 
     const size_t npix = job.npix;
     if ((rgbaz && p->host_rgbaz.ensure(npix * 5)) || (rgba8 && p->host_rgba8.ensure(npix * 4)))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the preview buffers");
-    if (int rc = progressive_filter_enqueue(p, rgbaz ? p->host_rgbaz.p : nullptr, rgba8 ? p->host_rgba8.p : nullptr, prm)) return rc;
+    if (int rc = progressive_filter_enqueue(p, rgbaz ? p->host_rgbaz.p : nullptr, rgba8 ? p->host_rgba8.p : nullptr, prm,
+                                            demod ? albedo_samples : 0)) return rc;
     if (rgbaz) HIP_TRY(hipMemcpyAsync(rgbaz, p->host_rgbaz.p, npix * 20, hipMemcpyDeviceToHost, job.s));
     if (rgba8) HIP_TRY(hipMemcpyAsync(rgba8, p->host_rgba8.p, npix * 4, hipMemcpyDeviceToHost, job.s));
     HIP_TRY(hipStreamSynchronize(job.s));
     return VMX_OK;
+}
+
+int vmx_progressive_preview_filtered(vmx_progressive *p, float *rgbaz, unsigned char *rgba8, const vmx_filter_params *params) {
+    return progressive_preview_filtered_host(p, rgbaz, rgba8, params, false, 0);
+}
+
+int vmx_progressive_preview_demodulated(vmx_progressive *p, float *rgbaz, unsigned char *rgba8, const vmx_filter_params *params,
+                                        uint32_t albedo_samples) {
+    return progressive_preview_filtered_host(p, rgbaz, rgba8, params, true, albedo_samples);
 }
 
 int vmx_progressive_end(vmx_progressive *p) {

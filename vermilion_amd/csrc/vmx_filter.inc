@@ -16,6 +16,14 @@
 //                   dword stores of consecutive lanes to consecutive addresses, as in k_preview; rgba8 from the same
 //                   values.  Else the result goes to the other float4 plane.
 //                   M: normal_squarings as a constant (the default, 5) or -1: read from the pass.
+//                   DEMOD (vmx_filter_apply_demodulated_device; LAST only): the result is multiplied by the pixel's own
+//                   albedo before it leaves, each channel clamped from below (filter_albedo).
+//   k_demod_divide  the demodulated call's pre-pass, one lane per pixel, dense: frame / albedo (or the pixel state as
+//                   k_preview shows it / albedo) into the float4 plane the first iteration then reads as IN = 0.  Measured
+//                   against dividing per tap inside the first iteration at 1920x1080 (profiles/demod_bench.txt): 436 us
+//                   against 477 for a five-iteration call on a frame, 119 against 299 for a single iteration, 441 against
+//                   1080 for a filtered preview — the per-tap forms of the first iteration need 300+ VGPRs.  The
+//                   existing instantiations are the instruction streams they were without the parameter.
 constexpr uint32_t kFilterBX = 32, kFilterBY = 8, kFilterBlock = kFilterBX * kFilterBY;
 
 __global__ void __launch_bounds__(256) k_filter_guide(const float4 *__restrict__ rayhit, uint32_t npix,
@@ -47,6 +55,15 @@ __device__ __forceinline__ void filter_src_pixel(const FilterSrc &s, uint32_t q,
     }
 }
 
+// pixel q's albedo as the demodulated filter divides and multiplies by it: VMX_ALBEDO_FLOOR unless above it and finite
+constexpr float kAlbedoFloor = 0.0009765625f;  // VMX_ALBEDO_FLOOR = 2^-10
+__device__ __forceinline__ void filter_albedo(const FilterPass &a, uint32_t q, float *am) {
+    const float4 v = ((const float4 *)a.albedo)[q];
+    am[0] = (v.x > kAlbedoFloor && v.x <= 3.402823466e+38f) ? v.x : kAlbedoFloor;
+    am[1] = (v.y > kAlbedoFloor && v.y <= 3.402823466e+38f) ? v.y : kAlbedoFloor;
+    am[2] = (v.z > kAlbedoFloor && v.z <= 3.402823466e+38f) ? v.z : kAlbedoFloor;
+}
+
 template <int IN>
 __device__ __forceinline__ void filter_colour(const FilterPass &a, uint32_t q, float *c) {
     if (IN == 0) {
@@ -59,8 +76,19 @@ __device__ __forceinline__ void filter_colour(const FilterPass &a, uint32_t q, f
     }
 }
 
-template <int IN, bool LAST, int M>
+template <bool STATE>
+__global__ void __launch_bounds__(256) k_demod_divide(FilterPass a, uint32_t npix) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    float v[5], am[3];
+    filter_src_pixel<STATE>(a.src, p, v);
+    filter_albedo(a, p, am);
+    ((float4 *)a.out_plane)[p] = make_float4(v[0] / am[0], v[1] / am[1], v[2] / am[2], 0.f);
+}
+
+template <int IN, bool LAST, int M, bool DEMOD = false>
 __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
+    static_assert(!DEMOD || (LAST && IN == 0), "demodulation: the pre-pass divides, the last iteration (from a plane) multiplies");
     __shared__ float s_px[LAST ? kFilterBlock * 5 : 1];
     const uint32_t W = a.width, H = a.height;
     // (a one-dimensional grid of blocks, row-major over the image: the second grid dimension ends at 65535)
@@ -120,6 +148,11 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
         o[0] = any ? sum0 / sumw : cp[0];
         o[1] = any ? sum1 / sumw : cp[1];
         o[2] = any ? sum2 / sumw : cp[2];
+        if (DEMOD && LAST) {
+            float am[3];
+            filter_albedo(a, p, am);
+            o[0] = o[0] * am[0], o[1] = o[1] * am[1], o[2] = o[2] * am[2];
+        }
     }
     if (!LAST) {
         if (live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], 0.f);
@@ -158,10 +191,31 @@ int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *st
 
 template <int IN, bool LAST>
 static void launch_atrous_m(const FilterPass &a, dim3 grid, hipStream_t s) {
+    // demodulation touches the iteration that writes the result (k_demod_divide wrote the plane the first one reads)
+    if constexpr (IN == 0 && LAST) {
+        if (a.albedo) {
+            if (a.squarings == 5)
+                hipLaunchKernelGGL((k_atrous<IN, LAST, 5, true>), grid, dim3(kFilterBlock), 0, s, a);
+            else
+                hipLaunchKernelGGL((k_atrous<IN, LAST, -1, true>), grid, dim3(kFilterBlock), 0, s, a);
+            return;
+        }
+    }
     if (a.squarings == 5)
         hipLaunchKernelGGL((k_atrous<IN, LAST, 5>), grid, dim3(kFilterBlock), 0, s, a);
     else
         hipLaunchKernelGGL((k_atrous<IN, LAST, -1>), grid, dim3(kFilterBlock), 0, s, a);
+}
+
+// the demodulated call's pre-pass: a.src / a.albedo into a.out_plane
+int launch_demod_divide(const FilterPass &a, void *stream) {
+    const uint32_t npix = a.width * a.height;
+    if (npix == 0) return 0;
+    if (a.src.frame)
+        hipLaunchKernelGGL(k_demod_divide<false>, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, npix);
+    else
+        hipLaunchKernelGGL(k_demod_divide<true>, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, npix);
+    return launch_status();
 }
 
 int launch_atrous(const FilterPass &a, void *stream) {

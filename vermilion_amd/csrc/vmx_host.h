@@ -207,6 +207,7 @@ struct vmx_scene {
         uint32_t grid[2][kQueryModes] = {};    // persistent blocks per [per-lane fetch][mode]: VMX_QUERY_* and the
                                                // raycast entries' kQueryCastRays / kQueryCastCamera
         uint32_t stack_entries = 0;            // the tree depth the slab was sized for (a REBUILD can change it)
+        DevBuf<unsigned char> albedo_rec;      // vmx_albedo_camera_device: 64 bytes per pixel for k_query's (tri_t, slot), on first use
     } qws;
     // in-place geometry updates (vmx_scene_update*): `done` is recorded after each update and waited on by every later
     // render, query and export of the scene, whatever its stream.  The refit plan is built on the first update that

@@ -243,9 +243,17 @@ struct FilterPass {  // one iteration
     float *out_rgbaz;      // the last iteration's outputs, either may be NULL
     void *rgba8;
     bool first, last;
+    const void *albedo;  // float4 (a.rgb, -) per pixel or NULL: the demodulated call (last, so that every other member is where it was)
 };
 int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *stream);
 int launch_atrous(const FilterPass &pass, void *stream);
+// the demodulated call's pre-pass: pass.src / pass.albedo into pass.out_plane, which the first iteration then reads as a plane
+int launch_demod_divide(const FilterPass &pass, void *stream);
+// the albedo plane of a camera (vmx_albedo.inc; the arithmetic is stated in include/vermilion_hip.h): sample q.sample
+// of a run of n — k_query<kQueryCastCamera> (per-lane fetch) with cfg into `rec` (64 bytes per pixel, q.n = W * H), then k_albedo_finish
+// into `plane` (float4 per pixel); first / last: of the run
+int launch_albedo_sample(const SceneDev &sc, const QueryDev &q, const FrameDev &fr, void *rec, bool first, bool last,
+                         uint32_t n, void *plane, LaunchCfg cfg, void *stream);
 // temporal accumulation (vmx_temporal.inc; the arithmetic is stated in include/vermilion_hip.h)
 struct TemporalCam {  // what proj reads of a FrameDev
     float m[9];       // m[col * 3 + row]

@@ -3860,6 +3860,9 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 // device ray queries of explicit batches: k_query<MODE> + launch_query
 #include "vmx_query.inc"
 
+// the albedo plane of a camera: k_query's camera mode + k_albedo_finish
+#include "vmx_albedo.inc"
+
 // in-place geometry updates: record rewrite and per-level refit
 #include "vmx_update.inc"
 

@@ -145,6 +145,15 @@ def _frame_tensor(x, name, dtype, shape, dev):
     return x
 
 
+def _albedo_tensor(x, name, shape, dev):
+    """an albedo plane as the ABI takes it (contiguous float32 [height, width, 4] on dev, 16-byte aligned), or a ValueError"""
+    import torch
+    _frame_tensor(x, name, torch.float32, tuple(shape) + (4,), dev)
+    if x.data_ptr() % 16:
+        raise ValueError(f"{name} must be 16-byte aligned")
+    return x
+
+
 def motion_vectors(raw, pos_now, pos_prev, nrm_prev=None, out=None, stream=None):
     """vmx_motion_device: the motion records of a G-buffer after a geometry update, for Temporal.accumulate(motion=...).
     `raw` is the ["raw"] tensor of Scene.raycast_camera on the updated scene (float32 [..., 16]); `pos_now` and `pos_prev`
@@ -349,6 +358,28 @@ class Scene:
                                                             C.c_void_p(raw.data_ptr()), flags,
                                                             C.c_void_p(run.cuda_stream)))
         return _rayhit_views(raw)
+
+    def albedo_camera(self, cam, opts, samples=4, first=0, out=None, stream=None):
+        """vmx_albedo_camera_device: the camera's albedo plane, float32 [H, W, 4] on this scene's device — per pixel the
+        mean over samples first .. first + samples - 1 of what the integrator multiplies a camera path's throughput by
+        at its first hit (the bound texture's texel, (1, 1, 1) off the mesh or without a texture), and in .w the
+        fraction of those rays that hit the mesh.  `out`: a contiguous, 16-byte aligned float32 [H, W, 4] tensor on
+        the scene's device to fill instead of a new one — anything else is a ValueError.  Computed on `stream`
+        (default torch.cuda.current_stream()), nothing synchronised."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        W, H = int(cam.image_res[0]), int(cam.image_res[1])
+        if int(samples) < 1:
+            raise ValueError("samples must be at least 1")
+        if int(first) < 0:
+            raise ValueError("first must not be negative")
+        if out is None:
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        _albedo_tensor(out, "out", (H, W), dev)
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_albedo_camera_device(self._h, C.byref(cam), C.byref(opts), int(first), int(samples),
+                                                           C.c_void_p(out.data_ptr()), C.c_void_p(run.cuda_stream)))
+        return out
 
     # -- ray queries -----------------------------------------------------------
     QUERY_MODES = {"nearest": L.VMX_QUERY_NEAREST, "any": L.VMX_QUERY_ANY, "collision": L.VMX_QUERY_COLLISION}
@@ -624,22 +655,34 @@ class Progressive:
         self._scene._check(self._lib.vmx_progressive_preview_device(self._h, ptr(rgbaz), ptr(rgba8)))
         return rgbaz, rgba8
 
-    def preview_filtered(self, rgba8=False, params=None):
+    def preview_filtered(self, rgba8=False, params=None, albedo_samples=None):
         """vmx_progressive_preview_filtered: `preview`'s frame pushed through the G-buffer-guided filter (guide: sample
         0's camera ray of every pixel, built on the first call), as host arrays like `preview`'s.  params:
-        make_filter_params(...), default the library's."""
+        make_filter_params(...), default the library's.  albedo_samples (vmx_progressive_preview_demodulated): filter
+        colour / albedo and multiply the albedo back, with the handle's albedo plane of that many samples (built on
+        the first such call, again when the number changes); None is the call without."""
+        if albedo_samples is not None and int(albedo_samples) < 1:
+            raise ValueError("albedo_samples must be at least 1")
         out = np.empty(self.shape + (5,), np.float32)
         q = np.empty(self.shape + (4,), np.uint8) if rgba8 else None
-        self._scene._check(self._lib.vmx_progressive_preview_filtered(self._h, out.ctypes.data,
-                                                                      None if q is None else q.ctypes.data,
-                                                                      None if params is None else C.byref(params)))
+        prm = None if params is None else C.byref(params)
+        if albedo_samples is None:
+            self._scene._check(self._lib.vmx_progressive_preview_filtered(self._h, out.ctypes.data,
+                                                                          None if q is None else q.ctypes.data, prm))
+        else:
+            self._scene._check(self._lib.vmx_progressive_preview_demodulated(self._h, out.ctypes.data,
+                                                                             None if q is None else q.ctypes.data, prm,
+                                                                             int(albedo_samples)))
         return (out, q) if rgba8 else out
 
-    def preview_filtered_device(self, rgbaz=None, rgba8=None, params=None):
+    def preview_filtered_device(self, rgbaz=None, rgba8=None, params=None, albedo_samples=None):
         """vmx_progressive_preview_filtered_device into torch tensors, checked as `preview_device` checks its own.
         Enqueued on the handle's stream, nothing synchronised (but the first filtered preview of a handle builds its
-        guide and blocks until that is done); returns (rgbaz, rgba8)."""
+        guide and blocks until that is done); returns (rgbaz, rgba8).  albedo_samples: as in `preview_filtered`
+        (vmx_progressive_preview_demodulated_device)."""
         import torch
+        if albedo_samples is not None and int(albedo_samples) < 1:
+            raise ValueError("albedo_samples must be at least 1")
         if rgbaz is None and rgba8 is None:
             raise ValueError("no output: rgbaz and rgba8 are both None")
         dev = torch.device("cuda", self.device)
@@ -648,8 +691,12 @@ class Progressive:
         if rgba8 is not None:
             _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-        self._scene._check(self._lib.vmx_progressive_preview_filtered_device(self._h, ptr(rgbaz), ptr(rgba8),
-                                                                             None if params is None else C.byref(params)))
+        prm = None if params is None else C.byref(params)
+        if albedo_samples is None:
+            self._scene._check(self._lib.vmx_progressive_preview_filtered_device(self._h, ptr(rgbaz), ptr(rgba8), prm))
+        else:
+            self._scene._check(self._lib.vmx_progressive_preview_demodulated_device(self._h, ptr(rgbaz), ptr(rgba8), prm,
+                                                                                    int(albedo_samples)))
         return rgbaz, rgba8
 
 
@@ -698,15 +745,19 @@ class Filter:
             self._check(self._lib.vmx_filter_set_guide_device(self._h, C.c_void_p(raw.data_ptr()),
                                                               C.c_void_p(run.cuda_stream)))
 
-    def apply(self, rgbaz, out=None, rgba8=None, params=None, stream=None):
+    def apply(self, rgbaz, out=None, rgba8=None, params=None, stream=None, albedo=None):
         """vmx_filter_apply_device: filters the float32 [height, width, 5] frame `rgbaz` into `out` (same shape; may be
         `rgbaz` itself) and / or `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is made.  All are
         contiguous torch tensors on the filter's device: anything else is a ValueError, never a copy through the host.
-        params: make_filter_params(...), default the library's.  Enqueued on `stream` (default
-        torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
+        params: make_filter_params(...), default the library's.  `albedo` (vmx_filter_apply_demodulated_device): what
+        Scene.albedo_camera made for the frame's camera, float32 [height, width, 4], 16-byte aligned, read only — the
+        filter then works on colour / albedo and multiplies the albedo back, so textures survive; None is the call
+        without.  Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
         import torch
         dev = torch.device("cuda", self.device)
         _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if albedo is not None:
+            _albedo_tensor(albedo, "albedo", self.shape, dev)
         if out is None and rgba8 is None:
             out = torch.empty_like(rgbaz)
         if out is not None:
@@ -715,9 +766,12 @@ class Filter:
             _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
         with _SideStream(dev, stream) as run:
-            self._check(self._lib.vmx_filter_apply_device(self._h, ptr(rgbaz), ptr(out), ptr(rgba8),
-                                                          None if params is None else C.byref(params),
-                                                          C.c_void_p(run.cuda_stream)))
+            prm, s = None if params is None else C.byref(params), C.c_void_p(run.cuda_stream)
+            if albedo is None:
+                self._check(self._lib.vmx_filter_apply_device(self._h, ptr(rgbaz), ptr(out), ptr(rgba8), prm, s))
+            else:
+                self._check(self._lib.vmx_filter_apply_demodulated_device(self._h, ptr(rgbaz), ptr(albedo), ptr(out),
+                                                                          ptr(rgba8), prm, s))
         return out, rgba8
 
 
