@@ -124,7 +124,9 @@ typedef struct vmx_opts {
     uint32_t reserved[7];  /* 0 unless tuning: [0] pipeline form (bits 0-7: 0 default routing, 1 fused kernel for every
                               pass, 4 split wavefront for every pass; bit 8: plain one-phase shading; bit 9: two-phase
                               shading through k_shade_ends instead of rays sorted by the traversal kernel; bit 11: no
-                              per-pixel claims for the camera rays),
+                              per-pixel claims for the camera rays; bit 12: the rays of a claimed pixel go through ray
+                              generation, traversal and shading kernels as the others do, instead of being formed, tested
+                              and shaded in the shading kernel alone),
                               [1] max paths per pass, [2] tail threshold, [3] refill_min, [4] shade_min,
                               [5] bounce reordering key (A/B library only), [6] LDS stack levels — all forms and
                               settings produce the same frame (see api_render.inc: render_impl, make_tuning) */
@@ -148,7 +150,8 @@ typedef struct vmx_stats {
     uint64_t samples;           /* pixel samples accumulated into the image            */
     uint64_t samples_discarded; /* speculative samples traced but dropped by early stop */
     uint64_t passes;            /* sample batches processed                            */
-    uint64_t kernel_launches;
+    uint64_t kernel_launches;   /* approximate, and the one count that depends on the pipeline form: a claim table adds
+                                   one, the lists of a pass with fused claimed pixels (reserved[0] bit 12 clear) four */
     double ms_total;            /* wall time of the call, host clock                   */
     double ms_device;           /* hipEvent time of the device work on the render stream */
     vmx_stage_stats primary; /* ms/launches: the depth-0 traversal kernel                  */
@@ -158,7 +161,7 @@ typedef struct vmx_stats {
 
 /* per-kernel device time (hipEvent pairs on the render stream) of the LAST render / radiance call on
  * a scene: what bench.py's roofline object is computed from (the dominant kernel of a step) */
-#define VMX_K_RAYGEN 0        /* k_raygen (+ live-path list under VMX_SAMPLING_ELIDE_DEAD)  */
+#define VMX_K_RAYGEN 0        /* k_raygen (+ live-path list under VMX_SAMPLING_ELIDE_DEAD, + the slot lists of a pass with fused claimed pixels) */
 #define VMX_K_TRACE_CAMERA 1  /* k_trace_w<0>: BVH traversal of the camera rays            */
 #define VMX_K_SHADE_CAMERA 2  /* k_shade<0> (with k_shade_ends<0> + list compaction where used) */
 #define VMX_K_TRACE_BOUNCE 3  /* k_trace_w<1>: BVH traversal of the bounce generations     */
@@ -383,6 +386,10 @@ int vmx_primary_ids(const vmx_scene *scene, const vmx_camera *cam, const vmx_opt
  * pixel hits.  Built whatever the sample count; *n_claimed = pixels with a claim.  Either output may be NULL. */
 int vmx_pixel_claims(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
                      uint32_t *n_claimed);
+/* Debug entry: how many camera paths of the last render call on this scene (vmx_render*, a vmx_progressive step) took the
+ * fused route — the paths of claimed pixels in a one-phase split pass (reserved[0] bit 8) of a multiple of 64 samples per
+ * pixel, whose rays the shading kernel forms and tests itself.  0 where no pass did, and with reserved[0] bit 12. */
+int vmx_fused_camera_paths(const vmx_scene *scene, uint64_t *paths);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

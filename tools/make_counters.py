@@ -20,9 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (vmx_timings name, substring of the demangled kernel name) — the kernels of the bench's headline frame: every Radiance
 # step shaded in full (vmx_opts.reserved[0] bit 8, bench.py HEADLINE_FORM)
 CLASSES = [
-    ("raygen", "k_raygen<0>"), ("trace_camera", "k_trace_w<0, false, false>"), ("shade_camera", "k_shade<0, false, false, 0, true>"),
+    # (shade_camera: one timed interval, two launches — the dense form over the unclaimed slots and its CLAIMED
+    # instantiation over the claimed ones; a class with several patterns adds their launches' counters and durations up)
+    ("raygen", "k_raygen<0>"), ("trace_camera", "k_trace_w<0, false, false>"),
+    ("shade_camera", ("k_shade<0, false, false, 0, true, false>", "k_shade<0, false, false, 0, true, true>")),
     # (one-phase bounce generations go through dense ray records, all kept: the SORT instantiation with WorkDev::keep_all)
-    ("trace_bounce", "k_trace_w<1, false, true>"), ("shade_bounce", "k_shade<1, false, false, 2, false>"),
+    ("trace_bounce", "k_trace_w<1, false, true>"), ("shade_bounce", "k_shade<1, false, false, 2, false, false>"),
     ("tail", "k_paths<false, 2"), ("fused", "k_paths<false, 0"), ("resolve", "k_resolve"),
 ]
 HEADLINE_FORM = 0x100
@@ -51,17 +54,24 @@ def main():
     tag = sys.argv[1]
     workload = sys.argv[2] if len(sys.argv) > 2 else "sponza260k 1920x1080 256spp, reference sampling, fixed spp"
     kernels = {}
-    for name, pat in CLASSES:
-        c, ms = {}, []
-        for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}_*"))):
-            if os.path.isdir(d):
-                v = longest(d, pat)
-                if "ms" in v:
-                    ms.append(v.pop("ms"))
-                c.update(v)
-        if not ms:
+    for name, pats in CLASSES:
+        pats = (pats,) if isinstance(pats, str) else pats
+        c, t = {}, 0.0
+        for pat in pats:
+            cp, ms = {}, []
+            for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}_*"))):
+                if os.path.isdir(d):
+                    v = longest(d, pat)
+                    if "ms" in v:
+                        ms.append(v.pop("ms"))
+                    cp.update(v)
+            if ms:
+                t += sum(ms) / len(ms) * 1e-3
+                for k_, v_ in cp.items():
+                    c[k_] = c.get(k_, 0.0) + v_
+        if t == 0.0:
             continue
-        t = sum(ms) / len(ms) * 1e-3
+        pat = " + ".join(pats)
         k = {"kernel": pat, "ms_under_pmc": round(t * 1e3, 4), "counters": c}
         d = {}
         if "GRBM_GUI_ACTIVE" in c:  # summed over the 8 XCDs (MI355X_MICROARCH.md, DVFS give-back)

@@ -201,6 +201,7 @@ int finish_stats(vmx_scene *sc, hipStream_t s, std::vector<TimedLaunch> &timed, 
     stats->samples_discarded = h.discarded;
     stats->passes = passes;
     stats->kernel_launches = launches;
+    sc->fused_paths = h.fused;
     std::memset(&sc->timings, 0, sizeof(sc->timings));
     for (auto &tl : timed) {
         float ms = 0.f;
@@ -248,7 +249,7 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     //   4 split wavefront for every pass (form 0 hands passes of fewer than 4 M paths to form 1's
     //     kernel, which needs no per-generation host round trip)
     const uint32_t pipeline = job.pipeline = opts->reserved[0] & 0xFFu;  // (bit 8: one-phase shading, see two_phase below)
-    if (pipeline > 4 || (opts->reserved[0] & ~0xFFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims)
+    if (pipeline > 4 || (opts->reserved[0] & ~0x1FFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims; bit 12: claimed pixels are not fused)
     if ((rc = ab_check_forms(sc, pipeline))) return rc;
     if ((rc = ab_check_pool(opts))) return rc;  // (reserved[0] bit 10)
     const bool split_any = job.split_any = pipeline == 0 || pipeline == 4;
@@ -345,6 +346,10 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     // form 0 runs its first pass split only from kHybridPaths path slots on.
     job.claims_on = split_any && !count && !job.elide && !(opts->reserved[0] & 0x800u) &&
                     (pipeline == 4 || (uint64_t)job.n_pad_max * smax >= kHybridPaths);
+    // ... and where the camera pass is the plain split form (one-phase, unsorted), a pass with claims whose sample count
+    // makes k_shade<0> dense fuses its claimed pixels into that kernel, unless reserved[0] bit 12 keeps them on the
+    // three-kernel route
+    job.fuse_on = job.claims_on && !tn.two_phase && !tn.sorted && !(opts->reserved[0] & 0x1000u);
     job.live_words_max = ((size_t)job.n_pad_max * smax + 63) / 64;
     if (job.elide) job.live_tmp_bytes = live_compact_tmp_bytes((uint32_t)job.live_words_max);
     if (pixels->ensure(npix)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the per-pixel state");
@@ -473,6 +478,16 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
             job.launches++;
         }
     }
+    // a plain dense camera pass with claims fuses its claimed pixels into k_shade<0> (render_pass) and needs the ordered
+    // lists of its unclaimed and of its claimed slots: at most every slot of the pixel list each
+    if (job.claims && job.fuse_on) {
+        const size_t words = n_pad_max / 64;
+        const size_t tmp = live_compact_tmp_bytes((uint32_t)words);
+        if (ws.unclaimed.ensure((size_t)n_pad_max + 64) || ws.claimed_slots.ensure((size_t)n_pad_max + 64) || ws.unclaimed_mask.ensure(words + 8) || ws.unclaimed_u32.ensure(2 * words + 16) ||
+            ws.unclaimed_tmp.ensure(tmp + 256))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the list of unclaimed pixels");
+        ws.unclaimed_words = words, ws.unclaimed_tmp_bytes = tmp;
+    }
     return VMX_OK;
 }
 
@@ -560,6 +575,8 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
         wk.cam_n_inner = sc->n_inner;
         wk.claims = job.claims;
+        // fused claimed pixels: where launch_shade picks the dense form of k_shade<0> (pixel-major ids, whole chunks of 64)
+        const bool fuse = job.fuse_on && job.claims && (S & 63u) == 0;
         LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)n_pad * S, job.tb);
         rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)n_pad * S, wk);
         if (rc) return rc;
@@ -580,6 +597,19 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
             LAUNCH_TRY(launch_raygen_live(sc->dev, fr, wk, px, pa, s));
             HIP_TRY(hipMemsetAsync(pa.rad_mask, 0, (size_t)nwords * 8, s));
         } else {
+            if (fuse) {
+                // the pass's unclaimed slots and its claimed ones, each in order (an unordered list costs the traversal kernel
+                // its bands' locality, see above), their numbers on the device only: k_raygen and k_trace_w<0> work on the
+                // first list; k_shade<0> runs over it as it is and, in its CLAIMED form, over the second, where it makes, tests
+                // and shades the rays itself.  Per pass: `active` shrinks between passes
+                const uint32_t nwords = n_pad / 64;
+                unsigned int *cnt = ws.unclaimed_u32.p, *offs = cnt + ws.unclaimed_words, *len = offs + ws.unclaimed_words;
+                LAUNCH_TRY(launch_unclaimed_words(act_cur, n_active, n_pad, job.claims, ws.unclaimed_mask.p, cnt, s));
+                HIP_TRY((hipError_t)launch_slot_lists(ws.unclaimed_mask.p, cnt, nwords, n_active, offs, ws.unclaimed.p, ws.claimed_slots.p, len,
+                                                      ws.unclaimed_tmp.p, ws.unclaimed_tmp_bytes, s));
+                wk.unclaimed = ws.unclaimed.p, wk.unclaimed_count = len;
+                launches += 3;  // (the scan counted as one launch, whatever hipcub makes of it)
+            }
             LAUNCH_TRY(launch_raygen(sc->dev, fr, wk, px, pa, s));
         }
         if (tn.sorted) {
@@ -589,7 +619,11 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         }
         if ((rc = timed_end(timed, s))) return rc;
         if ((rc = timed_begin(ws, timed, s, 0, VMX_K_TRACE_CAMERA))) return rc;
-        LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, px, pa, ws.counters.p, count, false, cfg, s));
+        {
+            WorkDev wt = wk;
+            if (fuse) wt.claims = nullptr;  // no listed slot has a claim: the refill-time claim branch has nothing to look up
+            LAUNCH_TRY(launch_trace_q(sc->dev, fr, wt, px, pa, ws.counters.p, count, false, cfg, s));
+        }
         if ((rc = timed_end(timed, s))) return rc;
         HIP_TRY(hipMemsetAsync(qi[0].counts, 0, kSubQueues * 32 * 4, s));
         // (under VMX_SAMPLING_ELIDE_DEAD the camera paths left are mostly those that go on: one phase — 0.56 against
@@ -598,7 +632,16 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         if (tn.two_phase && !elide && !tn.sorted) {
             if ((rc = shade_two_phase(sc, fr, wk, px, pa, qi, qi[0], 0, (size_t)(((uint64_t)n_pad * S + 63) / 64), false, ws.counters.p, false, s))) return rc;
         } else {
-            LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qi[0], 0, ws.counters.p, false, s));
+            if (fuse) {  // the unclaimed slots, then the claimed ones in the kernel's CLAIMED form
+                WorkDev wsh = wk;
+                wsh.shade_slots = wk.unclaimed, wsh.shade_count = wk.unclaimed_count;
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, s));
+                wsh.shade_slots = ws.claimed_slots.p, wsh.shade_count = wk.unclaimed_count + 1, wsh.fused = 1;
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, s));
+                launches++;
+            } else {
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qi[0], 0, ws.counters.p, false, s));
+            }
         }
         if ((rc = timed_end(timed, s))) return rc;
         launches += 4;
@@ -806,6 +849,14 @@ int vmx_pixel_claims(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts
     HIP_TRY(hipStreamSynchronize(s));
     if (claims_out) HIP_TRY(hipMemcpy(claims_out, ws.claims.p, (size_t)npix * 4, hipMemcpyDeviceToHost));
     if (n_claimed) HIP_TRY(hipMemcpy(n_claimed, ws.claims.p + npix, 4, hipMemcpyDeviceToHost));
+    return VMX_OK;
+}
+
+int vmx_fused_camera_paths(const vmx_scene *csc, uint64_t *paths) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !paths) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *paths = sc->fused_paths;
     return VMX_OK;
 }
 

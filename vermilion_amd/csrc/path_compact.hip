@@ -4,6 +4,8 @@
 // per wave of 64 consecutive path ids, one word of live bits and its popcount.  Here: exclusive scan of the popcounts
 // (hipcub), then every live path id is written to its place — neighbours stay neighbours, so a traversal wave still
 // holds samples of one pixel (or of a few neighbouring ones).
+// The same scan serves a pass that fuses its claimed pixels (k_slot_scatter): the ordered lists of the pass's unclaimed
+// and claimed slots from one word of "unclaimed" bits per 64 slots.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -26,6 +28,27 @@ k_live_scatter(const unsigned long long *__restrict__ live_mask, const unsigned 
     }
 }
 
+// the two ordered lists of a pass that fuses its claimed pixels: of the slots below n_active, those whose bit is set
+// (offs: the exclusive scan of the words' popcounts) and the others — the claimed ones, whose rank is what is left of
+// the slot's index
+__global__ void __launch_bounds__(256)
+k_slot_scatter(const unsigned long long *__restrict__ mask, const unsigned int *__restrict__ offs, uint32_t nwords, uint32_t n_active,
+               unsigned int *__restrict__ set_ids, unsigned int *__restrict__ clear_ids, unsigned int *__restrict__ counts) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nwords; w += waves) {
+        const unsigned long long bits = mask[w];
+        const uint32_t off = offs[w], slot = w * 64u + lane;
+        const uint32_t before = off + (uint32_t)__popcll(bits & ((1ull << lane) - 1ull));  // set bits below this slot
+        if ((bits >> lane) & 1ull) set_ids[before] = slot;
+        else if (slot < n_active) clear_ids[slot - before] = slot;
+        if (w + 1 == nwords && lane == 0) {
+            const uint32_t n_set = off + (uint32_t)__popcll(bits);
+            counts[0] = n_set, counts[1] = n_active - n_set;
+        }
+    }
+}
+
 }  // namespace
 
 size_t live_compact_tmp_bytes(uint32_t nwords) {
@@ -42,6 +65,17 @@ int launch_live_compact(const unsigned long long *live_mask, const unsigned int 
     if (e != hipSuccess) return (int)e;
     const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
     hipLaunchKernelGGL(k_live_scatter, dim3(grid), dim3(256), 0, s, live_mask, offs, nwords, ids, count);
+    return (int)hipGetLastError();
+}
+
+int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, uint32_t n_active, unsigned int *offs,
+                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (nwords == 0) return (int)hipMemsetAsync(counts, 0, 8, s);
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, offs, (int)nwords, s);
+    if (e != hipSuccess) return (int)e;
+    const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
+    hipLaunchKernelGGL(k_slot_scatter, dim3(grid), dim3(256), 0, s, mask, offs, nwords, n_active, unclaimed, claimed, counts);
     return (int)hipGetLastError();
 }
 

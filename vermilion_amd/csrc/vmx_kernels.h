@@ -95,6 +95,15 @@ struct WorkDev {
     // camera rays: one claim word per local pixel (pixel_claim.h; k_pixel_claims) or NULL: a claimed pixel's rays take
     // one triangle test in k_trace_w<0> instead of the BVH walk
     const unsigned int *claims;
+    // fused claimed pixels (render_pass; plain dense camera pass with claims): k_raygen<0> and k_trace_w<0> work on the
+    // ordered list of the pass's slots whose pixel has no claim (launch_slot_lists); k_shade<0, .., DENSE> is launched
+    // twice, over that list and — `fused`: its CLAIMED form, which forms, tests and shades the rays itself — over the
+    // ordered list of the claimed slots.  NULL / 0: every slot of the pass
+    const unsigned int *unclaimed;
+    const unsigned int *unclaimed_count;  // device scalar: entries of `unclaimed`
+    const unsigned int *shade_slots;      // the list a dense k_shade<0> walks (unclaimed slots; CLAIMED: the claimed slots)
+    const unsigned int *shade_count;      // device scalar: its entries
+    uint32_t fused;
 };
 
 // explicit ray batch of k_query (vmx_query.inc): device pointers, any output may be NULL
@@ -195,6 +204,13 @@ int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk
 size_t live_compact_tmp_bytes(uint32_t nwords);
 int launch_live_compact(const unsigned long long *live_mask, const unsigned int *live_cnt, uint32_t nwords,
                         unsigned int *offs, unsigned int *ids, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream);
+// the ordered lists of the slots [0, n_active) whose pixel has no claim / a claim, for a pass that fuses its claimed
+// pixels: one word of "unclaimed" bits and its popcount per 64 slots (mask, cnt: n_pad / 64 words), then launch_slot_lists:
+// set bits -> unclaimed, the other slots below n_active -> claimed; counts[0], counts[1] = the lists' lengths
+int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, uint32_t n_active, unsigned int *offs,
+                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, void *stream);
+int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
+                           unsigned long long *mask, unsigned int *cnt, void *stream);
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
                    DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream);
 int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks);

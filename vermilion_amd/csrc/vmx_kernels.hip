@@ -1760,6 +1760,19 @@ k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, co
     if (lane == 0 && n) atomicAdd(n_claimed, n);
 }
 
+// k_unclaimed_words — for a pass that fuses its claimed pixels: per 64 slots of the pass's pixel list, one word with the
+// bits of the slots whose pixel has no claim, and its popcount; launch_slot_lists (k_slot_scatter) makes the ORDERED lists of
+// those slots and of the claimed ones from them (ordered: the traversal kernel's 8 bands keep their image regions, see render_pass).  n_pad is a multiple of 64.
+__global__ void __launch_bounds__(256)
+k_unclaimed_words(const unsigned int *__restrict__ active, uint32_t n_active, uint32_t n_pad, const unsigned int *__restrict__ claims,
+                  unsigned long long *__restrict__ mask, unsigned int *__restrict__ cnt) {
+    for (uint32_t s_idx = blockIdx.x * blockDim.x + threadIdx.x; s_idx < n_pad; s_idx += gridDim.x * blockDim.x) {
+        const bool un = s_idx < n_active && claims[active[s_idx]] == kClaimNone;
+        const unsigned long long bits = __builtin_amdgcn_ballot_w64(un);
+        if ((threadIdx.x & 63u) == 0) mask[s_idx >> 6] = bits, cnt[s_idx >> 6] = (uint32_t)__popcll(bits);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // k_raygen — camera rays of one pass (pathtracer.cpp:251-280), written to rayA[pid] as
 // (direction, flag word): all camera rays share the frame's origin, so 16 bytes per ray suffice.
@@ -1782,8 +1795,13 @@ k_raygen(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa) 
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t waves = gridDim.x * (blockDim.x >> 6);
         const uint32_t chunks = wk.samples >> 6;
-        for (uint32_t s_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-             s_idx < wk.n_pad; s_idx += waves) {
+        // a pass that fuses its claimed pixels (WorkDev::unclaimed): only the listed slots get rays — a claimed pixel's
+        // are formed where they are shaded (k_shade<0, .., DENSE, CLAIMED>), and nothing reads the padding slots' records
+        const bool listed = !LIVE && wk.unclaimed != nullptr;
+        const uint32_t units = listed ? *wk.unclaimed_count : wk.n_pad;
+        for (uint32_t unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+             unit < units; unit += waves) {
+            const uint32_t s_idx = listed ? wk.unclaimed[unit] : unit;
             const uint32_t pid_base = s_idx * wk.samples;
             if (s_idx < wk.n_active) {
                 const uint32_t lp = wk.active[s_idx];
@@ -2573,6 +2591,10 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         const uint32_t n = *wk.live_count, seg = live_band(n);
                         lim = min(seg, n - min(n, src * seg));
                     }
+                    if (SRC == 0 && !LIVE && !SORT && wk.unclaimed) {  // the pass's unclaimed slots, in nsrc bands of the ordered list
+                        const uint32_t n = *wk.unclaimed_count, seg = (n + nsrc - 1u) / nsrc;
+                        lim = min(seg, n - min(n, src * seg)) * wk.samples;
+                    }
                     uint32_t base = 0;
                     if (lane == 0) base = atomicAdd(&wk.heads[src * 32], kReserve);
                     base = __builtin_amdgcn_readfirstlane(base);
@@ -2602,7 +2624,10 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         pid = src * live_band(*wk.live_count) + item;  // list position
                     } else if (SRC == 0) {
                         uint32_t j, s_idx;
-                        if (wk.pixel_major) {
+                        if (!SORT && wk.unclaimed) {  // (a fused pass is pixel-major) band-local item -> (list entry, sample)
+                            const uint32_t sl = fast_div(item, wk.div_samples), n = *wk.unclaimed_count;
+                            j = item - sl * wk.samples, s_idx = wk.unclaimed[src * ((n + nsrc - 1u) / nsrc) + sl];
+                        } else if (wk.pixel_major) {
                             const uint32_t sl = fast_div(item, wk.div_samples);
                             j = item - sl * wk.samples, s_idx = src * band_slots + sl;
                         } else {
@@ -2754,7 +2779,12 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
 #endif
 // FROMQ: 0 every path of the generation; 1 the ordered list of positions k_shade_ends + launch_live_compact left
 // (wk.flat_ids); 2 the records k_trace_w<.., SORT> appended (wk.out_rec: ray, hit and position in one place)
-template <int SRC, bool TEX, bool ELIDE = false, int FROMQ = 0, bool DENSE = false>
+// CLAIMED (dense form, a pass that fuses its claimed pixels): the work is the ordered list of the pass's CLAIMED slots
+// (wk.shade_slots, *wk.shade_count — as the plain dense form walks the unclaimed ones); the kernel forms each ray itself, as k_raygen does, and settles its BVH query by the pixel's claim —
+// neither rayA nor hit holds anything for these pixels.  The pass's other slots go through the plain dense form, over
+// the list of the unclaimed slots.  (One kernel with a wave-uniform branch was built first: 72 VGPRs, occupancy 7, but
+// 76 -> 108 bytes of scratch for every pixel, claimed or not — DESIGN.md §9.)
+template <int SRC, bool TEX, bool ELIDE = false, int FROMQ = 0, bool DENSE = false, bool CLAIMED = false>
 __global__ void __launch_bounds__(256, VMX_SHADE_WPS)
 k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, IdQueue qout, uint32_t max_chunks,
         DevCounters *ctr) {
@@ -2797,20 +2827,26 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
     // Path ids, the rad_mask word per 64 ids, the sub-queue of an id ((pid >> 8) % kSubQueues) and the tallies are
     // those of the block-item loop, which every other form keeps (one unit = one block item of 256 positions).
     static_assert(!DENSE || (SRC == 0 && FROMQ == 0 && !ELIDE), "the dense form is the plain camera pass");
+    static_assert(!CLAIMED || DENSE, "claimed pixels are fused in the dense form only");
     constexpr bool dense = DENSE;  // (launch_shade: wk.pixel_major && wk.samples % 64 == 0)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t chunks = dense ? wk.samples >> 6 : 1u;
+    uint32_t n_fused = 0;  // (wave-uniform) camera paths of claimed pixels whose ray was formed and tested here
     uint32_t unit = blockIdx.x, unit_step = gridDim.x, units = items;
     if (dense) {
         unit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-        unit_step = gridDim.x * (blockDim.x >> 6), units = wk.n_pad;
+        // (a pass that fuses its claimed pixels: the listed slots — the unclaimed ones here, the claimed ones in the CLAIMED form)
+        unit_step = gridDim.x * (blockDim.x >> 6), units = wk.shade_slots ? *wk.shade_count : wk.n_pad;
     }
     for (; unit < units; unit += unit_step) {
-        const bool px_active = dense && unit < wk.n_active;
+        const uint32_t slot = DENSE ? (wk.shade_slots ? wk.shade_slots[unit] : unit) : unit;
+        const bool px_active = dense && slot < wk.n_active;
+        uint32_t px_claim = kClaimNone, px_pixel = 0;  // CLAIMED: the pixel's claim and its global index, for the chunks below
         if (px_active) {
-            const uint32_t lp = wk.active[unit];
+            const uint32_t lp = wk.active[slot];
             const uint32_t pixel = global_pixel(fr, lp);
+            if (CLAIMED) px_claim = wk.claims[lp], px_pixel = pixel;
             const PixelKey pk = rng_pixel_key(fr.seed, pixel);
             const uint32_t cur = px.cursor[lp];  // (sample_index, with the cursor fetched once)
             // (the terms that depend on the frame or on the lane's sphere alone are formed here, per pixel, on purpose: kept
@@ -2837,7 +2873,7 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
             __builtin_amdgcn_wave_barrier();
         }
         for (uint32_t ch = 0; ch < chunks; ++ch) {
-            const uint32_t pos0 = dense ? unit * wk.samples + ch * 64u + lane : unit * blockDim.x + threadIdx.x;
+            const uint32_t pos0 = dense ? slot * wk.samples + ch * 64u + lane : unit * blockDim.x + threadIdx.x;
             const uint32_t item = dense ? pos0 >> 8 : unit;  // the block item of these positions (blocks are 256 wide)
             bool run;
             uint32_t pid = 0, src = 0;
@@ -2869,7 +2905,37 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
                     else j = pid / wk.n_pad, s_idx = pid - j * wk.n_pad;
                     run = j < wk.samples && s_idx < wk.n_pad && primary_item(fr, wk, px, j, s_idx, pid2, pixel, k);
                 }
-                if (run) {
+                if (CLAIMED) {
+                    // a claimed pixel of a fused pass: the ray is formed here as k_raygen forms it (same function, same
+                    // translation unit: bit-equal), which leaves the stream past its two jitter draws, and the pixel's
+                    // claim settles its BVH query as the refill branch of k_trace_w<0> does — the claimed triangle's own
+                    // test on its camera-relative record (wave-uniform: through the scalar cache), or no hit
+                    n_fused += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(run));
+                    if (run) {
+                        PixelKey pk;
+                        pk.a = (uint64_t)s_pix[wave][2] | ((uint64_t)s_pix[wave][3] << 32);
+                        pk.b = (uint64_t)s_pix[wave][4] | ((uint64_t)s_pix[wave][5] << 32);
+                        P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz, P.depth = 0;
+                        primary_ray_keyed(fr, px_pixel, pk, k, P.rng, P.dx, P.dy, P.dz);
+                        float best = 999999999.f;
+                        int leaf = -1;
+                        if (px_claim < kClaimMiss) {  // a slot claim (a listed pixel has a claim: never kClaimNone)
+                            typedef float f32x4 __attribute__((ext_vector_type(4)));
+                            typedef const __attribute__((address_space(4))) f32x4 *scalar_ptr;
+                            const uint32_t claim = (uint32_t)__builtin_amdgcn_readfirstlane((int)px_claim);
+                            const scalar_ptr rec = (scalar_ptr)((uintptr_t)wk.cam_tris + (size_t)claim * 64u);
+                            const f32x4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+                            float dist;
+                            if (tri_test_cam(make_float4(r0.x, r0.y, r0.z, r0.w), make_float4(r1.x, r1.y, r1.z, r1.w),
+                                             make_float4(r2.x, r2.y, r2.z, r2.w), r3.x, P.dx, P.dy, P.dz, dist) && dist < best)
+                                best = dist, leaf = (int)claim;
+                        }
+                        hrec = make_float2(best, __int_as_float(leaf));
+                        P.ar = P.ag = P.ab = 0.f;
+                        P.aw = -100.f;  // pathtracer.cpp:29
+                        P.tr = P.tg = P.tb = P.tw = 1.f;  // :30
+                    }
+                } else if (run) {
                     // the ray comes from k_raygen; the stream is re-keyed and its two jitter draws skipped
                     const float4 a = FROMQ == 2 ? rec0 : ((const float4 *)pa.rayA)[src];
                     P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz, P.dx = a.x, P.dy = a.y, P.dz = a.z, P.depth = 0;
@@ -2919,7 +2985,7 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
                 P.dest = pid;
                 depth0 = P.depth == 0 ? 1u : 0u;
                 fl.was_ray = depth0 ? true : finite3(P.dx, P.dy, P.dz);
-                const float2 h = FROMQ == 2 ? hrec : hits[SRC == 0 ? src : pid];
+                const float2 h = (FROMQ == 2 || CLAIMED) ? hrec : hits[SRC == 0 ? src : pid];
                 // (the pixel's sphere bounds: the dense camera form only — elsewhere lmax_min < 0, every sphere is evaluated)
                 cast_finish<true, SRC == 0, DENSE>(sc, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, h.x, __float_as_int(h.y), c,
                                                                              s_geom, s_cam_op, s_lmax[wave], dense);
@@ -2972,6 +3038,8 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
                 if (listed || FROMQ != 0) {  // the mask was cleared for the pass / written by k_shade_ends; neighbours share words
                     if (need) atomicOr(&pa.rad_mask[pid >> 6], 1ull << (pid & 63u));
                 } else {
+                    // (a pass that fuses its claimed pixels walks lists of slots below n_active: the words of its padding slots
+                    // keep what an earlier pass left, which nothing reads — k_resolve takes the slots below n_active only)
                     const unsigned long long word = __builtin_amdgcn_ballot_w64(need);
                     if (lane == 0) pa.rad_mask[pos0 >> 6] = word;
                 }
@@ -2982,6 +3050,7 @@ k_shade(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa, I
     }
     const Cnt none = {0, 0};
     tally_flush<false>(ctr, tl, none, none);
+    if (CLAIMED && lane == 0 && n_fused) atomicAdd(&ctr->fused, (unsigned long long)n_fused);
 }
 
 // ---------------------------------------------------------------------------
@@ -3673,6 +3742,13 @@ int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &w
     return launch_status();
 }
 
+int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
+                           unsigned long long *mask, unsigned int *cnt, void *stream) {
+    const uint32_t grid = std::max(1u, std::min<uint32_t>((n_pad + 255) / 256, 4096u));
+    hipLaunchKernelGGL(k_unclaimed_words, dim3(grid), dim3(256), 0, (hipStream_t)stream, active, n_active, n_pad, claims, mask, cnt);
+    return launch_status();
+}
+
 int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream) {
     // the list's length is known on the device only: a grid for a third of the pass's paths, striding over the rest
     const uint64_t total = ((uint64_t)wk.samples * wk.n_pad + 2) / 3;
@@ -3738,8 +3814,11 @@ int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
                                               : (dense ? ((uint64_t)wk.n_pad + 3) / 4 : ((uint64_t)wk.samples * wk.n_pad + 255) / 256));
     uint32_t grid = (uint32_t)std::min<uint64_t>(items, kShadeGrid);
     if (grid == 0) grid = 1;
-#define VMX_GO(S, T, E, Q, D) \
-    hipLaunchKernelGGL((k_shade<S, T, E, Q, D>), dim3(grid), dim3(256), 0, s, sc, fr, wk, px, pa, qout, max_chunks, counters)
+#define VMX_GO(S, T, E, Q, D)                                                                                                    \
+    do {  /* (wk.fused: the dense form's CLAIMED instantiation, over the pass's claimed slots) */                                \
+        if (D && wk.fused) hipLaunchKernelGGL((k_shade<S, T, E, Q, D, D>), dim3(grid), dim3(256), 0, s, sc, fr, wk, px, pa, qout, max_chunks, counters); \
+        else hipLaunchKernelGGL((k_shade<S, T, E, Q, D>), dim3(grid), dim3(256), 0, s, sc, fr, wk, px, pa, qout, max_chunks, counters); \
+    } while (0)
 #define VMX_GO_T(S, E, Q, ...)                       \
     do {                                             \
         if (sc.tex) VMX_GO(S, true, E, Q, (false __VA_ARGS__)); \

@@ -92,7 +92,7 @@ def make_opts(seed=1, early_stop=True, sampling=L.VMX_SAMPLING_PARITY, rank=0, w
     o.rank, o.world, o.stripe_rows = int(rank), int(world), int(stripe_rows)
     o.samples_per_batch = int(samples_per_batch)
     o.collect_counters = 1 if collect_counters else 0
-    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims
+    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims, | 0x1000 claimed pixels are not fused into the shading kernel
     o.reserved[1] = int(max_paths)     # paths in flight per pass (0 -> 16M)
     o.reserved[2] = int(tail_threshold)
     o.reserved[3] = int(refill_min)    # k_paths: refill when this many lanes idle (0 -> 16)
@@ -543,6 +543,13 @@ class Scene:
         n = C.c_uint32(0)
         self._check(self._lib.vmx_pixel_claims(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(n)))
         return out, int(n.value)
+
+    def fused_camera_paths(self):
+        """vmx_fused_camera_paths: the camera paths of the last render on this scene whose rays the shading kernel
+        formed and tested itself (claimed pixels of a fused pass)"""
+        n = C.c_uint64(0)
+        self._check(self._lib.vmx_fused_camera_paths(self._h, C.byref(n)))
+        return int(n.value)
 
     def render(self, cam, opts):
         """PathTracer::Render into a host array [local_rows, W, 5] (RGBAZ)."""
