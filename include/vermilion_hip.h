@@ -126,7 +126,8 @@ typedef struct vmx_opts {
                               shading through k_shade_ends instead of rays sorted by the traversal kernel; bit 11: no
                               per-pixel claims for the camera rays; bit 12: the rays of a claimed pixel go through ray
                               generation, traversal and shading kernels as the others do, instead of being formed, tested
-                              and shaded in the shading kernel alone),
+                              and shaded in the shading kernel alone; bit 13: no list claims for the pixels without a
+                              claim),
                               [1] max paths per pass, [2] tail threshold, [3] refill_min, [4] shade_min,
                               [5] bounce reordering key (A/B library only), [6] LDS stack levels — all forms and
                               settings produce the same frame (see api_render.inc: render_impl, make_tuning) */
@@ -390,6 +391,15 @@ int vmx_pixel_claims(const vmx_scene *scene, const vmx_camera *cam, const vmx_op
  * fused route — the paths of claimed pixels in a one-phase split pass (reserved[0] bit 8) of a multiple of 64 samples per
  * pixel, whose rays the shading kernel forms and tests itself.  0 where no pass did, and with reserved[0] bit 12. */
 int vmx_fused_camera_paths(const vmx_scene *scene, uint64_t *paths);
+/* Debug entry: vmx_pixel_claims and, for the pixels without a claim, the list claims a render would use: four 32-bit words
+ * per pixel of this rank's rows, up to four leaf-order slots padded with 0xFFFFFFFF (all four: no list).  A camera ray of
+ * such a pixel is tested against the listed triangles alone and skips the BVH walk where that test is decisive.
+ * lists_out is required; claims_out and n_claimed may be NULL. */
+int vmx_pixel_claim_lists(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                          uint32_t *lists_out, uint32_t *n_claimed);
+/* Debug entry: how many camera rays of the last render call on this scene were settled by a list claim.  0 where no
+ * claims were built, with reserved[0] bit 11 or bit 13, and in the counting build. */
+int vmx_list_settled_rays(const vmx_scene *scene, uint64_t *rays);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

@@ -202,6 +202,7 @@ int finish_stats(vmx_scene *sc, hipStream_t s, std::vector<TimedLaunch> &timed, 
     stats->passes = passes;
     stats->kernel_launches = launches;
     sc->fused_paths = h.fused;
+    sc->list_settled = h.listed;
     std::memset(&sc->timings, 0, sizeof(sc->timings));
     for (auto &tl : timed) {
         float ms = 0.f;
@@ -249,7 +250,7 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     //   4 split wavefront for every pass (form 0 hands passes of fewer than 4 M paths to form 1's
     //     kernel, which needs no per-generation host round trip)
     const uint32_t pipeline = job.pipeline = opts->reserved[0] & 0xFFu;  // (bit 8: one-phase shading, see two_phase below)
-    if (pipeline > 4 || (opts->reserved[0] & ~0x1FFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims; bit 12: claimed pixels are not fused)
+    if (pipeline > 4 || (opts->reserved[0] & ~0x3FFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims; bit 12: claimed pixels are not fused; bit 13: no list claims)
     if ((rc = ab_check_forms(sc, pipeline))) return rc;
     if ((rc = ab_check_pool(opts))) return rc;  // (reserved[0] bit 10)
     const bool split_any = job.split_any = pipeline == 0 || pipeline == 4;
@@ -350,6 +351,8 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     // makes k_shade<0> dense fuses its claimed pixels into that kernel, unless reserved[0] bit 12 keeps them on the
     // three-kernel route
     job.fuse_on = job.claims_on && !tn.two_phase && !tn.sorted && !(opts->reserved[0] & 0x1000u);
+    // list claims for the pixels without a claim (pixel_claim.h), wherever claims are on, unless reserved[0] bit 13
+    job.lists_on = job.claims_on && !(opts->reserved[0] & 0x2000u);
     job.live_words_max = ((size_t)job.n_pad_max * smax + 63) / 64;
     if (job.elide) job.live_tmp_bytes = live_compact_tmp_bytes((uint32_t)job.live_words_max);
     if (pixels->ensure(npix)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the per-pixel state");
@@ -389,10 +392,12 @@ uint32_t claim_min_samples() {
 }
 
 // the per-pixel claims of the frame `fr` from the camera tables in the workspace, into ws.claims[0, npix) and the number
-// of claimed pixels into ws.claims[npix]
-int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t npix, hipStream_t s) {
+// of claimed pixels into ws.claims[npix]; lists: the list records of the pixels without a claim into ws.claim_lists too, in
+// the same launch
+int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t npix, bool lists, hipStream_t s) {
     Workspace &ws = sc->ws;
     if (ws.claims.ensure((size_t)npix + 1)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the pixel claims");
+    if (lists && ws.claim_lists.ensure((size_t)npix * kListWords)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the claim lists");
     WorkDev wk;
     std::memset(&wk, 0, sizeof(wk));
     wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
@@ -401,7 +406,7 @@ int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t n
     int rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)tiles * 64, wk);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ws.claims.p + npix, 0, 4, s));
-    LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, ws.claims.p + npix, cfg, s));
+    LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, lists ? ws.claim_lists.p : nullptr, ws.claims.p + npix, cfg, s));
     return VMX_OK;
 }
 
@@ -465,16 +470,17 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
     // been updated since a progressive handle's last step), reused by all its passes — when the run's samples per pixel
     // pay for them (an early-stop frame: what most pixels take, the samples before the rule can fire and the first one
     // of every later stratum)
-    job.claims = nullptr;
+    job.claims = job.claim_lists = nullptr;
     if (job.claims_on) {
         uint32_t expect = fr.early_stop ? std::min(fr.kmax, fr.nmin + 1 + (fr.quarter ? fr.kmax / fr.quarter - 1u : 0u)) : fr.kmax;
         if (run_samples) expect = std::min(expect, run_samples);
         if (expect >= claim_min_samples()) {
             int rc = timed_begin(ws, job.timed, s, -1, VMX_K_OTHER);
             if (rc) return rc;
-            if ((rc = build_claims(sc, fr, tn, job.npix, s))) return rc;
+            if ((rc = build_claims(sc, fr, tn, job.npix, job.lists_on, s))) return rc;
             if ((rc = timed_end(job.timed, s))) return rc;
             job.claims = ws.claims.p;
+            if (job.lists_on) job.claim_lists = ws.claim_lists.p;
             job.launches++;
         }
     }
@@ -575,6 +581,7 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
         wk.cam_n_inner = sc->n_inner;
         wk.claims = job.claims;
+        wk.claim_lists = elide ? nullptr : job.claim_lists, wk.list_ctr = ws.counters.p;
         // fused claimed pixels: where launch_shade picks the dense form of k_shade<0> (pixel-major ids, whole chunks of 64)
         const bool fuse = job.fuse_on && job.claims && (S & 63u) == 0;
         LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)n_pad * S, job.tb);
@@ -827,8 +834,8 @@ int vmx_render(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts
     return VMX_OK;
 }
 
-int vmx_pixel_claims(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
-                     uint32_t *n_claimed) {
+static int pixel_claims_impl(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                             uint32_t *lists_out, uint32_t *n_claimed) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
     if (!sc || !cam || !opts) return fail(VMX_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lock(sc->mu);
@@ -845,10 +852,30 @@ int vmx_pixel_claims(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts
     const size_t n_inner = std::max<size_t>(sc->n_inner, 1);
     if (ws.cam_inner.ensure(n_inner * 64 * 8 + (size_t)sc->ntris * 64)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the camera tables");
     LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p, ws.cam_inner.p + n_inner * 64 * 8, s));
-    if ((rc = build_claims(sc, fr, make_tuning(sc, opts), npix, s))) return rc;
+    if ((rc = build_claims(sc, fr, make_tuning(sc, opts), npix, lists_out != nullptr, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (claims_out) HIP_TRY(hipMemcpy(claims_out, ws.claims.p, (size_t)npix * 4, hipMemcpyDeviceToHost));
+    if (lists_out) HIP_TRY(hipMemcpy(lists_out, ws.claim_lists.p, (size_t)npix * kListWords * 4, hipMemcpyDeviceToHost));
     if (n_claimed) HIP_TRY(hipMemcpy(n_claimed, ws.claims.p + npix, 4, hipMemcpyDeviceToHost));
+    return VMX_OK;
+}
+
+int vmx_pixel_claims(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                     uint32_t *n_claimed) {
+    return pixel_claims_impl(csc, cam, opts, claims_out, nullptr, n_claimed);
+}
+
+int vmx_pixel_claim_lists(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, uint32_t *claims_out,
+                          uint32_t *lists_out, uint32_t *n_claimed) {
+    if (!lists_out) return fail(VMX_ERR_INVALID, "NULL argument");
+    return pixel_claims_impl(csc, cam, opts, claims_out, lists_out, n_claimed);
+}
+
+int vmx_list_settled_rays(const vmx_scene *csc, uint64_t *rays) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !rays) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *rays = sc->list_settled;
     return VMX_OK;
 }
 

@@ -281,13 +281,17 @@ VMX_PC_FN int pc_nearest(const float *cam_inner, const float *cam_tris, uint32_t
 }
 
 // The per-pixel procedure over the camera-relative tables (octant-0 node copy, triangle records) of the frame's origin
+// (cand_out: the candidate of the centre ray, -1: it hits nothing, -2: no cone or no walk; other_out: the live triangle
+// that ended the culled walk, or -1 — pc_pixel_list starts from the two)
 template <class Stack>
-VMX_PC_FN uint32_t pc_pixel_claim(const PcFilm &fm, uint32_t p, const float *cam_inner, const float *cam_tris,
-                                  uint32_t root_ref, Stack &stk, int max_sp) {
+VMX_PC_FN uint32_t pc_pixel_claim_cand(const PcFilm &fm, uint32_t p, const float *cam_inner, const float *cam_tris,
+                                       uint32_t root_ref, Stack &stk, int max_sp, int &cand_out, int &other_out) {
     const PcCone c = pc_cone(fm, p);
+    cand_out = -2, other_out = -1;
     if (!c.ok) return kClaimNone;
     const int cand = pc_nearest(cam_inner, cam_tris, root_ref, c.ax, c.ay, c.az, stk, max_sp);
     if (cand < -1) return kClaimNone;
+    cand_out = cand;
     PcTri T;
     T.nx = T.ny = T.nz = T.dlo = T.dhi = T.sd = T.acd = 0.0f, T.covers = false;
     float tcut = kPcNoCut;
@@ -313,7 +317,10 @@ VMX_PC_FN uint32_t pc_pixel_claim(const PcFilm &fm, uint32_t p, const float *cam
                 PcTri U;
                 const PcClass k = pc_classify(c, cam_tris + (size_t)(first + i) * 16, U);
                 if (k == kPcRejected) continue;
-                if (cand < 0 || k == kPcUnsure || !pc_farther(c, T, U)) return kClaimNone;
+                if (cand < 0 || k == kPcUnsure || !pc_farther(c, T, U)) {
+                    if (k == kPcLive) other_out = (int)(first + i);
+                    return kClaimNone;
+                }
             }
             if (sp == 0) break;
             float unused;
@@ -339,6 +346,252 @@ VMX_PC_FN uint32_t pc_pixel_claim(const PcFilm &fm, uint32_t p, const float *cam
         }
     }
     return cand >= 0 ? (uint32_t)cand : kClaimMiss;
+}
+template <class Stack>
+VMX_PC_FN uint32_t pc_pixel_claim(const PcFilm &fm, uint32_t p, const float *cam_inner, const float *cam_tris,
+                                  uint32_t root_ref, Stack &stk, int max_sp) {
+    int cand, other;
+    return pc_pixel_claim_cand(fm, p, cam_inner, cam_tris, root_ref, stk, max_sp, cand, other);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// List claims — for a pixel whose claim is kClaimNone: a short list L = {T1..Tk}, k <= kListK, of leaf-order slots.
+// Record of a pixel: kListWords words, the slots padded with kClaimNone (one 16-byte load).  An empty list is
+// kListWords x kClaimNone.
+//
+// Per-ray rule (pc_list_settle).  The ray's own test (pc_ray_test: the operations of tri_test_cam, same bits) runs on
+// every member.  The ray WALKS
+//   - if no member accepts it,
+//   - if the two smallest accepted distances lie within 2^-16 (kPcRel) of each other, equality included (the
+//     reference's test order decides such ties),
+//   - or if the nearest member's hit lies within the containment band of (3).
+// Otherwise it is settled with that member's (t, slot).  Contract: whenever the rule settles a ray of the pixel,
+// BVH::getIntersection returns exactly that pair.  A list may settle none of the pixel's rays; there is no coverage
+// condition.
+//
+// Why a settled ray is right.  Let m be the winner and t its float distance.
+//   (1) Members are kPcLive: sign(det) fixed over the cone, lengths in range, s cd > 0.  So for every ray of the cone
+//       that m accepts, t |w| <= thi(m) = |cd| / (dlo - sd), as for T in (b) above.
+//   (2) Non-members.  The culled walk of (b) runs with tcut = max thi(m) (1 + 2^-10) over the FINAL list: whenever a
+//       reached triangle joins, the walk restarts from the root with the new list.  That is at most kListK restarts;
+//       the first two candidates come from pc_pixel_claim_cand's own walk.  So the walk that ends has seen every
+//       triangle in a node the cone may reach no later than the final tcut, and each was a member, surely rejected, or
+//       surely farther (pc_farther) than EVERY member, hence farther than m by 2^-16 for this ray.  A kPcUnsure
+//       triangle, a join that would overflow, or a joining triangle that is not kPcLive with a distance in range: no
+//       list.  A triangle in a node beyond tcut is hit, if at all, beyond every member's distance.  So no non-member
+//       is accepted at a distance <= t (1 + 2^-16).
+//   (3) The reference reaches m (pc_hit_in_own_box).  (c) cannot ask that the whole cone's hits lie inside m's box, so
+//       the rule asks it of the ray.  Let mn_k, mx_k be the box of m's vertices from the record, as in
+//       pc_inside_own_box, and sl_k = 2^-19 (|mn| + |mx|) + 2^-22 |e| the same slab slack: 8 times the three roundings
+//       of a slab product (bbox.cpp:72-73) plus the one of the product below, and the 2^-24 |e| by which the tree's
+//       boxes contain the vertices.
+//       (3a) The box has extent on all three axes.  The rule asks t d_k in [mn_k + sl_k, mx_k - sl_k] for every k.
+//            Then every slab interval of the leaf and, boxes being nested and rounding monotonic, of every ancestor
+//            contains the float t itself, whatever the accuracy of t: `near <= far` holds, and near <= t (1 + 3 x
+//            2^-24).
+//       (3b) The box has no extent on axis f (a triangle in a coordinate plane: a wall, a floor).  There both slab
+//            products of m's own box are the one number s = p0_f * (1 / d_f), computed here as bbox.cpp computes it,
+//            and the float t of the triangle test need NOT agree with it: for a thin triangle in such a plane the
+//            terms of det and cd cancel, and t is off by up to 2^-7 relative while the slab slack is 2^-19.  So the
+//            rule does not rest on t there.  It asks |s - t| <= 2^-17 t, and s d_k in [mn_k + sl_k, mx_k - sl_k] on
+//            the two other axes as well as t d_k.  Then every slab interval of the leaf and of every ancestor
+//            contains s (on axis f by nesting, on the others by the slack), so `near <= far` holds and
+//            near <= s (1 + 3 x 2^-24) <= t (1 + 2^-17) (1 + 3 x 2^-24).  Two axes without extent: the ray walks.
+//       In both cases no node on the way to m is pruned (bvh.cpp:69): its near is below t (1 + 2^-16), while the
+//       nearest hit so far is a non-member's (farther by 2^-16, (2)) or another member's (farther by more than 2^-16:
+//       the tie band of the rule).  The band is absolute and a few 2^-19 of the coordinates wide: a triangle thinner
+//       than that along an axis settles no ray.
+//       (A band on the barycentrics, u, v, 1 - u - v >= delta, was built first.  Its delta has to cover the float
+//       error of u, v and t over the whole cone: 0.015 for the median list pixel of the 1080p bench frame, as wide as
+//       the pixel, and 40 % of the unclaimed rays settled.)
+//   (4) Other members are tested by the rule itself with the reference's arithmetic.  Those that accept lie beyond
+//       t (1 + 2^-16) and lose whatever the order; those that reject are rejected by the reference as well.
+//   (5) The guards of (c) and (d) stay: pc_cone's answer on a coordinate plane (so no d_k is zero), NaN (every
+//       comparison fails on one), stack depth, and kListBudget node and triangle visits over all restarts together.
+// kListK = 4: the shares of list lengths on the 1080p bench frame are in profiles/claim_lists.txt; K = 3 loses 3 % of
+// the pixels without a single claim.  kListBudget: the walks of one pixel restart at most four times and each is a
+// kClaimBudget-sized walk with a longer tcut; the largest pixel of that frame takes 659 visits, none is lost to it.
+// Checked against the oracle in tests/test_claim_lists.py.
+#ifndef VMX_PC_WHY
+#define VMX_PC_WHY(code)  // (tools/claim_list_shares.py --why: the host program counts why a pixel got no list)
+#endif
+constexpr int kListK = 4;
+constexpr int kListWords = 4;
+constexpr uint32_t kListBudget = 1536;
+
+// the reference's triangle test on a camera-relative record, with its u and v: the operations of tri_test_cam
+VMX_PC_FN bool pc_ray_test(const float *r, float dx, float dy, float dz, float &dist, float &u, float &v) {
+    const float pvx = dy * r[5] - r[4] * dz, pvy = dz * r[3] - r[5] * dx, pvz = dx * r[4] - r[3] * dy;
+    const float det = (r[0] * pvx + r[1] * pvy) + r[2] * pvz;
+    const float inv = 1.0f / det;
+    u = ((r[6] * pvx + r[7] * pvy) + r[8] * pvz) * inv;
+    v = ((dx * r[9] + dy * r[10]) + dz * r[11]) * inv;
+    dist = r[12] * inv;
+    const bool parallel = fabsf(det) <= 9.99999993922529e-09f;
+    const bool u_out = (u < 0.0f) || (u > 1.0f);
+    const bool v_out = (v < 0.0f) || (u + v > 1.0f);
+    return !parallel && !u_out && !v_out && (dist > 0.0f);
+}
+
+// (3) for one ray: its hit inside the box of the record's vertices by the slab slack — t d on every axis with extent
+// (3a), and where one axis has none, the slab distance s of that axis within 2^-17 of t and s d inside as well (3b)
+constexpr float kPcFlatRel = 7.62939453125e-06f;  // 2^-17
+VMX_PC_FN bool pc_hit_in_own_box(const float *r, float t, float dx, float dy, float dz) {
+    const float d[3] = {dx, dy, dz};
+    bool ok = true;
+    int nflat = 0;
+    float s = t;
+    for (int k = 0; k < 3; ++k) {
+        if (r[k] == 0.0f && r[3 + k] == 0.0f) {  // no extent: v1 = v2 = v0 on this axis
+            s = -r[6 + k] * (1.0f / d[k]);
+            ++nflat;
+        }
+    }
+    if (nflat > 1 || !(fabsf(s - t) <= kPcFlatRel * t)) ok = false;  // (nflat = 0: s = t)
+    for (int k = 0; k < 3; ++k) {
+        const float p0 = -r[6 + k], p1 = p0 + r[k], p2 = p0 + r[3 + k];
+        const float mn = fminf(p0, fminf(p1, p2)), mx = fmaxf(p0, fmaxf(p1, p2));
+        const float sl = 1.9073486328125e-06f * (fabsf(mn) + fabsf(mx)) + 2.384185791015625e-07f * (fabsf(r[k]) + fabsf(r[3 + k]));
+        const float h = t * d[k], g = s * d[k];
+        const bool flat = r[k] == 0.0f && r[3 + k] == 0.0f;
+        if (!flat && !(h >= mn + sl && h <= mx - sl && g >= mn + sl && g <= mx - sl)) ok = false;
+    }
+    return ok;
+}
+
+// the per-ray rule.  l0..l3: the pixel's slots.  true: the ray is settled with (t, slot)
+VMX_PC_FN bool pc_list_settle(const float *cam_tris, uint32_t l0, uint32_t l1, uint32_t l2, uint32_t l3, float dx, float dy,
+                              float dz, float &t, uint32_t &slot) {
+    float t1 = 3.0e38f, t2 = 3.0e38f;
+    uint32_t s1 = kClaimNone;
+    bool inside = false;
+    uint32_t m = l0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int k = 0; k < kListK; ++k) {
+        if (m == kClaimNone) break;  // (padding follows the members)
+        const float *r = (const float *)__builtin_assume_aligned(cam_tris + (size_t)m * 16, 16);
+        float d, u, v;
+        if (pc_ray_test(r, dx, dy, dz, d, u, v)) {
+            if (d < t1) {
+                t2 = t1, t1 = d, s1 = m;
+                inside = pc_hit_in_own_box(r, d, dx, dy, dz);
+            } else {
+                t2 = fminf(t2, d);
+            }
+        }
+        m = k == 0 ? l1 : (k == 1 ? l2 : l3);
+    }
+    if (s1 == kClaimNone || !inside || !(t1 < 999999999.f)) return false;  // (the walk starts from 999999999: bvh.cpp:48)
+    if (t2 <= t1 + t1 * kPcRel) return false;
+    t = t1, slot = s1;
+    return true;
+}
+
+// The per-pixel procedure of a list, for a pixel whose single claim is kClaimNone.  cand, other: what
+// pc_pixel_claim_cand left — the centre ray's nearest triangle (-1: none, -2: no list) and the triangle its walk ended
+// on (-1: none); both are only the first candidates for membership, and a list that starts from any live triangles is
+// sound: what (2) asks is asked of the final list.  out: the record (kListWords words).  Returns the number of members.
+// The members are kept as slots alone and classified again where pc_farther needs one: a few reached triangles per
+// walk need it, and four PcTri in registers cost k_pixel_claims three of its seven waves per SIMD.
+template <class Stack>
+VMX_PC_FN int pc_pixel_list(const PcFilm &fm, uint32_t p, const float *cam_inner, const float *cam_tris, uint32_t root_ref,
+                            Stack &stk, int max_sp, int cand, int other, uint32_t *out) {
+    for (int k = 0; k < kListWords; ++k) out[k] = kClaimNone;
+    if (cand < -1) return 0;
+    const PcCone c = pc_cone(fm, p);
+    if (!c.ok) return 0;
+    uint32_t s0 = kClaimNone, s1 = kClaimNone, s2 = kClaimNone, s3 = kClaimNone;
+    int n = 0;
+    float tcut = kPcNoCut, thi_max = 0.0f;
+    uint32_t join = cand >= 0 ? (uint32_t)cand : kClaimNone, join2 = other >= 0 ? (uint32_t)other : kClaimNone;
+    uint32_t visits = 0;
+    for (;;) {
+        if (join == kClaimNone) join = join2, join2 = kClaimNone;
+        if (join != kClaimNone) {
+            if (n == kListK) { VMX_PC_WHY(3); return 0; }
+            PcTri T;
+            if (pc_classify(c, cam_tris + (size_t)join * 16, T) != kPcLive) { VMX_PC_WHY(4); return 0; }
+            const float thi = T.acd / (T.dlo - T.sd);  // the largest tau = t |w| of the cone, float det included
+            if (!(T.dlo > 2.0f * T.sd && thi > 1e-20f && thi < 1e8f)) { VMX_PC_WHY(1); return 0; }
+            if (n == 0) s0 = join;
+            else if (n == 1) s1 = join;
+            else if (n == 2) s2 = join;
+            else s3 = join;
+            ++n;
+            thi_max = fmaxf(thi_max, thi);
+            tcut = thi_max * (1.0f + 9.765625e-04f);
+            join = kClaimNone;
+            if (join2 != kClaimNone) continue;
+        }
+        // the culled walk with the current list; a triangle that must join ends it
+        int sp = 0;
+        uint32_t cur = root_ref;
+        for (;;) {
+            if (++visits > kListBudget) { VMX_PC_WHY(5); return 0; }
+            if (cur & kLeafBit) {
+                const uint32_t first = cur & kLeafStartMask, cnt = (cur >> kLeafCountShift) & 31u;
+                visits += cnt;
+                for (uint32_t i = 0; i < cnt && join == kClaimNone; ++i) {
+                    const uint32_t t = first + i;
+                    if (t == s0 || t == s1 || t == s2 || t == s3) continue;
+                    PcTri U;
+                    const PcClass k = pc_classify(c, cam_tris + (size_t)t * 16, U);
+                    if (k == kPcRejected) continue;
+                    if (k == kPcUnsure) { VMX_PC_WHY(6); return 0; }
+                    bool far = n > 0;
+                    uint32_t m = s0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+                    for (int j = 0; j < kListK && far && m != kClaimNone; ++j) {
+                        PcTri T;
+                        pc_classify(c, cam_tris + (size_t)m * 16, T);  // (kPcLive: it was when m joined)
+                        far = pc_farther(c, T, U);
+                        m = j == 0 ? s1 : (j == 1 ? s2 : s3);
+                    }
+                    if (!far) join = t;
+                }
+                if (join != kClaimNone) break;
+                if (sp == 0) break;
+                float unused;
+                stk.get(--sp, cur, unused);
+            } else {
+                const float *q = cam_inner + (size_t)cur * 16;
+                const bool h0 = pc_box_reached(c, q, q + 3, tcut), h1 = pc_box_reached(c, q + 6, q + 9, tcut);
+                uint32_t lref, rref;
+                __builtin_memcpy(&lref, q + 12, 4), __builtin_memcpy(&rref, q + 13, 4);
+                if (h0 && h1) {
+                    if (sp >= max_sp) return 0;
+                    stk.put(sp++, rref, 0.0f);
+                    cur = lref;
+                } else if (h0) {
+                    cur = lref;
+                } else if (h1) {
+                    cur = rref;
+                } else {
+                    if (sp == 0) break;
+                    float unused;
+                    stk.get(--sp, cur, unused);
+                }
+            }
+        }
+        if (join == kClaimNone) break;
+    }
+    if (n == 0) { VMX_PC_WHY(7); return 0; }
+    out[0] = s0, out[1] = s1, out[2] = s2, out[3] = s3;
+    return n;
+}
+
+// both planes of a pixel, as k_pixel_claims and the host program fill them: the claim, and the list of a pixel without one
+template <class Stack>
+VMX_PC_FN uint32_t pc_pixel_claim_and_list(const PcFilm &fm, uint32_t p, const float *cam_inner, const float *cam_tris,
+                                           uint32_t root_ref, Stack &stk, int max_sp, uint32_t *list_out) {
+    int cand, other;
+    const uint32_t c = pc_pixel_claim_cand(fm, p, cam_inner, cam_tris, root_ref, stk, max_sp, cand, other);
+    pc_pixel_list(fm, p, cam_inner, cam_tris, root_ref, stk, max_sp, c == kClaimNone ? cand : -2, other, list_out);
+    return c;
 }
 
 }  // namespace vmx

@@ -28,6 +28,7 @@
 #include "bvh_build.h"
 #include "vmx_device.h"
 #include "vmx_kernels.h"
+#include "pixel_claim.h"  // kListWords
 
 #ifndef VMX_LDS_PRIMARY
 #define VMX_LDS_PRIMARY 8  // LDS stack levels of the camera-ray kernel (A/B builds: make EXTRA=-DVMX_LDS_PRIMARY=n)

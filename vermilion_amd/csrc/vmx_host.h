@@ -141,6 +141,7 @@ struct Workspace {
     DevBuf<unsigned char> sort_tmp;
     DevBuf<unsigned char> cam_inner;                    // per-frame camera-relative scene tables: 8 node copies, then the triangles
     DevBuf<unsigned int> claims;                        // per-pixel claims of the run's frame (pixel_claim.h) + the number of claimed pixels
+    DevBuf<unsigned int> claim_lists;                   // ... and the list records of its pixels without a claim (kListWords words each)
     // passes that fuse their claimed pixels: the ordered lists of the pass's unclaimed and claimed slots, rebuilt per pass;
     // "unclaimed" bits per 64 slots; [popcounts | their exclusive scan | the two lists' lengths]; scan scratch
     DevBuf<unsigned int> unclaimed, claimed_slots, unclaimed_u32;
@@ -204,6 +205,7 @@ struct vmx_scene {
     float bounds_lo[3] = {0, 0, 0}, bounds_hi[3] = {1, 1, 1};  // vertex bounds (origin cells of the bounce reordering)
     vmx_timings timings{};  // per-kernel durations of the last render on this scene
     uint64_t fused_paths = 0;  // ... and its camera paths that took the fused route (vmx_fused_camera_paths)
+    uint64_t list_settled = 0;  // ... and its camera rays that a list claim settled (vmx_list_settled_rays)
     // device ray queries (vmx_query_device): allocated on the first query, then reused.  `done` is recorded after each
     // query's last kernel and waited on by the next one: one query at a time uses the workspace
     struct QueryWs {
@@ -423,6 +425,7 @@ struct RenderJob {
     uint32_t npix = 0, pipeline = 0;
     bool count = false, split_any = false, legacy = false, elide = false;
     bool claims_on = false;  // split passes may use per-pixel claims (pixel_claim.h): not counting, not eliding, reserved[0] bit 11 clear
+    bool lists_on = false;   // ... and the pixels without a claim get list claims (reserved[0] bit 13 clear)
     bool fuse_on = false;    // ... and a dense plain camera pass fuses its claimed pixels into k_shade<0> (reserved[0] bit 12 clear)
     uint32_t smax = 0, smax_alloc = 0;  // samples per pixel and pass: the most a pass takes / what the buffers are sized for
     uint32_t n_pad_max = 0, sub_cap = 0;
@@ -438,6 +441,7 @@ struct RenderJob {
     IdQueue qi[3];
     QueueDev q[2];  // first-generation kernels (A/B library) only
     const unsigned int *claims = nullptr;  // this run's claim table, or NULL: none was built (render_bind)
+    const unsigned int *claim_lists = nullptr;  // ... and its list records, or NULL
     // the schedule's state between passes
     bool initialised = false;  // the tile-ordered pixel list is uploaded and the per-pixel state zeroed
     uint32_t n_active = 0;

@@ -95,6 +95,10 @@ struct WorkDev {
     // camera rays: one claim word per local pixel (pixel_claim.h; k_pixel_claims) or NULL: a claimed pixel's rays take
     // one triangle test in k_trace_w<0> instead of the BVH walk
     const unsigned int *claims;
+    // ... and one list record (kListWords words) per local pixel or NULL: the rays of a pixel without a claim that
+    // pc_list_settle settles skip the walk too; list_ctr: the frame's counters (DevCounters::listed)
+    const unsigned int *claim_lists;
+    DevCounters *list_ctr;
     // fused claimed pixels (render_pass; plain dense camera pass with claims): k_raygen<0> and k_trace_w<0> work on the
     // ordered list of the pass's slots whose pixel has no claim (launch_slot_lists); k_shade<0, .., DENSE> is launched
     // twice, over that list and — `fused`: its CLAIMED form, which forms, tests and shades the rays itself — over the
@@ -196,8 +200,8 @@ int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, in
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
                          void *cam_tris, void *stream);
 // the per-pixel claims of a frame (pixel_claim.h) from the camera tables in wk: claims[local pixel], *n_claimed += the
-// pixels with a slot or a miss claim; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
-int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *n_claimed,
+// pixels with a slot or a miss claim; lists (or NULL: none): the list records of the pixels without one; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
+int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *lists, unsigned int *n_claimed,
                         LaunchCfg cfg, void *stream);
 int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
 int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);

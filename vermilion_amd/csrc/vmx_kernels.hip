@@ -1732,8 +1732,8 @@ struct ClaimStack {
 };
 __global__ void __launch_bounds__(256)
 k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, const float *__restrict__ cam_tris,
-               unsigned int *__restrict__ claims, unsigned int *n_claimed, uint32_t lds_levels, uint32_t overflow_entries,
-               void *overflow_stack) {
+               unsigned int *__restrict__ claims, unsigned int *__restrict__ lists, unsigned int *n_claimed, uint32_t lds_levels,
+               uint32_t overflow_entries, void *overflow_stack) {
     extern __shared__ uint2 lds_stack[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     ClaimStack stk;
@@ -1750,8 +1750,15 @@ k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, co
         const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
         if (x < fr.width && y < fr.local_rows) {
             const uint32_t lp = y * fr.width + x;
-            const uint32_t c = pc_pixel_claim(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk,
-                                              (int)(lds_levels + overflow_entries));
+            uint32_t c;
+            if (lists) {  // both planes: the list of a pixel without a claim (an empty one for the others)
+                uint32_t l[kListWords];
+                c = pc_pixel_claim_and_list(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk,
+                                            (int)(lds_levels + overflow_entries), l);
+                ((uint4 *)lists)[lp] = make_uint4(l[0], l[1], l[2], l[3]);
+            } else {
+                c = pc_pixel_claim(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk, (int)(lds_levels + overflow_entries));
+            }
             claims[lp] = c;
             n += c != kClaimNone ? 1u : 0u;
         }
@@ -2427,6 +2434,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
     // SORT: the ray's flag word; bit 31 set while the lane holds a finished ray that has not been sorted yet
     uint32_t rflags = 0;
     uint32_t out_lo = 0, out_hi = 0, n_rays = 0, n_hits = 0;  // (wave-uniform) reserved list entries; rays / triangle hits settled here
+    uint32_t n_listed = 0;  // (wave-uniform) camera rays settled by a list claim
     // camera rays: direction octant of the wave's rays if they all share it (else 8): selects the
     // per-octant copy of the node table (k_camera_tables) for wave-uniform steps
     uint32_t wave_octant = 8;
@@ -2617,9 +2625,11 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                 const bool take = cur == kIdle && rank < avail;
                 const uint32_t item = res_lo + rank;
                 res_lo = __builtin_amdgcn_readfirstlane(res_lo + min((uint32_t)__popcll(want), avail));
+                bool listed = false;  // this lane's ray was settled by its pixel's list
                 if (take) {
                     bool valid = true;
                     uint32_t claim = kClaimNone;  // (camera rays: the pixel's claim, pixel_claim.h)
+                    uint4 lrec = make_uint4(kClaimNone, kClaimNone, kClaimNone, kClaimNone);  // ... and its list
                     if (LIVE) {
                         pid = src * live_band(*wk.live_count) + item;  // list position
                     } else if (SRC == 0) {
@@ -2636,6 +2646,8 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         valid = s_idx < wk.n_active;
                         pid = path_id(wk, j, s_idx);
                         if (wk.claims && valid) claim = wk.claims[wk.active[s_idx]];
+                        // (a fused pass hands no claims on — its listed slots have none — but the lists, if the run has any)
+                        if (wk.claim_lists && valid && claim == kClaimNone) lrec = ((const uint4 *)wk.claim_lists)[wk.active[s_idx]];
                     } else {
                         pid = wk.qids.ids[(size_t)src * wk.qids.sub_capacity + item];
                     }
@@ -2666,11 +2678,24 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                         else hit_out[pid] = make_float2(best, __int_as_float(slot));
                         valid = false;
                     }
+                    if (SRC == 0 && !LIVE && valid && lrec.x != kClaimNone) {
+                        // the pixel's list: the ray's own test on its two to four members settles it where the nearest one
+                        // is clear of the others and of its box's faces (pc_list_settle); else the ray walks
+                        float t;
+                        uint32_t m;
+                        if (pc_list_settle((const float *)tris, lrec.x, lrec.y, lrec.z, lrec.w, dx, dy, dz, t, m)) {
+                            best = t, slot = (int)m;
+                            if (SORT) rflags |= 0x80000000u;
+                            else hit_out[pid] = make_float2(best, __int_as_float(slot));
+                            valid = false, listed = true;
+                        }
+                    }
                     if (valid) {
                         ray_start(dx, dy, dz, root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
                         exact = !(finite3(ix, iy, iz) && finite3(ox, oy, oz));
                     }
                 }
+                if (SRC == 0 && !LIVE && wk.claim_lists) n_listed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(listed));
                 if (SRC == 0 && !LIVE && SORT && wk.claims) {
                     if (__builtin_amdgcn_ballot_w64((rflags >> 31) != 0) != 0) sort_finished();
                 }
@@ -2742,6 +2767,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
         prof_t = __builtin_readcyclecounter();
 #endif
     }
+    if (SRC == 0 && !LIVE && lane == 0 && n_listed) atomicAdd(&wk.list_ctr->listed, (unsigned long long)n_listed);
     if (SORT) {
         sort_finished();
         float4 *__restrict__ rec = (float4 *)wk.out_rec;
@@ -3734,10 +3760,10 @@ int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pix
     return launch_status();
 }
 
-int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *n_claimed,
+int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *lists, unsigned int *n_claimed,
                         LaunchCfg cfg, void *stream) {
     hipLaunchKernelGGL(k_pixel_claims, dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, (hipStream_t)stream, sc, fr,
-                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, claims, n_claimed, wk.lds_entries, wk.overflow_entries,
+                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, claims, lists, n_claimed, wk.lds_entries, wk.overflow_entries,
                        wk.overflow_stack);
     return launch_status();
 }

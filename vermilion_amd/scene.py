@@ -92,7 +92,7 @@ def make_opts(seed=1, early_stop=True, sampling=L.VMX_SAMPLING_PARITY, rank=0, w
     o.rank, o.world, o.stripe_rows = int(rank), int(world), int(stripe_rows)
     o.samples_per_batch = int(samples_per_batch)
     o.collect_counters = 1 if collect_counters else 0
-    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims, | 0x1000 claimed pixels are not fused into the shading kernel
+    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims, | 0x1000 claimed pixels are not fused into the shading kernel, | 0x2000 no list claims
     o.reserved[1] = int(max_paths)     # paths in flight per pass (0 -> 16M)
     o.reserved[2] = int(tail_threshold)
     o.reserved[3] = int(refill_min)    # k_paths: refill when this many lanes idle (0 -> 16)
@@ -549,6 +549,23 @@ class Scene:
         formed and tested itself (claimed pixels of a fused pass)"""
         n = C.c_uint64(0)
         self._check(self._lib.vmx_fused_camera_paths(self._h, C.byref(n)))
+        return int(n.value)
+
+    def pixel_claim_lists(self, cam, opts):
+        """vmx_pixel_claim_lists: (claims [local_rows, W], list records uint32 [local_rows, W, 4], number of claimed pixels):
+        for a pixel without a claim up to four leaf-order slots, padded with 0xFFFFFFFF"""
+        rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
+        out = np.empty((rows, cam.image_res[0]), np.uint32)
+        lists = np.empty((rows, cam.image_res[0], 4), np.uint32)
+        n = C.c_uint32(0)
+        self._check(self._lib.vmx_pixel_claim_lists(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, lists.ctypes.data,
+                                                    C.byref(n)))
+        return out, lists, int(n.value)
+
+    def list_settled_rays(self):
+        """vmx_list_settled_rays: the camera rays of the last render on this scene that a list claim settled"""
+        n = C.c_uint64(0)
+        self._check(self._lib.vmx_list_settled_rays(self._h, C.byref(n)))
         return int(n.value)
 
     def render(self, cam, opts):
