@@ -15,7 +15,7 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough [--moving] [--textured] fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] [--textured] [--variance] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
@@ -34,6 +34,13 @@
 //   vmx_filter_apply_demodulated_device  the filter on colour / albedo, the albedo multiplied back
 // The accumulator is untouched: reprojection follows surface points, so textured history is valid.  fly_plain.ppm is
 // the same accumulated frame through vmx_filter_apply_device, where the checker on the flat walls is averaged away.
+//
+// --variance: the accumulator is made with VMX_TEMPORAL_MOMENTS and the accumulate and filter steps become
+//   vmx_temporal_accumulate_variance_device  the same accumulation, and the variance of every pixel's luminance
+//   vmx_filter_apply_variance_device         the filter's colour stop measured in standard deviations of that pixel
+// It composes with --moving (the motion records go to the variance call) and with --textured (the albedo plane goes to
+// the variance-guided call, which then works on colour / albedo as the demodulated call does).  The mean variance of each
+// frame is printed beside its history length.
 #include <dlfcn.h>
 
 #include <cmath>
@@ -96,10 +103,11 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool moving = false, textured = false;
+    bool moving = false, textured = false, variance = false;
     for (; argc > 1 && std::strncmp(argv[1], "--", 2) == 0; --argc, ++argv) {
         if (std::strcmp(argv[1], "--moving") == 0) moving = true;
         else if (std::strcmp(argv[1], "--textured") == 0) textured = true;
+        else if (std::strcmp(argv[1], "--variance") == 0) variance = true;
         else {
             std::fprintf(stderr, "flythrough: unknown option %s\n", argv[1]);
             return 1;
@@ -157,6 +165,8 @@ int main(int argc, char **argv) {
     vmx_temporal *plain = nullptr;
     void *d_pos[2] = {nullptr, nullptr}, *d_motion = nullptr, *d_acc_plain = nullptr, *d_hist_plain = nullptr;
     void *d_albedo = nullptr;  // --textured: the frame's albedo plane, float4 per pixel
+    void *d_var = nullptr;     // --variance: the variance of each pixel's luminance, one float per pixel
+    std::vector<float> var(variance ? (size_t)W * H : 0);
     std::vector<float> moved = pos, hist_plain(moving ? (size_t)W * H : 0);
     std::vector<unsigned char> rgba(npix * 4);
     std::vector<float> hist(npix);
@@ -164,9 +174,10 @@ int main(int argc, char **argv) {
     bool io_ok = true;
     bool hip_ok = hip.stream_create(&stream) == 0 && hip.malloc_(&d_frame, npix * 20) == 0 && hip.malloc_(&d_rec, npix * 64) == 0 &&
                   hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, npix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
-    if (hip_ok) rc = vmx_temporal_create(0, W, H, &temporal);
+    if (hip_ok) rc = vmx_temporal_create_ex(0, W, H, variance ? VMX_TEMPORAL_MOMENTS : 0u, &temporal);
     if (hip_ok && rc == VMX_OK) rc = vmx_filter_create(0, W, H, &filter);
     if (textured && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_albedo, npix * 16) == 0;
+    if (variance && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_var, npix * 4) == 0;
     if (moving && hip_ok && rc == VMX_OK) {
         hip_ok = hip.malloc_(&d_pos[0], pos.size() * 4) == 0 && hip.malloc_(&d_pos[1], pos.size() * 4) == 0 &&
                  hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0 && hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
@@ -208,8 +219,12 @@ int main(int argc, char **argv) {
                                               stream)) != VMX_OK)
             break;
         if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
-        if ((rc = vmx_temporal_accumulate_motion_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc, nullptr,
-                                                        d_hist, nullptr, stream)) != VMX_OK)
+        if (variance) {
+            if ((rc = vmx_temporal_accumulate_variance_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+                                                              nullptr, d_hist, d_var, nullptr, nullptr, stream)) != VMX_OK)
+                break;
+        } else if ((rc = vmx_temporal_accumulate_motion_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+                                                               nullptr, d_hist, nullptr, stream)) != VMX_OK)
             break;
         if (moving && (rc = vmx_temporal_accumulate_device(plain, &cam, d_rec, d_frame, d_acc_plain, nullptr, d_hist_plain, nullptr,
                                                            stream)) != VMX_OK)
@@ -226,12 +241,27 @@ int main(int argc, char **argv) {
                 }
                 if (!hip_ok) break;
             }
-            if ((rc = vmx_filter_apply_demodulated_device(filter, d_acc, d_albedo, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+            if (variance) {
+                if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, d_albedo, nullptr, d_rgba8, nullptr,
+                                                           VMX_SIGMA_LUMINANCE_DEFAULT, stream)) != VMX_OK)
+                    break;
+            } else if ((rc = vmx_filter_apply_demodulated_device(filter, d_acc, d_albedo, nullptr, d_rgba8, nullptr, stream)) != VMX_OK)
+                break;
+        } else if (variance) {
+            if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, nullptr, nullptr, d_rgba8, nullptr,
+                                                       VMX_SIGMA_LUMINANCE_DEFAULT, stream)) != VMX_OK)
+                break;
         } else if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK)
             break;
         if (!(hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(hist.data(), d_hist, npix * 4, 2) == 0)) break;
         double mean = 0;
         for (float n : hist) mean += n;
+        if (variance) {
+            if (!(hip_ok = hip.memcpy_(var.data(), d_var, npix * 4, 2) == 0)) break;
+            double mean_var = 0;
+            for (float v : var) mean_var += v;
+            std::printf("frame %u: mean luminance variance %.6f\n", i, mean_var / (double)npix);
+        }
         if (moving) {
             if (!(hip_ok = hip.memcpy_(hist_plain.data(), d_hist_plain, npix * 4, 2) == 0)) break;
             double mean_plain = 0;
@@ -257,7 +287,7 @@ int main(int argc, char **argv) {
     if (filter) vmx_filter_destroy(filter);
     if (temporal) vmx_temporal_destroy(temporal);
     if (plain) vmx_temporal_destroy(plain);
-    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo})
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo, d_var})
         if (p) hip.free_(p);
     if (stream) hip.stream_destroy(stream);
     vmx_scene_destroy(scene);

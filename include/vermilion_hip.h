@@ -704,6 +704,81 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
                                           void *d_rgba8, void *d_history_len, const vmx_temporal_params *params,
                                           void *stream);
 
+/* ---- variance-guided denoising: temporal luminance moments steer the filter -----------------------------
+ * The filter's colour stop above is one sigma_colour for every pixel: a pixel that has converged over 32 reprojected
+ * frames is blurred as hard as one disoccluded this frame, and a shading detail with no G-buffer edge behind it (a
+ * contact shadow, a light's falloff on a wall) goes at the rate of noise of its amplitude.  This is the variance
+ * estimate and the variance-driven edge stop of Schied et al. 2017 (SVGF): the accumulator carries the first and second
+ * moment of the luminance through its reprojection taps, a second kernel turns them into a per-pixel variance, and a
+ * filter call replaces the colour stop by the luminance difference measured in standard deviations.  The stop is
+ * rational, as the existing weights are; there are no transcendentals.  Everything is float, one rounding per written
+ * operation, left to right; `/` is correctly rounded, denormals are kept.
+ *   lum(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b
+ *
+ * Moments.  A handle made with VMX_TEMPORAL_MOMENTS keeps a fourth state plane of float2 (m1, m2): 2 x 56 B per pixel.
+ * vmx_temporal_accumulate_variance_device is vmx_temporal_accumulate_motion_device (colour, n', guide, X and camera are
+ * exactly what that call computes, d_motion may be NULL) and in addition, per pixel, l = lum(c) of the input frame:
+ *   in each of the four taps, right after sum_n, with the colour's ok and wt:
+ *     sum_m1 = sum_m1 + wt*m1_h(q);  sum_m2 = sum_m2 + wt*m2_h(q)                                          (from 0)
+ *   sum_w > 0:  h1 = sum_m1/sum_w;  h2 = sum_m2/sum_w;  m1' = h1 + (l - h1)*a;  m2' = h2 + (l*l - h2)*a   (the colour's a)
+ *   else, and on a first call and on a miss:  m1' = l;  m2' = l*l
+ * Variance, from the new state (n', guide n / z, m1', m2'), per pixel p:
+ *   vt = m2' - m1'*m1';  vt = vt > 0 ? vt : 0
+ *   n' >= min_history:  var = vt.  Otherwise a 7 x 7 window, dy = -3..3 (outer), dx = -3..3 (inner), q = p + (dx, dy); a
+ *   tap outside the image or with (z_q >= 0) != (z_p >= 0) is skipped;
+ *     p a hit:  d = n_p.x*n_q.x + n_p.y*n_q.y + n_p.z*n_q.z;  d = d > 0 ? d : 0;  normal_squarings times d = d*d;
+ *               t = (z_p - z_q) * (1.f/(sigma_depth*z_p));  w = d / (1.f + t*t)          p a miss:  w = 1.f
+ *     if w > 0 and finite:  s1 = s1 + w*m1'(q);  s2 = s2 + w*m2'(q);  sw = sw + w                           (from 0)
+ *   sw > 0:  a1 = s1/sw;  a2 = s2/sw;  vs = a2 - a1*a1;  vs = vs > 0 ? vs : 0;  var = vs * (min_history / n')
+ *   else:    var = vt
+ * A first frame has vt == 0 exactly, so its variance is all spatial, boosted by min_history.
+ * d_variance: W*H floats, non-NULL — it counts as an output, so d_out_rgbaz and d_rgba8 may both be NULL — DEVICE memory
+ * of the handle's device, 4-byte aligned, overlapping no other buffer of the call.  Every other rule is the motion
+ * call's, in its order of checks (vparams right after tparams, d_variance after d_in_rgbaz).  A handle without moments
+ * is refused (VMX_ERR_INVALID, "... VMX_TEMPORAL_MOMENTS ..."); on a moments handle the two calls above are
+ * VMX_ERR_INVALID, because they would leave the moments stale.  Reset and frames work on both kinds of handle.
+ * tests/variance_spec.py restates it; the kernels hold to it bit for bit.
+ * Out of scope: the progressive previews (a vmx_progressive handle keeps no second moment), the analytic spheres'
+ * motion, and a variance output of the filter. */
+#define VMX_TEMPORAL_MOMENTS 1u
+typedef struct vmx_variance_params {
+    float min_history;         /* finite, >= 1; default 4.f                       */
+    uint32_t normal_squarings; /* 0..8;         default 5                         */
+    float sigma_depth;         /* finite, > 0;  default 0.1f                      */
+    uint32_t reserved[5];      /* must be 0                                       */
+} vmx_variance_params;
+int vmx_variance_default_params(vmx_variance_params *out);
+/* vmx_temporal_create with flags: 0 (that call) or VMX_TEMPORAL_MOMENTS; any other bit is VMX_ERR_INVALID. */
+int vmx_temporal_create_ex(int device, uint32_t width, uint32_t height, uint32_t flags, vmx_temporal **out);
+int vmx_temporal_accumulate_variance_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit,
+                                            const void *d_motion /* or NULL */, const void *d_in_rgbaz,
+                                            void *d_out_rgbaz, void *d_rgba8, void *d_history_len, void *d_variance,
+                                            const vmx_temporal_params *tparams, const vmx_variance_params *vparams,
+                                            void *stream);
+/* The variance-guided filter call.  Arguments, order of checks, overlaps, in place, guide and stream ordering follow
+ * vmx_filter_apply_demodulated_device, with d_albedo NULL for the call without demodulation.  d_variance: W*H floats
+ * (what the call above writes), read only, non-NULL, 4-byte aligned, overlapping no written buffer.  sigma_luminance:
+ * finite, > 0 (VMX_SIGMA_LUMINANCE_DEFAULT); params->sigma_colour is checked as ever and not used.
+ * A dense pre-pass writes the filter's plane as (c.r, c.g, c.b, v):
+ *   without albedo:  c = the frame's r, g, b;  v = d_variance[p]
+ *   with albedo:     c. = frame. / am.  (am: the demodulated call's clamped albedo);  la = lum(am);
+ *                    v = d_variance[p] / (la*la)        (exact only for a grey albedo: the variance is the luminance's)
+ * Every iteration is the restatement of "G-buffer-guided denoising" reading that plane, with these changes only:
+ *   per pixel p:  vbar = sum of (k[dy+1]*k[dx+1]) * v(p + (dx, dy)),  dy = -1..1 (outer), dx = -1..1 (inner), from 0 in
+ *                 tap order, k = {0.25f, 0.5f, 0.25f}, at one pixel's distance whatever the step; a neighbour outside
+ *                 the image takes v_p;  den = (sigma_luminance*sigma_luminance)*vbar + VMX_VARIANCE_EPS
+ *   per tap:      dl = lum(c_p) - lum(c_q);  w = num / (g * (1.f + (dl*dl)/den))      (num, g, skip rules unchanged)
+ *                 if w > 0 and finite:  sum_c. = sum_c. + w*c_q.;  sum_v = sum_v + (w*w)*v_q;  sum_w = sum_w + w
+ *   sum_w > 0:    out. = sum_c./sum_w;  v_out = sum_v/(sum_w*sum_w)           else:  out = c_p, v_out = v_p
+ * sigma_luminance does not shrink over the iterations: the variance does, by propagation.  kz = sigma_depth*(float)s as
+ * before.  The last iteration writes the caller's buffers as the plain call's does — with albedo the result is
+ * multiplied by am_p first — and drops the propagated variance. */
+#define VMX_VARIANCE_EPS 1e-10f
+#define VMX_SIGMA_LUMINANCE_DEFAULT 4.f
+int vmx_filter_apply_variance_device(vmx_filter *f, const void *d_in_rgbaz, const void *d_variance,
+                                     const void *d_albedo /* or NULL */, void *d_out_rgbaz, void *d_rgba8,
+                                     const vmx_filter_params *params, float sigma_luminance, void *stream);
+
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers
  * back to back, each padded to `rank_stride_floats`; writes the W*H*5 frame.

@@ -34,6 +34,9 @@ VMX_QUERY_ANY = 1
 VMX_QUERY_COLLISION = 2
 VMX_QUERY_FETCH_PER_LANE = 0x100
 VMX_ALBEDO_FLOOR = 2.0 ** -10  # the demodulated filter's lower clamp of an albedo channel
+VMX_TEMPORAL_MOMENTS = 1  # vmx_temporal_create_ex: the handle keeps luminance moments (vmx_temporal_accumulate_variance_device)
+VMX_VARIANCE_EPS = 1e-10  # the variance-guided filter's floor of sigma_luminance^2 * variance
+VMX_SIGMA_LUMINANCE_DEFAULT = 4.0
 VMX_UPDATE_REFIT = 0
 VMX_UPDATE_REBUILD = 1
 
@@ -212,6 +215,19 @@ class TemporalParams(C.Structure):
                 "reserved": list(self.reserved)}
 
 
+class VarianceParams(C.Structure):
+    _fields_ = [
+        ("min_history", C.c_float),
+        ("normal_squarings", C.c_uint32),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+    def as_dict(self):
+        return {"min_history": self.min_history, "normal_squarings": self.normal_squarings,
+                "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
+
+
 # every symbol include/vermilion_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -273,6 +289,11 @@ SYMBOLS = {
     "vmx_temporal_accumulate_motion_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P,
                                                         C.POINTER(TemporalParams), _P]),
     "vmx_motion_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_int, _P]),
+    "vmx_variance_default_params": (C.c_int, [C.POINTER(VarianceParams)]),
+    "vmx_temporal_create_ex": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "vmx_temporal_accumulate_variance_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P,
+                                                          C.POINTER(TemporalParams), C.POINTER(VarianceParams), _P]),
+    "vmx_filter_apply_variance_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(FilterParams), C.c_float, _P]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

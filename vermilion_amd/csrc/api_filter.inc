@@ -50,12 +50,12 @@ static int filter_guide_enqueue(vmx_filter *f, const void *d_rayhit, hipStream_t
 // the iterations of one call on `s`; the caller holds f->mu and has checked arguments and pointers.  albedo: the
 // demodulated call's plane (float4 per pixel) or NULL
 static int filter_enqueue(vmx_filter *f, FilterSrc src, float *out, void *rgba8, const vmx_filter_params &prm, hipStream_t s,
-                          const void *albedo = nullptr) {
+                          const void *albedo = nullptr, const float *variance = nullptr, float sigma_luminance = 0.f) {
     if (int rc = f->done.wait(s)) return rc;  // after the previous call on this handle
     const size_t npix = (size_t)f->width * f->height;
     // one iteration in place would read neighbours another block has already replaced: it filters a copy of the frame
     // (a demodulated call's taps read the pre-pass's plane, and its last iteration only its own pixel of the frame)
-    if (prm.iterations == 1 && src.frame && src.frame == out && !albedo) {
+    if (prm.iterations == 1 && src.frame && src.frame == out && !albedo && !variance) {
         HIP_TRY(hipMemcpyAsync(f->planes.p, src.frame, npix * 20, hipMemcpyDeviceToDevice, s));
         src.frame = (const float *)f->planes.p;
     }
@@ -66,7 +66,11 @@ static int filter_enqueue(vmx_filter *f, FilterSrc src, float *out, void *rgba8,
     a.src = src;
     a.albedo = albedo;
     unsigned char *plane[2] = {f->planes.p, f->planes.p + npix * 16};
-    if (albedo) {  // frame / albedo into the plane iteration 0 reads, as if it were iteration -1's output
+    a.sl2 = sigma_luminance * sigma_luminance;
+    if (variance) {  // (frame [/ albedo], variance) into the plane iteration 0 reads
+        a.out_plane = plane[1];
+        LAUNCH_TRY(launch_variance_pack(a, variance, s));
+    } else if (albedo) {  // frame / albedo into the plane iteration 0 reads, as if it were iteration -1's output
         a.out_plane = plane[1];
         LAUNCH_TRY(launch_demod_divide(a, s));
     }
@@ -76,12 +80,15 @@ static int filter_enqueue(vmx_filter *f, FilterSrc src, float *out, void *rgba8,
         a.isc2 = 1.f / (sc * sc);
         a.kz = prm.sigma_depth * (float)a.step;
         sc = sc * 0.5f;
-        a.first = it == 0 && !albedo, a.last = it + 1 == prm.iterations;
+        a.first = it == 0 && !albedo && !variance, a.last = it + 1 == prm.iterations;
         a.in_plane = a.first ? nullptr : plane[(it + 1) & 1];
         a.out_plane = a.last ? nullptr : plane[it & 1];
         a.out_rgbaz = a.last ? out : nullptr;
         a.rgba8 = a.last ? rgba8 : nullptr;
-        LAUNCH_TRY(launch_atrous(a, s));
+        if (variance)
+            LAUNCH_TRY(launch_atrous_var(a, s));
+        else
+            LAUNCH_TRY(launch_atrous(a, s));
     }
     return f->done.record(s);
 }
@@ -126,17 +133,23 @@ int vmx_filter_set_guide_device(vmx_filter *f, const void *d_rayhit, void *strea
     return filter_guide_enqueue(f, d_rayhit, (hipStream_t)stream);
 }
 
-// vmx_filter_apply_device and, demod, vmx_filter_apply_demodulated_device
+// vmx_filter_apply_device and, demod, vmx_filter_apply_demodulated_device and, variance, vmx_filter_apply_variance_device
+// (whose d_albedo may be NULL: demod says whether it is there)
 static int filter_apply(vmx_filter *f, const void *d_in_rgbaz, bool demod, const void *d_albedo, void *d_out_rgbaz, void *d_rgba8,
-                        const vmx_filter_params *params, void *stream) {
+                        const vmx_filter_params *params, void *stream, bool variance = false, const void *d_variance = nullptr,
+                        float sigma_luminance = 0.f) {
     // checks that need no device, in this order so that each can be seen alone; the handle comes last
     vmx_filter_params prm;
     if (int rc = filter_params(params, prm)) return rc;
+    if (variance && !(std::isfinite(sigma_luminance) && sigma_luminance > 0.f))
+        return fail(VMX_ERR_INVALID, "sigma_luminance must be finite and > 0");
     if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
+    if (variance && !d_variance) return fail(VMX_ERR_INVALID, "NULL d_variance");
     if (demod && !d_albedo) return fail(VMX_ERR_INVALID, "NULL d_albedo");
     if (!d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
     if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8) & 3u)
         return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz and d_rgba8 must be 4-byte aligned");
+    if ((uintptr_t)d_variance & 3u) return fail(VMX_ERR_INVALID, "d_variance must be 4-byte aligned");
     if (demod && ((uintptr_t)d_albedo & 15u)) return fail(VMX_ERR_INVALID, "d_albedo must be 16-byte aligned");
     if (!f) return fail(VMX_ERR_INVALID, "NULL handle");
     std::lock_guard<std::mutex> lock(f->mu);
@@ -156,13 +169,19 @@ static int filter_apply(vmx_filter *f, const void *d_in_rgbaz, bool demod, const
             for (int j = 1; j < 3; ++j)
                 if (lo[j] && (uintptr_t)d_albedo < lo[j] + len[j] && lo[j] < (uintptr_t)d_albedo + npix * 16)
                     return fail(VMX_ERR_INVALID, "d_albedo overlaps d_out_rgbaz or d_rgba8");
+        // the variance is read by the pre-pass, before anything is written; still, it is an input and may meet no output
+        if (variance)
+            for (int j = 1; j < 3; ++j)
+                if (lo[j] && (uintptr_t)d_variance < lo[j] + len[j] && lo[j] < (uintptr_t)d_variance + npix * 4)
+                    return fail(VMX_ERR_INVALID, "d_variance overlaps d_out_rgbaz or d_rgba8");
     }
     if (!f->guide_set) return fail(VMX_ERR_INVALID, "no guide: call vmx_filter_set_guide_device first");
     HIP_TRY(hipSetDevice(f->device));
-    if (int rc = check_device_ptrs(f->device, {{d_in_rgbaz, "d_in_rgbaz"}, {d_albedo, "d_albedo"}, {d_out_rgbaz, "d_out_rgbaz"}, {d_rgba8, "d_rgba8"}})) return rc;
+    if (int rc = check_device_ptrs(f->device, {{d_in_rgbaz, "d_in_rgbaz"}, {d_albedo, "d_albedo"}, {d_out_rgbaz, "d_out_rgbaz"}, {d_rgba8, "d_rgba8"}, {d_variance, "d_variance"}})) return rc;
     FilterSrc src{};
     src.frame = (const float *)d_in_rgbaz;
-    return filter_enqueue(f, src, (float *)d_out_rgbaz, d_rgba8, prm, (hipStream_t)stream, d_albedo);
+    return filter_enqueue(f, src, (float *)d_out_rgbaz, d_rgba8, prm, (hipStream_t)stream, d_albedo, (const float *)d_variance,
+                          sigma_luminance);
 }
 
 int vmx_filter_apply_device(vmx_filter *f, const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8,
@@ -173,6 +192,13 @@ int vmx_filter_apply_device(vmx_filter *f, const void *d_in_rgbaz, void *d_out_r
 int vmx_filter_apply_demodulated_device(vmx_filter *f, const void *d_in_rgbaz, const void *d_albedo, void *d_out_rgbaz,
                                         void *d_rgba8, const vmx_filter_params *params, void *stream) {
     return filter_apply(f, d_in_rgbaz, true, d_albedo, d_out_rgbaz, d_rgba8, params, stream);
+}
+
+int vmx_filter_apply_variance_device(vmx_filter *f, const void *d_in_rgbaz, const void *d_variance, const void *d_albedo,
+                                     void *d_out_rgbaz, void *d_rgba8, const vmx_filter_params *params, float sigma_luminance,
+                                     void *stream) {
+    return filter_apply(f, d_in_rgbaz, d_albedo != nullptr, d_albedo, d_out_rgbaz, d_rgba8, params, stream, true, d_variance,
+                        sigma_luminance);
 }
 
 } /* extern "C" */

@@ -6,6 +6,7 @@ struct VMX_OPAQUE vmx_temporal {
     int device = 0;
     uint32_t width = 0, height = 0;
     DevBuf<unsigned char> state[2];  // three float4 planes per buffer: (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -)
+    bool moments = false;            // VMX_TEMPORAL_MOMENTS: a fourth plane of float2 (m1, m2) follows them
     int cur = 0;                     // the buffer the last call wrote
     bool has_history = false;        // false after create and reset: the next call is a first call
     TemporalCam hist_cam{};          // the last call's camera
@@ -30,6 +31,26 @@ static int temporal_params(const vmx_temporal_params *in, vmx_temporal_params &o
     return VMX_OK;
 }
 
+static const vmx_variance_params kVarianceDefaults = {4.f, 5u, 0.1f, {0u, 0u, 0u, 0u, 0u}};
+
+static int variance_params(const vmx_variance_params *in, vmx_variance_params &out) {
+    out = in ? *in : kVarianceDefaults;
+    if (!(std::isfinite(out.min_history) && out.min_history >= 1.f))
+        return fail(VMX_ERR_INVALID, "vmx_variance_params: min_history must be finite and >= 1");
+    if (out.normal_squarings > 8) return fail(VMX_ERR_INVALID, "vmx_variance_params: normal_squarings must be 0..8");
+    if (!(std::isfinite(out.sigma_depth) && out.sigma_depth > 0.f))
+        return fail(VMX_ERR_INVALID, "vmx_variance_params: sigma_depth must be finite and > 0");
+    for (uint32_t r : out.reserved)
+        if (r) return fail(VMX_ERR_INVALID, "vmx_variance_params: reserved words must be 0");
+    return VMX_OK;
+}
+
+int vmx_variance_default_params(vmx_variance_params *out) {
+    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    *out = kVarianceDefaults;
+    return VMX_OK;
+}
+
 int vmx_temporal_default_params(vmx_temporal_params *out) {
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
     *out = kTemporalDefaults;
@@ -37,8 +58,13 @@ int vmx_temporal_default_params(vmx_temporal_params *out) {
 }
 
 int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_temporal **out) {
+    return vmx_temporal_create_ex(device, width, height, 0u, out);
+}
+
+int vmx_temporal_create_ex(int device, uint32_t width, uint32_t height, uint32_t flags, vmx_temporal **out) {
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
     *out = nullptr;
+    if (flags & ~VMX_TEMPORAL_MOMENTS) return fail(VMX_ERR_INVALID, "vmx_temporal_create_ex: unknown flags");
     if (width == 0 || height == 0) return fail(VMX_ERR_INVALID, "image resolution must be non-zero");
     if ((uint64_t)width * height > 0x7fffffffull / 8) return fail(VMX_ERR_INVALID, "image too large");
     int ndev = 0;
@@ -49,8 +75,9 @@ int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_tempora
     std::unique_ptr<vmx_temporal> t(new (std::nothrow) vmx_temporal);
     if (!t) return fail(VMX_ERR_NOMEM, "out of host memory");
     t->device = device, t->width = width, t->height = height;
-    const size_t npix = (size_t)width * height;
-    if (t->state[0].ensure(npix * 48) || t->state[1].ensure(npix * 48))
+    t->moments = (flags & VMX_TEMPORAL_MOMENTS) != 0;
+    const size_t npix = (size_t)width * height, per_pixel = t->moments ? 56 : 48;
+    if (t->state[0].ensure(npix * per_pixel) || t->state[1].ensure(npix * per_pixel))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the temporal state");
     *out = t.release();
     return VMX_OK;
@@ -88,20 +115,27 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
                                                  params, stream);
 }
 
-int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
-                                          const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
-                                          const vmx_temporal_params *params, void *stream) {
+// the three accumulate entries; variance: vmx_temporal_accumulate_variance_device, whose d_variance is an output
+static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
+                               const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len, bool variance,
+                               void *d_variance, const vmx_temporal_params *params, const vmx_variance_params *vparams,
+                               void *stream) {
     // checks that need no device, in the filter's order so that each can be seen alone; the handle comes last
     vmx_temporal_params prm;
     if (int rc = temporal_params(params, prm)) return rc;
+    vmx_variance_params vprm = kVarianceDefaults;
+    if (variance)
+        if (int rc = variance_params(vparams, vprm)) return rc;
     if (!cam) return fail(VMX_ERR_INVALID, "NULL camera");
     if (!d_rayhit) return fail(VMX_ERR_INVALID, "NULL d_rayhit");
     if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
-    if (!d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
+    if (variance && !d_variance) return fail(VMX_ERR_INVALID, "NULL d_variance");
+    if (!variance && !d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
     if ((uintptr_t)d_rayhit & 15u) return fail(VMX_ERR_INVALID, "d_rayhit must be 16-byte aligned");
     if ((uintptr_t)d_motion & 15u) return fail(VMX_ERR_INVALID, "d_motion must be 16-byte aligned");
     if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8 | (uintptr_t)d_history_len) & 3u)
         return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len must be 4-byte aligned");
+    if ((uintptr_t)d_variance & 3u) return fail(VMX_ERR_INVALID, "d_variance must be 4-byte aligned");
     FrameDev fr;
     {
         const vmx_opts none{};  // (make_frame reads a camera's opts too: the defaults of a zeroed struct)
@@ -109,6 +143,10 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
     }
     if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
     std::lock_guard<std::mutex> lock(t->mu);
+    if (variance && !t->moments)
+        return fail(VMX_ERR_INVALID, "the handle keeps no moments: create it with vmx_temporal_create_ex(.., VMX_TEMPORAL_MOMENTS, ..)");
+    if (!variance && t->moments)
+        return fail(VMX_ERR_INVALID, "a VMX_TEMPORAL_MOMENTS handle takes vmx_temporal_accumulate_variance_device only (this call would leave its moments stale)");
     if (fr.width != t->width || fr.height != t->height)
         return fail(VMX_ERR_INVALID, "cam->image_res is " + std::to_string(fr.width) + " x " + std::to_string(fr.height) +
                                          ", the handle's frames are " + std::to_string(t->width) + " x " + std::to_string(t->height));
@@ -127,10 +165,17 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
                 if (lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i])
                     return fail(VMX_ERR_INVALID, "d_rayhit, d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len overlap (only d_out_rgbaz == d_in_rgbaz may)");
             }
+        if (variance) {  // (it may meet no other buffer of the call)
+            const uintptr_t v = (uintptr_t)d_variance;
+            bool meets = d_motion && v < (uintptr_t)d_motion + npix * 32 && (uintptr_t)d_motion < v + npix * 4;
+            for (int i = 0; i < 5; ++i) meets = meets || (lo[i] && v < lo[i] + len[i] && lo[i] < v + npix * 4);
+            if (meets) return fail(VMX_ERR_INVALID, "d_variance overlaps another buffer of the call");
+        }
     }
     HIP_TRY(hipSetDevice(t->device));
     if (int rc = check_device_ptrs(t->device, {{d_rayhit, "d_rayhit"}, {d_in_rgbaz, "d_in_rgbaz"}, {d_out_rgbaz, "d_out_rgbaz"},
-                                               {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}, {d_motion, "d_motion"}}))
+                                               {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}, {d_motion, "d_motion"},
+                                               {d_variance, "d_variance"}}))
         return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = t->done.wait(s)) return rc;  // after the previous call on this handle
@@ -146,7 +191,15 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
     a.out_rgbaz = (float *)d_out_rgbaz, a.rgba8 = d_rgba8, a.history_len = (float *)d_history_len;
     a.first = !t->has_history;
     a.motion = d_motion;
+    a.moments = t->moments;
     LAUNCH_TRY(launch_temporal(a, s));
+    if (variance) {
+        VariancePass v{};
+        v.width = t->width, v.height = t->height;
+        v.squarings = vprm.normal_squarings, v.min_history = vprm.min_history, v.sigma_depth = vprm.sigma_depth;
+        v.state = a.new_state, v.variance = (float *)d_variance;
+        LAUNCH_TRY(launch_variance(v, s));
+    }
     if (int rc = t->done.record(s)) {
         // the next call could not be ordered after this kernel: wait for it here and leave the history as it was (the
         // kernel wrote the other buffer only)
@@ -155,6 +208,21 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
     }
     t->cur ^= 1, t->has_history = true, t->hist_cam = a.cam, t->frames += 1;
     return VMX_OK;
+}
+
+int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
+                                          const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                                          const vmx_temporal_params *params, void *stream) {
+    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, false, nullptr,
+                               params, nullptr, stream);
+}
+
+int vmx_temporal_accumulate_variance_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
+                                            const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                                            void *d_variance, const vmx_temporal_params *params,
+                                            const vmx_variance_params *vparams, void *stream) {
+    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, true, d_variance,
+                               params, vparams, stream);
 }
 
 } /* extern "C" */

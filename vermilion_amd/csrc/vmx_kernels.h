@@ -263,12 +263,19 @@ struct FilterPass {  // one iteration
     float *out_rgbaz;      // the last iteration's outputs, either may be NULL
     void *rgba8;
     bool first, last;
+    float sl2;           // the variance-guided call: sigma_luminance * sigma_luminance (in the padding before the next pointer,
+                         // so that every other member is where it was); its planes are (r, g, b, v)
     const void *albedo;  // float4 (a.rgb, -) per pixel or NULL: the demodulated call (last, so that every other member is where it was)
 };
+static_assert(sizeof(FilterPass) == 128, "FilterPass: a member moved (the kernels' argument offsets would)");
 int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *stream);
 int launch_atrous(const FilterPass &pass, void *stream);
 // the demodulated call's pre-pass: pass.src / pass.albedo into pass.out_plane, which the first iteration then reads as a plane
 int launch_demod_divide(const FilterPass &pass, void *stream);
+// the variance-guided call (vmx_variance.inc): its pre-pass, (pass.src [/ pass.albedo], variance) into pass.out_plane, and
+// one iteration from pass.in_plane
+int launch_variance_pack(const FilterPass &pass, const float *variance, void *stream);
+int launch_atrous_var(const FilterPass &pass, void *stream);
 // the albedo plane of a camera (vmx_albedo.inc; the arithmetic is stated in include/vermilion_hip.h): sample q.sample
 // of a run of n — k_query<kQueryCastCamera> (per-lane fetch) with cfg into `rec` (64 bytes per pixel, q.n = W * H), then k_albedo_finish
 // into `plane` (float4 per pixel); first / last: of the run
@@ -293,8 +300,18 @@ struct TemporalPass {  // one call
     float *history_len;
     bool first;
     const void *motion;    // vmx_motion per pixel or NULL (last, so that every other member is where it was); not read by a first call
+    bool moments;          // a fourth plane of float2 (m1, m2) follows the three in both states (after `motion`, for the same reason)
 };
 int launch_temporal(const TemporalPass &pass, void *stream);
+// the variance of a moments state (vmx_variance.inc; the arithmetic is stated in include/vermilion_hip.h)
+struct VariancePass {
+    uint32_t width, height;
+    uint32_t squarings;     // normal_squarings
+    float min_history, sigma_depth;
+    const void *state;      // the state k_temporal<.., MOMENTS> just wrote: (c.rgb, n') (n.xyz, z) (X.xyz, -) and float2 (m1, m2)
+    float *variance;        // W*H floats
+};
+int launch_variance(const VariancePass &pass, void *stream);
 // motion records for refitted geometry (vmx_motion.inc; the arithmetic is stated in include/vermilion_hip.h)
 constexpr uint32_t kMotionMoved = 1u;  // VMX_MOTION_MOVED
 int launch_motion(const void *rayhit, uint32_t n, const float *pos_now, const float *pos_prev, const float *nrm_prev,

@@ -20,6 +20,10 @@
 //               (nh, -) of vmx_motion.inc: the history is looked up where the surface point was (proj of Xh in the
 //               previous camera) and tested against what was there (nh, Xh); without it Xh, nh are the record's own X, n_p
 //               and the instantiation is the one there was before motion records.  A first call ignores them.
+//               MOMENTS: vmx_temporal_accumulate_variance_device — a fourth state plane of float2 (m1, m2), the first and
+//               second moment of the input's luminance: one float2 load per tap (same ok, same wt as the colour) and one
+//               float2 store; k_variance (vmx_variance.inc) turns them into a variance.  Without it the instantiations
+//               are the instruction streams they were before the parameter.
 struct TemporalProj {
     float u, w;
     bool front;
@@ -38,7 +42,7 @@ __device__ __forceinline__ TemporalProj temporal_proj(const TemporalCam &cam, fl
     return r;
 }
 
-template <bool FIRST, bool MOTION>
+template <bool FIRST, bool MOTION, bool MOMENTS = false>
 __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
     __shared__ float s_px[kFilterBlock * 5];
     const uint32_t W = a.width, H = a.height;
@@ -67,6 +71,8 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
         const bool hit = (__float_as_uint(rc.w) & 1u) != 0;
         const size_t npix = (size_t)W * H;
         float o0 = c0, o1 = c1, o2 = c2, n_new = 1.f;
+        const float lum = MOMENTS ? (0.2126f * c0 + 0.7152f * c1) + 0.0722f * c2 : 0.f;
+        float m1 = lum, m2 = lum * lum;
         if (!FIRST) {
             float Xhx = ra.x, Xhy = ra.y, Xhz = ra.z, mnx = rb.x, mny = rb.y, mnz = rb.z;
             if (MOTION) {
@@ -86,7 +92,8 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
             const int x0i = (int)(inrange ? x0 : 0.f), y0i = (int)(inrange ? y0 : 0.f);
             const float zz = a.tol2 * (ra.w * ra.w);
             const float4 *old_c = (const float4 *)a.old_state, *old_g = old_c + npix, *old_x = old_g + npix;
-            float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumn = 0.f, sumw = 0.f;
+            const float2 *old_m = (const float2 *)(old_x + npix);
+            float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumn = 0.f, sumw = 0.f, summ1 = 0.f, summ2 = 0.f;
 #pragma unroll
             for (int dy = 0; dy <= 1; ++dy) {
 #pragma unroll
@@ -105,6 +112,11 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
                     sum1 = ok ? sum1 + wt * hc.y : sum1;
                     sum2 = ok ? sum2 + wt * hc.z : sum2;
                     sumn = ok ? sumn + wt * hc.w : sumn;
+                    if (MOMENTS) {
+                        const float2 hm = old_m[q];
+                        summ1 = ok ? summ1 + wt * hm.x : summ1;
+                        summ2 = ok ? summ2 + wt * hm.y : summ2;
+                    }
                     sumw = ok ? sumw + wt : sumw;
                 }
             }
@@ -117,11 +129,17 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
             o1 = any ? h1 + (c1 - h1) * al : c1;
             o2 = any ? h2 + (c2 - h2) * al : c2;
             n_new = any ? n1 : 1.f;
+            if (MOMENTS) {
+                const float g1 = summ1 / sumw, g2 = summ2 / sumw;
+                m1 = any ? g1 + (lum - g1) * al : m1;
+                m2 = any ? g2 + (lum * lum - g2) * al : m2;
+            }
         }
         float4 *new_c = (float4 *)a.new_state, *new_g = new_c + npix, *new_x = new_g + npix;
         new_c[p] = make_float4(o0, o1, o2, n_new);
         new_g[p] = hit ? make_float4(rb.x, rb.y, rb.z, ra.w) : make_float4(0.f, 0.f, 0.f, -1.f);
         new_x[p] = make_float4(ra.x, ra.y, ra.z, 0.f);
+        if (MOMENTS) ((float2 *)(new_x + npix))[p] = make_float2(m1, m2);
         v[0] = o0, v[1] = o1, v[2] = o2;  // (v[3], v[4]: alpha and depth, the input's bits)
         if (a.rgba8) ((uchar4 *)a.rgba8)[p] = quantized_pixel(v);
         if (a.history_len) a.history_len[p] = n_new;
@@ -139,7 +157,14 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
 int launch_temporal(const TemporalPass &a, void *stream) {
     if (a.width == 0 || a.height == 0) return 0;
     const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    if (a.first)
+    if (a.moments) {
+        if (a.first)
+            hipLaunchKernelGGL((k_temporal<true, false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+        else if (a.motion)
+            hipLaunchKernelGGL((k_temporal<false, true, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL((k_temporal<false, false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
+    } else if (a.first)
         hipLaunchKernelGGL((k_temporal<true, false>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
     else if (a.motion)
         hipLaunchKernelGGL((k_temporal<false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);

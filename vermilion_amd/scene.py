@@ -130,6 +130,19 @@ def make_temporal_params(normal_min=None, plane_tol=None, max_history=None):
     return p
 
 
+def make_variance_params(min_history=None, normal_squarings=None, sigma_depth=None):
+    """vmx_variance_params: the library's defaults (vmx_variance_default_params) with the given fields replaced"""
+    p = L.VarianceParams()
+    L.check(L.lib().vmx_variance_default_params(C.byref(p)))
+    if min_history is not None:
+        p.min_history = float(min_history)
+    if normal_squarings is not None:
+        p.normal_squarings = int(normal_squarings)
+    if sigma_depth is not None:
+        p.sigma_depth = float(sigma_depth)
+    return p
+
+
 def _frame_tensor(x, name, dtype, shape, dev):
     """an output or input of the device filter / previews as the ABI takes it, or a ValueError"""
     if not _is_tensor(x):
@@ -769,19 +782,28 @@ class Filter:
             self._check(self._lib.vmx_filter_set_guide_device(self._h, C.c_void_p(raw.data_ptr()),
                                                               C.c_void_p(run.cuda_stream)))
 
-    def apply(self, rgbaz, out=None, rgba8=None, params=None, stream=None, albedo=None):
+    def apply(self, rgbaz, out=None, rgba8=None, params=None, stream=None, albedo=None, variance=None,
+              sigma_luminance=L.VMX_SIGMA_LUMINANCE_DEFAULT):
         """vmx_filter_apply_device: filters the float32 [height, width, 5] frame `rgbaz` into `out` (same shape; may be
         `rgbaz` itself) and / or `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is made.  All are
         contiguous torch tensors on the filter's device: anything else is a ValueError, never a copy through the host.
         params: make_filter_params(...), default the library's.  `albedo` (vmx_filter_apply_demodulated_device): what
         Scene.albedo_camera made for the frame's camera, float32 [height, width, 4], 16-byte aligned, read only — the
         filter then works on colour / albedo and multiplies the albedo back, so textures survive; None is the call
-        without.  Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
+        without.  `variance` (vmx_filter_apply_variance_device): what Temporal.accumulate(..., variance=...) wrote for this
+        frame, float32 [height, width], read only — the colour stop is then the luminance difference in standard
+        deviations, `sigma_luminance` of them (params.sigma_colour is not used); it composes with `albedo`.
+        Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
         import torch
         dev = torch.device("cuda", self.device)
         _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
         if albedo is not None:
             _albedo_tensor(albedo, "albedo", self.shape, dev)
+        if variance is not None:
+            _frame_tensor(variance, "variance", torch.float32, self.shape, dev)
+            sigma_luminance = float(sigma_luminance)
+            if not (0.0 < sigma_luminance < float("inf")):
+                raise ValueError("sigma_luminance must be finite and > 0")
         if out is None and rgba8 is None:
             out = torch.empty_like(rgbaz)
         if out is not None:
@@ -791,7 +813,10 @@ class Filter:
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
         with _SideStream(dev, stream) as run:
             prm, s = None if params is None else C.byref(params), C.c_void_p(run.cuda_stream)
-            if albedo is None:
+            if variance is not None:
+                self._check(self._lib.vmx_filter_apply_variance_device(self._h, ptr(rgbaz), ptr(variance), ptr(albedo),
+                                                                       ptr(out), ptr(rgba8), prm, sigma_luminance, s))
+            elif albedo is None:
                 self._check(self._lib.vmx_filter_apply_device(self._h, ptr(rgbaz), ptr(out), ptr(rgba8), prm, s))
             else:
                 self._check(self._lib.vmx_filter_apply_demodulated_device(self._h, ptr(rgbaz), ptr(albedo), ptr(out),
@@ -802,15 +827,21 @@ class Filter:
 class Temporal:
     """One vmx_temporal handle: temporal accumulation (include/vermilion_hip.h) of [height, width] frames on `device`.
     `accumulate` reprojects the frames accumulated so far into the new camera through the new frame's G-buffer and
-    blends the new frame in; `reset` forgets them."""
+    blends the new frame in; `reset` forgets them.  moments=True (vmx_temporal_create_ex with VMX_TEMPORAL_MOMENTS): the
+    handle also carries the luminance's first and second moment, and every `accumulate` writes a per-pixel variance."""
 
-    def __init__(self, width, height, device=0, lib=None):
+    def __init__(self, width, height, device=0, lib=None, moments=False):
         self._lib = lib if lib is not None else L.lib()
         self._h = None
         self.device = int(device)
         self.shape = (int(height), int(width))
+        self.moments = bool(moments)
         h = C.c_void_p()
-        self._check(self._lib.vmx_temporal_create(self.device, int(width), int(height), C.byref(h)))
+        if self.moments:
+            self._check(self._lib.vmx_temporal_create_ex(self.device, int(width), int(height), L.VMX_TEMPORAL_MOMENTS,
+                                                         C.byref(h)))
+        else:
+            self._check(self._lib.vmx_temporal_create(self.device, int(width), int(height), C.byref(h)))
         self._h = h
 
     def _check(self, code):
@@ -834,7 +865,8 @@ class Temporal:
     def __exit__(self, *a):
         self.close()
 
-    def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None, motion=None):
+    def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None, motion=None,
+                   variance=None, variance_params=None):
         """vmx_temporal_accumulate_device: one frame.  `cam` is that frame's camera (make_camera), `raw` its G-buffer —
         the ["raw"] tensor of Scene.raycast_camera(cam, opts, 0), float32 [height, width, 16] — and `rgbaz` the float32
         [height, width, 5] frame.  The accumulated frame goes to `out` (same shape; may be `rgbaz` itself) and / or
@@ -843,11 +875,21 @@ class Temporal:
         a ValueError, never a copy through the host.  params: make_temporal_params(...), default the library's.
         `motion` (vmx_temporal_accumulate_motion_device): what motion_vectors made of `raw` after a geometry update,
         float32 [height, width, 8], read only — moved surfaces then keep their history; None is the call without.
+        `variance` (vmx_temporal_accumulate_variance_device): float32 [height, width], receives the variance of each
+        pixel's luminance, for Filter.apply(..., variance=...); required on a handle made with moments=True and refused
+        on any other.  variance_params: make_variance_params(...), default the library's.
         Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
         import torch
         dev = torch.device("cuda", self.device)
+        moments = getattr(self, "moments", False)
+        if moments and variance is None:
+            raise ValueError("variance is required: the handle was made with moments=True")
+        if not moments and (variance is not None or variance_params is not None):
+            raise ValueError("variance needs a handle made with moments=True")
         _frame_tensor(raw, "raw", torch.float32, self.shape + (16,), dev)
         _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
+        if variance is not None:
+            _frame_tensor(variance, "variance", torch.float32, self.shape, dev)
         if motion is not None:
             _frame_tensor(motion, "motion", torch.float32, self.shape + (8,), dev)
         if out is None and rgba8 is None:
@@ -861,7 +903,12 @@ class Temporal:
         ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
         with _SideStream(dev, stream) as run:
             prm, s = None if params is None else C.byref(params), C.c_void_p(run.cuda_stream)
-            if motion is None:
+            if moments:
+                vprm = None if variance_params is None else C.byref(variance_params)
+                self._check(self._lib.vmx_temporal_accumulate_variance_device(self._h, C.byref(cam), ptr(raw), ptr(motion),
+                                                                              ptr(rgbaz), ptr(out), ptr(rgba8), ptr(history),
+                                                                              ptr(variance), prm, vprm, s))
+            elif motion is None:
                 self._check(self._lib.vmx_temporal_accumulate_device(self._h, C.byref(cam), ptr(raw), ptr(rgbaz), ptr(out),
                                                                      ptr(rgba8), ptr(history), prm, s))
             else:
