@@ -15,7 +15,7 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough [--moving] [--textured] [--variance] fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] [--textured] [--variance] [--upsample N/D] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
@@ -41,6 +41,13 @@
 // It composes with --moving (the motion records go to the variance call) and with --textured (the albedo plane goes to
 // the variance-guided call, which then works on colour / albedo as the demodulated call does).  The mean variance of each
 // frame is printed beside its history length.
+//
+// --upsample N/D (1 <= N <= D <= 4 N): every frame is rendered at N/D of the size with (D/N)^2 times the samples, rounded
+// down to a multiple of 4 — the same ray count — and accumulated and filtered at that low size; then
+//   vmx_raycast_camera_device            a second G-buffer, of the full-size camera: one ray per pixel
+//   vmx_upsample_set_guides_device + vmx_upsample_apply_device  the filtered low frame reconstructed at full size -> rgba8
+// It composes with --moving, --textured and --variance, which then all work at the low size; fly_out.ppm is full size,
+// fly_raw.ppm, fly_acc.ppm and fly_plain.ppm are the low size.
 #include <dlfcn.h>
 
 #include <cmath>
@@ -104,19 +111,33 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 
 int main(int argc, char **argv) {
     bool moving = false, textured = false, variance = false;
+    uint32_t up_n = 0, up_d = 0;  // --upsample N/D
     for (; argc > 1 && std::strncmp(argv[1], "--", 2) == 0; --argc, ++argv) {
         if (std::strcmp(argv[1], "--moving") == 0) moving = true;
         else if (std::strcmp(argv[1], "--textured") == 0) textured = true;
         else if (std::strcmp(argv[1], "--variance") == 0) variance = true;
+        else if (std::strcmp(argv[1], "--upsample") == 0 && argc > 2) {
+            if (std::sscanf(argv[2], "%u/%u", &up_n, &up_d) != 2 || up_n < 1 || up_n > up_d || up_d > 4 * up_n) {
+                std::fprintf(stderr, "flythrough: --upsample N/D needs 1 <= N <= D <= 4 N\n");
+                return 1;
+            }
+            --argc, ++argv;
+        }
         else {
             std::fprintf(stderr, "flythrough: unknown option %s\n", argv[1]);
             return 1;
         }
     }
     const std::string out = argc > 1 ? argv[1] : "fly";
-    const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
+    const uint32_t FW = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, FH = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t frames = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 8;
-    const uint32_t spp = argc > 5 ? (uint32_t)std::atoi(argv[5]) : 4;
+    const uint32_t full_spp = argc > 5 ? (uint32_t)std::atoi(argv[5]) : 4;
+    // W x H and spp are what is rendered, accumulated and filtered: the low size under --upsample, else the full size FW x FH
+    const bool upsample = up_n != 0;
+    const uint32_t W = upsample ? (FW * up_n + up_d - 1) / up_d : FW, H = upsample ? (FH * up_n + up_d - 1) / up_d : FH;
+    uint32_t spp = full_spp;
+    if (upsample && full_spp * up_d * up_d / (up_n * up_n) >= 4) spp = full_spp * up_d * up_d / (up_n * up_n) / 4 * 4;
+    if (upsample) std::printf("rendering %u x %u at %u spp for %u x %u at %u spp\n", W, H, spp, FW, FH, full_spp);
     const uint64_t seed = argc > 6 ? std::strtoull(argv[6], nullptr, 10) : 1;
 
     std::vector<float> pos, nrm, uv;
@@ -166,16 +187,24 @@ int main(int argc, char **argv) {
     void *d_pos[2] = {nullptr, nullptr}, *d_motion = nullptr, *d_acc_plain = nullptr, *d_hist_plain = nullptr;
     void *d_albedo = nullptr;  // --textured: the frame's albedo plane, float4 per pixel
     void *d_var = nullptr;     // --variance: the variance of each pixel's luminance, one float per pixel
+    // --upsample: the handle, the full-size G-buffer and the filtered low frame (RGBAZ: the upsampler's input)
+    vmx_upsample *upsampler = nullptr;
+    void *d_rec_full = nullptr, *d_filtered = nullptr;
+    const size_t full_pix = (size_t)FW * FH;
     std::vector<float> var(variance ? (size_t)W * H : 0);
     std::vector<float> moved = pos, hist_plain(moving ? (size_t)W * H : 0);
-    std::vector<unsigned char> rgba(npix * 4);
+    std::vector<unsigned char> rgba(full_pix * 4);
     std::vector<float> hist(npix);
     int rc = VMX_OK;
     bool io_ok = true;
     bool hip_ok = hip.stream_create(&stream) == 0 && hip.malloc_(&d_frame, npix * 20) == 0 && hip.malloc_(&d_rec, npix * 64) == 0 &&
-                  hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, npix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
+                  hip.malloc_(&d_acc, npix * 20) == 0 && hip.malloc_(&d_rgba8, full_pix * 4) == 0 && hip.malloc_(&d_hist, npix * 4) == 0;
     if (hip_ok) rc = vmx_temporal_create_ex(0, W, H, variance ? VMX_TEMPORAL_MOMENTS : 0u, &temporal);
     if (hip_ok && rc == VMX_OK) rc = vmx_filter_create(0, W, H, &filter);
+    if (upsample && hip_ok && rc == VMX_OK) {
+        hip_ok = hip.malloc_(&d_rec_full, full_pix * 64) == 0 && hip.malloc_(&d_filtered, npix * 20) == 0;
+        if (hip_ok) rc = vmx_upsample_create(0, W, H, FW, FH, &upsampler);
+    }
     if (textured && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_albedo, npix * 16) == 0;
     if (variance && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_var, npix * 4) == 0;
     if (moving && hip_ok && rc == VMX_OK) {
@@ -184,18 +213,20 @@ int main(int argc, char **argv) {
                  hip.malloc_(&d_hist_plain, npix * 4) == 0 && hip.memcpy_(d_pos[0], pos.data(), pos.size() * 4, 1) == 0;
         if (hip_ok) rc = vmx_temporal_create(0, W, H, &plain);
     }
-    // rgba8 of a device frame (vmx_quantize_device), or of d_rgba8 as it stands, on the host
-    auto fetch = [&](const void *d_rgbaz) {
-        if (d_rgbaz && (rc = vmx_quantize_device(d_rgbaz, npix, d_rgba8, nullptr, 0, stream)) != VMX_OK) return false;
-        return (hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(rgba.data(), d_rgba8, npix * 4, 2) == 0);
+    // rgba8 of a device frame of n pixels (vmx_quantize_device), or of d_rgba8 as it stands, on the host
+    auto fetch = [&](const void *d_rgbaz, size_t n) {
+        if (d_rgbaz && (rc = vmx_quantize_device(d_rgbaz, n, d_rgba8, nullptr, 0, stream)) != VMX_OK) return false;
+        return (hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(rgba.data(), d_rgba8, n * 4, 2) == 0);
     };
+    // where the filter's result goes: straight to rgba8, or, under --upsample, to the RGBAZ frame the upsampler reads
+    void *const f5 = upsample ? d_filtered : nullptr, *const f4 = upsample ? nullptr : d_rgba8;
     for (uint32_t i = 0; hip_ok && rc == VMX_OK && i < frames; ++i) {
         vmx_camera cam;
         std::memset(&cam, 0, sizeof(cam));
         cam.position[0] = 6.0f * (float)i, cam.position[1] = 420, cam.position[2] = 1900;  // a slow pan to the right ...
         cam.rotation_deg[1] = 0.15f * (float)i;                                             // ... while turning
         cam.back_distance = 6.0f;  // renderEngine.cpp:135
-        cam.back_size[0] = 3.6f, cam.back_size[1] = 3.6f * (float)H / (float)W;
+        cam.back_size[0] = 3.6f, cam.back_size[1] = 3.6f * (float)FH / (float)FW;
         cam.image_res[0] = W, cam.image_res[1] = H;
         cam.rays_per_pixel = spp;
         vmx_opts opts;
@@ -235,24 +266,32 @@ int main(int argc, char **argv) {
             if ((rc = vmx_albedo_camera_device(scene, &cam, &opts, 0, albedo_samples, d_albedo, stream)) != VMX_OK) break;
             if (i + 1 == frames) {  // the plain filter's picture of the same frame, for comparison
                 if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
-                if (fetch(nullptr) && !write_ppm(out + "_plain.ppm", rgba, W, H)) {
+                if (fetch(nullptr, npix) && !write_ppm(out + "_plain.ppm", rgba, W, H)) {
                     std::fprintf(stderr, "flythrough: cannot write %s_plain.ppm\n", out.c_str());
                     io_ok = false;
                 }
                 if (!hip_ok) break;
             }
             if (variance) {
-                if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, d_albedo, nullptr, d_rgba8, nullptr,
+                if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, d_albedo, f5, f4, nullptr,
                                                            VMX_SIGMA_LUMINANCE_DEFAULT, stream)) != VMX_OK)
                     break;
-            } else if ((rc = vmx_filter_apply_demodulated_device(filter, d_acc, d_albedo, nullptr, d_rgba8, nullptr, stream)) != VMX_OK)
+            } else if ((rc = vmx_filter_apply_demodulated_device(filter, d_acc, d_albedo, f5, f4, nullptr, stream)) != VMX_OK)
                 break;
         } else if (variance) {
-            if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, nullptr, nullptr, d_rgba8, nullptr,
+            if ((rc = vmx_filter_apply_variance_device(filter, d_acc, d_var, nullptr, f5, f4, nullptr,
                                                        VMX_SIGMA_LUMINANCE_DEFAULT, stream)) != VMX_OK)
                 break;
-        } else if ((rc = vmx_filter_apply_device(filter, d_acc, nullptr, d_rgba8, nullptr, stream)) != VMX_OK)
+        } else if ((rc = vmx_filter_apply_device(filter, d_acc, f5, f4, nullptr, stream)) != VMX_OK)
             break;
+        if (upsample) {
+            vmx_camera full = cam;  // the same field on FW x FH pixels; a G-buffer is one camera ray per pixel
+            full.image_res[0] = FW, full.image_res[1] = FH;
+            full.rays_per_pixel = full_spp;
+            if ((rc = vmx_raycast_camera_device(scene, &full, &opts, 0, d_rec_full, 0, stream)) != VMX_OK) break;
+            if ((rc = vmx_upsample_set_guides_device(upsampler, d_rec, d_rec_full, stream)) != VMX_OK) break;
+            if ((rc = vmx_upsample_apply_device(upsampler, d_filtered, nullptr, d_rgba8, nullptr, stream)) != VMX_OK) break;
+        }
         if (!(hip_ok = hip.stream_sync(stream) == 0 && hip.memcpy_(hist.data(), d_hist, npix * 4, 2) == 0)) break;
         double mean = 0;
         for (float n : hist) mean += n;
@@ -273,9 +312,10 @@ int main(int argc, char **argv) {
             std::printf("frame %u: camera x %.0f, y-rotation %.2f deg, %.2f ms device, mean history %.2f frames\n", i,
                         cam.position[0], cam.rotation_deg[1], st.ms_device, mean / (double)npix);
         if (i + 1 == frames) {
+            // (the filtered and, under --upsample, reconstructed frame is full size; the other two are the rendered size)
             const std::pair<const char *, const void *> files[3] = {{"_out.ppm", nullptr}, {"_acc.ppm", d_acc}, {"_raw.ppm", d_frame}};
             for (const auto &f : files)
-                if (fetch(f.second) && !write_ppm(out + f.first, rgba, W, H)) {
+                if (fetch(f.second, f.second ? npix : full_pix) && !write_ppm(out + f.first, rgba, f.second ? W : FW, f.second ? H : FH)) {
                     std::fprintf(stderr, "flythrough: cannot write %s%s\n", out.c_str(), f.first);
                     io_ok = false;
                 }
@@ -284,10 +324,11 @@ int main(int argc, char **argv) {
     if (rc != VMX_OK) std::fprintf(stderr, "flythrough: %s\n", vmx_last_error());
     if (!hip_ok) std::fprintf(stderr, "flythrough: a HIP runtime call failed\n");
     if (stream) hip.stream_sync(stream);
+    if (upsampler) vmx_upsample_destroy(upsampler);
     if (filter) vmx_filter_destroy(filter);
     if (temporal) vmx_temporal_destroy(temporal);
     if (plain) vmx_temporal_destroy(plain);
-    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo, d_var})
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo, d_var, d_rec_full, d_filtered})
         if (p) hip.free_(p);
     if (stream) hip.stream_destroy(stream);
     vmx_scene_destroy(scene);

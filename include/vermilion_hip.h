@@ -779,6 +779,66 @@ int vmx_filter_apply_variance_device(vmx_filter *f, const void *d_in_rgbaz, cons
                                      const void *d_albedo /* or NULL */, void *d_out_rgbaz, void *d_rgba8,
                                      const vmx_filter_params *params, float sigma_luminance, void *stream);
 
+/* ---- guided upsampling: render small, reconstruct at full size ----------------------------------------------
+ * A render costs rays = pixels x samples, a G-buffer one camera ray per pixel at any size.  So paths are traced at a
+ * reduced resolution (and denoised there) and the full-size frame is reconstructed under a full-size G-buffer: joint
+ * bilateral upsampling (Kopf et al. 2007) with the guide the filter already uses, a 2 x 2 tent footprint.
+ *
+ * Pixel x of a W-wide image is centred on sensor coordinate x / W (pathtracer.cpp:251-252, no half-pixel offset), and a
+ * low camera that differs from the full one only in image_res sees the same field: full pixel x lies at low coordinate
+ * x*lw/W.  Inputs: a low frame `lo` of lw x lh RGBAZ pixels; a low and a full guide, each (n, z) per pixel exactly as
+ * the filter packs them from vmx_rayhit records ((normal, distance) where flags bit 0 is set, ((0, 0, 0), -1) elsewhere;
+ * "a hit" is z >= 0).  1 <= lw <= W <= 4*lw and 1 <= lh <= H <= 4*lh; the ratios need not be integers.
+ *
+ * Per full pixel p = (x, y), all in float, one rounding per written operation, left to right, denormals kept:
+ *   rx = (float)lw / (float)W;  ry = (float)lh / (float)H                                                 (once per call)
+ *   u = (float)x * rx;  X0 = min((int)floorf(u), lw-1);  fx = u - (float)X0;       v, Y0, fy alike from y, ry, lh
+ *     (the min acts only where rounding lifts u to lw, beyond 2^21 pixels across: it keeps tap (0, 0) inside)
+ *   isz = 1.f / (sigma_depth * z_p)                                                       (used where p is a hit)
+ *   sum_c = (0, 0, 0);  sum_w = 0;  best_b = -1
+ *   taps j = 0..1 (outer), i = 0..1 (inner):  q = (X0 + i, Y0 + j); a tap with X0+i >= lw or Y0+j >= lh is outside
+ *   and skipped;
+ *     b = (j ? fy : 1.f - fy) * (i ? fx : 1.f - fx)
+ *     if b > best_b:  best_b = b, anchor = q         (strictly greater: ties keep the earlier tap; tap (0, 0) is inside)
+ *     a tap with (z_q >= 0) != (z_p >= 0) contributes nothing further
+ *     p a hit:  d = n_p.x*n_q.x + n_p.y*n_q.y + n_p.z*n_q.z;  d = d > 0 ? d : 0;  normal_squarings times d = d*d;
+ *               t = (z_p - z_q) * isz;  num = b * d;  g = 1.f + t*t               p a miss:  num = b;  g = 1.f
+ *     w = num / g;   if w > 0 and finite:  sum_c. = sum_c. + w * lo_q.;  sum_w = sum_w + w
+ *   out.rgb = sum_w > 0 ? sum_c. / sum_w : lo_anchor.rgb   (the fallback: no tap of p's kind, a zero or NaN normal, a
+ *   z_p so small that isz overflows);  out.alpha, out.depth = lo_anchor's, bitwise, always
+ *   rgba8 = vmx_quantize_device's arithmetic on that output pixel
+ * The kernel holds to this restatement bit for bit (tests/upsample_spec.py).
+ * Out of scope: upsampled progressive previews, multi-device frames, fusing the filter's last iteration into this call,
+ * and a temporal pass at full size after it. */
+typedef struct vmx_upsample_params {
+    uint32_t normal_squarings; /* 0..8;        default 5                          */
+    float sigma_depth;         /* finite, > 0; default 0.1f                       */
+    uint32_t reserved[6];      /* must be 0                                       */
+} vmx_upsample_params;
+
+typedef struct vmx_upsample vmx_upsample;
+
+int vmx_upsample_default_params(vmx_upsample_params *out);
+/* An upsampler from low_width x low_height frames to width x height frames on `device`.  It owns the two packed guides
+ * (16 B per pixel each); nothing is allocated after creation.  A zero size, a size outside the limits above, or a frame
+ * vmx_render would call too large, is VMX_ERR_INVALID; without a usable device VMX_ERR_NO_DEVICE. */
+int vmx_upsample_create(int device, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height,
+                        vmx_upsample **out);
+int vmx_upsample_destroy(vmx_upsample *u);
+/* d_rayhit_low, d_rayhit_full: low_width*low_height and width*height vmx_rayhit records in pixel order (what
+ * vmx_raycast_camera_device writes for the low and the full camera), 16-byte aligned DEVICE memory of the handle's
+ * device, packed into the handle's guides on `stream`.  The guides stay until the next call. */
+int vmx_upsample_set_guides_device(vmx_upsample *u, const void *d_rayhit_low, const void *d_rayhit_full, void *stream);
+/* Reconstructs the lw*lh*5-float frame d_low_rgbaz into d_out_rgbaz (W*H*5 floats) and / or d_rgba8 (W*H*4 bytes); at
+ * least one of the two must be non-NULL.  params == NULL selects the defaults; a field out of range or a non-zero
+ * reserved word is VMX_ERR_INVALID before any launch, as is a call before any guides were set.  The sizes differ, so
+ * there is no in-place form: any overlap of the input with an output, or of the two outputs, is VMX_ERR_INVALID.
+ * Pointers are checked as vmx_query_device checks its own (DEVICE memory of the handle's device) and must be 4-byte
+ * aligned.  Enqueued on `stream`, no synchronisation.  Calls on one handle from different streams are ordered by
+ * enqueue (each waits on an event the previous one recorded), as vmx_filter_apply_device's are. */
+int vmx_upsample_apply_device(vmx_upsample *u, const void *d_low_rgbaz, void *d_out_rgbaz, void *d_rgba8,
+                              const vmx_upsample_params *params, void *stream);
+
 /*
  * Multi-GPU assembly on the root: `d_gathered` = world packed per-rank buffers
  * back to back, each padded to `rank_stride_floats`; writes the W*H*5 frame.

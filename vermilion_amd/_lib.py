@@ -228,6 +228,17 @@ class VarianceParams(C.Structure):
                 "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
 
 
+class UpsampleParams(C.Structure):
+    _fields_ = [
+        ("normal_squarings", C.c_uint32),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+    def as_dict(self):
+        return {"normal_squarings": self.normal_squarings, "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
+
+
 # every symbol include/vermilion_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -294,6 +305,11 @@ SYMBOLS = {
     "vmx_temporal_accumulate_variance_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P,
                                                           C.POINTER(TemporalParams), C.POINTER(VarianceParams), _P]),
     "vmx_filter_apply_variance_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(FilterParams), C.c_float, _P]),
+    "vmx_upsample_default_params": (C.c_int, [C.POINTER(UpsampleParams)]),
+    "vmx_upsample_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "vmx_upsample_destroy": (C.c_int, [_P]),
+    "vmx_upsample_set_guides_device": (C.c_int, [_P, _P, _P, _P]),
+    "vmx_upsample_apply_device": (C.c_int, [_P, _P, _P, _P, C.POINTER(UpsampleParams), _P]),
     "vmx_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(Stats)]),
     "vmx_render_bruteforce_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, _P,
                                               C.POINTER(Stats)]),

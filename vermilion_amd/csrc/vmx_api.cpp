@@ -43,6 +43,7 @@ using namespace vmx;
 #include "api_scene.inc"       // vmx_scene_create / destroy / bind_texture / describe / timings / bvh
 #include "api_query.inc"       // vmx_trace, vmx_raycast*, vmx_query*, vmx_primary_ids, vmx_radiance, vmx_trig
 #include "api_filter.inc"      // vmx_filter_*
+#include "api_upsample.inc"    // vmx_upsample_*
 #include "api_albedo.inc"      // vmx_albedo_camera_device
 #include "api_temporal.inc"    // vmx_temporal_*
 #include "api_motion.inc"      // vmx_motion_device

@@ -276,6 +276,17 @@ int launch_demod_divide(const FilterPass &pass, void *stream);
 // one iteration from pass.in_plane
 int launch_variance_pack(const FilterPass &pass, const float *variance, void *stream);
 int launch_atrous_var(const FilterPass &pass, void *stream);
+// G-buffer-guided upsampling (vmx_upsample.inc; the arithmetic is stated in include/vermilion_hip.h): one call
+struct UpsamplePass {
+    uint32_t width, height, low_width, low_height;
+    uint32_t squarings;  // normal_squarings
+    float sigma_depth;
+    const void *guide_low, *guide_full;  // float4 (n.xyz, z) per pixel, as launch_filter_guide packs them
+    const float *low;                    // the low RGBAZ frame
+    float *out_rgbaz;                    // outputs, either may be NULL
+    void *rgba8;
+};
+int launch_upsample(const UpsamplePass &pass, void *stream);
 // the albedo plane of a camera (vmx_albedo.inc; the arithmetic is stated in include/vermilion_hip.h): sample q.sample
 // of a run of n — k_query<kQueryCastCamera> (per-lane fetch) with cfg into `rec` (64 bytes per pixel, q.n = W * H), then k_albedo_finish
 // into `plane` (float4 per pixel); first / last: of the run

@@ -3976,6 +3976,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 
 // G-buffer-guided a-trous filter of frames and previews
 #include "vmx_filter.inc"
+// G-buffer-guided upsampling: a low frame reconstructed under a full-size guide
+#include "vmx_upsample.inc"
 
 // temporal accumulation: reprojected history blended with each new frame
 #include "vmx_temporal.inc"

@@ -143,6 +143,26 @@ def make_variance_params(min_history=None, normal_squarings=None, sigma_depth=No
     return p
 
 
+def make_upsample_params(normal_squarings=None, sigma_depth=None):
+    """vmx_upsample_params: the library's defaults (vmx_upsample_default_params) with the given fields replaced"""
+    p = L.UpsampleParams()
+    L.check(L.lib().vmx_upsample_default_params(C.byref(p)))
+    if normal_squarings is not None:
+        p.normal_squarings = int(normal_squarings)
+    if sigma_depth is not None:
+        p.sigma_depth = float(sigma_depth)
+    return p
+
+
+def low_camera(cam, low_width, low_height):
+    """a copy of the CameraDesc `cam` with image_res replaced: the same field of view on fewer pixels, what a frame for
+    Upsample is rendered and ray-cast with"""
+    c = L.CameraDesc()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(L.CameraDesc))
+    c.image_res[:] = [int(low_width), int(low_height)]
+    return c
+
+
 def _frame_tensor(x, name, dtype, shape, dev):
     """an output or input of the device filter / previews as the ABI takes it, or a ValueError"""
     if not _is_tensor(x):
@@ -822,6 +842,80 @@ class Filter:
                 self._check(self._lib.vmx_filter_apply_demodulated_device(self._h, ptr(rgbaz), ptr(albedo), ptr(out),
                                                                           ptr(rgba8), prm, s))
         return out, rgba8
+
+
+class Upsample:
+    """One vmx_upsample handle: G-buffer-guided upsampling (include/vermilion_hip.h) of [low_height, low_width] frames to
+    [height, width] frames on `device`.  `set_guides` takes the camera raycasts' records of both sizes, `apply`
+    reconstructs RGBAZ frames with them."""
+
+    def __init__(self, low_width, low_height, width, height, device=0, lib=None):
+        self._lib = lib if lib is not None else L.lib()
+        self._h = None
+        self.device = int(device)
+        self.low_shape = (int(low_height), int(low_width))
+        self.shape = (int(height), int(width))
+        h = C.c_void_p()
+        self._check(self._lib.vmx_upsample_create(self.device, int(low_width), int(low_height), int(width), int(height),
+                                                  C.byref(h)))
+        self._h = h
+
+    def _check(self, code):
+        if code != L.VMX_OK:
+            raise L.VmxError(code, self._lib.vmx_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._check(self._lib.vmx_upsample_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_guides(self, raw_low, raw_full, stream=None):
+        """vmx_upsample_set_guides_device: the ["raw"] tensors of Scene.raycast_camera for low_camera(cam, ...) and for
+        cam, or any contiguous float32 [low_height, low_width, 16] and [height, width, 16] tensors of vmx_rayhit records
+        on the handle's device — anything else is a ValueError.  Enqueued on `stream` (default
+        torch.cuda.current_stream()), nothing synchronised."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        _frame_tensor(raw_low, "raw_low", torch.float32, self.low_shape + (16,), dev)
+        _frame_tensor(raw_full, "raw_full", torch.float32, self.shape + (16,), dev)
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_upsample_set_guides_device(self._h, C.c_void_p(raw_low.data_ptr()),
+                                                                 C.c_void_p(raw_full.data_ptr()),
+                                                                 C.c_void_p(run.cuda_stream)))
+
+    def apply(self, frame_low, out=None, rgba8=None, params=None, stream=None):
+        """vmx_upsample_apply_device: reconstructs the float32 [low_height, low_width, 5] frame `frame_low` into `out`
+        (float32 [height, width, 5]) and / or `rgba8` (uint8 [height, width, 4]); with neither given, a new `out` is
+        made.  All are contiguous torch tensors on the handle's device: anything else is a ValueError, never a copy
+        through the host.  params: make_upsample_params(...), default the library's.  Enqueued on `stream` (default
+        torch.cuda.current_stream()), nothing synchronised; returns `out` (None where only `rgba8` was asked for)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        _frame_tensor(frame_low, "frame_low", torch.float32, self.low_shape + (5,), dev)
+        if out is None and rgba8 is None:
+            out = torch.empty(self.shape + (5,), dtype=torch.float32, device=dev)
+        if out is not None:
+            _frame_tensor(out, "out", torch.float32, self.shape + (5,), dev)
+        if rgba8 is not None:
+            _frame_tensor(rgba8, "rgba8", torch.uint8, self.shape + (4,), dev)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        with _SideStream(dev, stream) as run:
+            self._check(self._lib.vmx_upsample_apply_device(self._h, ptr(frame_low), ptr(out), ptr(rgba8),
+                                                            None if params is None else C.byref(params),
+                                                            C.c_void_p(run.cuda_stream)))
+        return out
 
 
 class Temporal:
