@@ -10,9 +10,10 @@ from ._lib import (VMX_SAMPLING_CORRECTED, VMX_SAMPLING_ELIDE_DEAD, VMX_SAMPLING
 from ._lib import VMX_ALBEDO_FLOOR as ALBEDO_FLOOR
 from ._lib import VMX_SIGMA_LUMINANCE_DEFAULT as SIGMA_LUMINANCE_DEFAULT
 from ._lib import VMX_VARIANCE_EPS as VARIANCE_EPS
-from .scene import (MOTION_DTYPE, Filter, MultiScene, Progressive, Scene, Temporal, Upsample, default_spheres,
+from .scene import (MOTION_DTYPE, MultiScene, Progressive, Scene, default_spheres,
                     local_row_indices, local_rows, low_camera, make_camera, make_filter_params, make_opts,
                     make_temporal_params, make_upsample_params, make_variance_params, motion_vectors, spheres_array)
+from .image import Filter, Temporal, Upsample
 from .api import (Camera, Integrator, MeshEngine, PathTracer, RenderEngine, cameraSettings, float3,
                   pixelValue, vermRenderMode)
 from . import scenes

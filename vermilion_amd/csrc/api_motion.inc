@@ -14,21 +14,12 @@ int vmx_motion_device(const void *d_rayhit, uint32_t n, const void *d_pos_now, c
     if (((uintptr_t)d_pos_now | (uintptr_t)d_pos_prev | (uintptr_t)d_nrm_prev) & 3u)
         return fail(VMX_ERR_INVALID, "d_pos_now, d_pos_prev and d_nrm_prev must be 4-byte aligned");
     if (n > 0x7fffffffu) return fail(VMX_ERR_INVALID, "n must be at most 2^31 - 1");
-    {
-        // the one buffer the call writes may overlap none it reads
-        const uintptr_t lo[4] = {(uintptr_t)d_rayhit, (uintptr_t)d_pos_now, (uintptr_t)d_pos_prev, (uintptr_t)d_nrm_prev};
-        const uintptr_t len[4] = {(uintptr_t)n * 64, (uintptr_t)ntris * 36, (uintptr_t)ntris * 36, (uintptr_t)ntris * 36};
-        const uintptr_t out = (uintptr_t)d_out, out_len = (uintptr_t)n * 32;
-        for (int i = 0; i < 4; ++i)
-            if (lo[i] && lo[i] < out + out_len && out < lo[i] + len[i])
-                return fail(VMX_ERR_INVALID, "d_out overlaps d_rayhit, d_pos_now, d_pos_prev or d_nrm_prev");
-    }
+    // d_out, the one buffer the call writes, against each it reads
+    if (meets_any(Span{d_out, (size_t)n * 32}, {{d_rayhit, (size_t)n * 64}, {d_pos_now, (size_t)ntris * 36}, {d_pos_prev, (size_t)ntris * 36},
+                                                {d_nrm_prev, (size_t)ntris * 36}}))
+        return fail(VMX_ERR_INVALID, "d_out overlaps d_rayhit, d_pos_now, d_pos_prev or d_nrm_prev");
     if (n == 0) return VMX_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = device_checks(device)) return rc;
     if (int rc = check_device_ptrs(device, {{d_rayhit, "d_rayhit"}, {d_pos_now, "d_pos_now"}, {d_pos_prev, "d_pos_prev"},
                                             {d_nrm_prev, "d_nrm_prev"}, {d_out, "d_out"}}))
         return rc;

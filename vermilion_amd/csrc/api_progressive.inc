@@ -175,7 +175,7 @@ static int progressive_filter_enqueue(vmx_progressive *p, float *d_rgbaz, void *
     src.finished = p->frame.p;
     src.kmax = p->job.fr.kmax;
     std::lock_guard<std::mutex> lock(p->filter->mu);
-    return filter_enqueue(p->filter.get(), src, d_rgbaz, d_rgba8, prm, p->job.s, albedo_samples ? p->albedo.p : nullptr);
+    return filter_enqueue(p->filter.get(), src, d_rgbaz, d_rgba8, prm, p->job.s, FilterExtras{albedo_samples ? p->albedo.p : nullptr});
 }
 
 // demod: vmx_progressive_preview_demodulated_device, whose albedo_samples must be 1 .. kmax
@@ -190,10 +190,8 @@ static int progressive_preview_filtered_device(vmx_progressive *p, void *d_rgbaz
     std::lock_guard<std::mutex> lock(sc->mu);
     if (int rc = bind_device(sc)) return rc;
     if (int rc = check_device_ptrs(sc->device, {{d_rgbaz, "d_rgbaz"}, {d_rgba8, "d_rgba8"}})) return rc;
-    if (d_rgbaz && d_rgba8) {
-        const uintptr_t a = (uintptr_t)d_rgbaz, b = (uintptr_t)d_rgba8, n = p->job.npix;
-        if (a < b + n * 4 && b < a + n * 20) return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 overlap");
-    }
+    if (spans_meet(Span{d_rgbaz, (size_t)p->job.npix * 20}, Span{d_rgba8, (size_t)p->job.npix * 4}))
+        return fail(VMX_ERR_INVALID, "d_rgbaz and d_rgba8 overlap");
     return progressive_filter_enqueue(p, (float *)d_rgbaz, d_rgba8, prm, demod ? albedo_samples : 0);
 }
 

@@ -22,40 +22,14 @@ static int temporal_params(const vmx_temporal_params *in, vmx_temporal_params &o
     out = in ? *in : kTemporalDefaults;
     if (!(std::isfinite(out.normal_min) && out.normal_min >= -1.f && out.normal_min <= 1.f))
         return fail(VMX_ERR_INVALID, "vmx_temporal_params: normal_min must be finite and -1..1");
-    if (!(std::isfinite(out.plane_tol) && out.plane_tol > 0.f))
-        return fail(VMX_ERR_INVALID, "vmx_temporal_params: plane_tol must be finite and > 0");
+    if (!finite_positive(out.plane_tol)) return fail(VMX_ERR_INVALID, "vmx_temporal_params: plane_tol must be finite and > 0");
     if (!(std::isfinite(out.max_history) && out.max_history >= 1.f))
         return fail(VMX_ERR_INVALID, "vmx_temporal_params: max_history must be finite and >= 1");
-    for (uint32_t r : out.reserved)
-        if (r) return fail(VMX_ERR_INVALID, "vmx_temporal_params: reserved words must be 0");
+    if (!reserved_zero(out.reserved)) return fail(VMX_ERR_INVALID, "vmx_temporal_params: reserved words must be 0");
     return VMX_OK;
 }
 
-static const vmx_variance_params kVarianceDefaults = {4.f, 5u, 0.1f, {0u, 0u, 0u, 0u, 0u}};
-
-static int variance_params(const vmx_variance_params *in, vmx_variance_params &out) {
-    out = in ? *in : kVarianceDefaults;
-    if (!(std::isfinite(out.min_history) && out.min_history >= 1.f))
-        return fail(VMX_ERR_INVALID, "vmx_variance_params: min_history must be finite and >= 1");
-    if (out.normal_squarings > 8) return fail(VMX_ERR_INVALID, "vmx_variance_params: normal_squarings must be 0..8");
-    if (!(std::isfinite(out.sigma_depth) && out.sigma_depth > 0.f))
-        return fail(VMX_ERR_INVALID, "vmx_variance_params: sigma_depth must be finite and > 0");
-    for (uint32_t r : out.reserved)
-        if (r) return fail(VMX_ERR_INVALID, "vmx_variance_params: reserved words must be 0");
-    return VMX_OK;
-}
-
-int vmx_variance_default_params(vmx_variance_params *out) {
-    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
-    *out = kVarianceDefaults;
-    return VMX_OK;
-}
-
-int vmx_temporal_default_params(vmx_temporal_params *out) {
-    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
-    *out = kTemporalDefaults;
-    return VMX_OK;
-}
+int vmx_temporal_default_params(vmx_temporal_params *out) { return default_params(out, kTemporalDefaults); }
 
 int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_temporal **out) {
     return vmx_temporal_create_ex(device, width, height, 0u, out);
@@ -65,13 +39,7 @@ int vmx_temporal_create_ex(int device, uint32_t width, uint32_t height, uint32_t
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
     *out = nullptr;
     if (flags & ~VMX_TEMPORAL_MOMENTS) return fail(VMX_ERR_INVALID, "vmx_temporal_create_ex: unknown flags");
-    if (width == 0 || height == 0) return fail(VMX_ERR_INVALID, "image resolution must be non-zero");
-    if ((uint64_t)width * height > 0x7fffffffull / 8) return fail(VMX_ERR_INVALID, "image too large");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = image_handle_checks(device, width, height)) return rc;
     std::unique_ptr<vmx_temporal> t(new (std::nothrow) vmx_temporal);
     if (!t) return fail(VMX_ERR_NOMEM, "out of host memory");
     t->device = device, t->width = width, t->height = height;
@@ -115,17 +83,24 @@ int vmx_temporal_accumulate_device(vmx_temporal *t, const vmx_camera *cam, const
                                                  params, stream);
 }
 
-// the three accumulate entries; variance: vmx_temporal_accumulate_variance_device, whose d_variance is an output
+// what vmx_temporal_accumulate_variance_device takes besides the others' arguments
+struct TemporalVariance {
+    void *d_variance;  // an output
+    const vmx_variance_params *params;
+};
+
+// the three accumulate entries; var: the variance entry's own arguments, NULL for the other two
 static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
-                               const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len, bool variance,
-                               void *d_variance, const vmx_temporal_params *params, const vmx_variance_params *vparams,
-                               void *stream) {
+                               const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                               const vmx_temporal_params *params, void *stream, const TemporalVariance *var) {
+    const bool variance = var != nullptr;
+    void *d_variance = var ? var->d_variance : nullptr;
     // checks that need no device, in the filter's order so that each can be seen alone; the handle comes last
     vmx_temporal_params prm;
     if (int rc = temporal_params(params, prm)) return rc;
     vmx_variance_params vprm = kVarianceDefaults;
     if (variance)
-        if (int rc = variance_params(vparams, vprm)) return rc;
+        if (int rc = variance_params(var->params, vprm)) return rc;
     if (!cam) return fail(VMX_ERR_INVALID, "NULL camera");
     if (!d_rayhit) return fail(VMX_ERR_INVALID, "NULL d_rayhit");
     if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
@@ -151,26 +126,19 @@ static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const voi
         return fail(VMX_ERR_INVALID, "cam->image_res is " + std::to_string(fr.width) + " x " + std::to_string(fr.height) +
                                          ", the handle's frames are " + std::to_string(t->width) + " x " + std::to_string(t->height));
     {
-        // in place (d_out_rgbaz == d_in_rgbaz) is the one overlap a buffer the call writes may have
-        const uintptr_t npix = (uintptr_t)t->width * t->height;
-        const uintptr_t lo[5] = {(uintptr_t)d_rayhit, (uintptr_t)d_in_rgbaz, (uintptr_t)d_out_rgbaz, (uintptr_t)d_rgba8,
-                                 (uintptr_t)d_history_len};
-        const uintptr_t len[5] = {npix * 64, npix * 20, npix * 20, npix * 4, npix * 4};
-        for (int j = 2; j < 5 && d_motion; ++j)  // (the motion records are read only, like d_rayhit)
-            if (lo[j] && (uintptr_t)d_motion < lo[j] + len[j] && lo[j] < (uintptr_t)d_motion + npix * 32)
-                return fail(VMX_ERR_INVALID, "d_motion overlaps d_out_rgbaz, d_rgba8 or d_history_len");
-        for (int i = 0; i < 5; ++i)
-            for (int j = std::max(i + 1, 2); j < 5; ++j) {  // (j: the written ones)
-                if (!lo[i] || !lo[j] || (i == 1 && j == 2 && lo[1] == lo[2])) continue;
-                if (lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i])
-                    return fail(VMX_ERR_INVALID, "d_rayhit, d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len overlap (only d_out_rgbaz == d_in_rgbaz may)");
-            }
-        if (variance) {  // (it may meet no other buffer of the call)
-            const uintptr_t v = (uintptr_t)d_variance;
-            bool meets = d_motion && v < (uintptr_t)d_motion + npix * 32 && (uintptr_t)d_motion < v + npix * 4;
-            for (int i = 0; i < 5; ++i) meets = meets || (lo[i] && v < lo[i] + len[i] && lo[i] < v + npix * 4);
-            if (meets) return fail(VMX_ERR_INVALID, "d_variance overlaps another buffer of the call");
-        }
+        const size_t npix = (size_t)t->width * t->height;
+        const Span rayhit{d_rayhit, npix * 64}, motion{d_motion, npix * 32}, in{d_in_rgbaz, npix * 20}, out{d_out_rgbaz, npix * 20},
+            q8{d_rgba8, npix * 4}, hist{d_history_len, npix * 4};
+        // d_motion against each buffer the call writes (the motion records are read only, like d_rayhit)
+        if (meets_any(motion, {out, q8, hist})) return fail(VMX_ERR_INVALID, "d_motion overlaps d_out_rgbaz, d_rgba8 or d_history_len");
+        // every pair of {rayhit, in, out, rgba8, history_len} with a written one in it, except in == out: in place is
+        // the one overlap a buffer the call writes may have
+        if (meets_any(rayhit, {out, q8, hist}) || (d_in_rgbaz != d_out_rgbaz && spans_meet(in, out)) || meets_any(in, {q8, hist}) ||
+            meets_any(out, {q8, hist}) || spans_meet(q8, hist))
+            return fail(VMX_ERR_INVALID, "d_rayhit, d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len overlap (only d_out_rgbaz == d_in_rgbaz may)");
+        // d_variance against every other buffer of the call
+        if (meets_any(Span{d_variance, npix * 4}, {motion, rayhit, in, out, q8, hist}))
+            return fail(VMX_ERR_INVALID, "d_variance overlaps another buffer of the call");
     }
     HIP_TRY(hipSetDevice(t->device));
     if (int rc = check_device_ptrs(t->device, {{d_rayhit, "d_rayhit"}, {d_in_rgbaz, "d_in_rgbaz"}, {d_out_rgbaz, "d_out_rgbaz"},
@@ -213,16 +181,15 @@ static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const voi
 int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
                                           const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
                                           const vmx_temporal_params *params, void *stream) {
-    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, false, nullptr,
-                               params, nullptr, stream);
+    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, params, stream, nullptr);
 }
 
 int vmx_temporal_accumulate_variance_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
                                             const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
                                             void *d_variance, const vmx_temporal_params *params,
                                             const vmx_variance_params *vparams, void *stream) {
-    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, true, d_variance,
-                               params, vparams, stream);
+    const TemporalVariance var{d_variance, vparams};
+    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, params, stream, &var);
 }
 
 } /* extern "C" */

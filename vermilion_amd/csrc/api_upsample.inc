@@ -16,19 +16,13 @@ static const vmx_upsample_params kUpsampleDefaults = {5u, 0.1f, {0u, 0u, 0u, 0u,
 // NULL selects the defaults; anything out of range is refused before any launch
 static int upsample_params(const vmx_upsample_params *in, vmx_upsample_params &out) {
     out = in ? *in : kUpsampleDefaults;
-    if (out.normal_squarings > 8) return fail(VMX_ERR_INVALID, "vmx_upsample_params: normal_squarings must be 0..8");
-    if (!(std::isfinite(out.sigma_depth) && out.sigma_depth > 0.f))
-        return fail(VMX_ERR_INVALID, "vmx_upsample_params: sigma_depth must be finite and > 0");
-    for (uint32_t r : out.reserved)
-        if (r) return fail(VMX_ERR_INVALID, "vmx_upsample_params: reserved words must be 0");
+    if (!squarings_ok(out.normal_squarings)) return fail(VMX_ERR_INVALID, "vmx_upsample_params: normal_squarings must be 0..8");
+    if (!finite_positive(out.sigma_depth)) return fail(VMX_ERR_INVALID, "vmx_upsample_params: sigma_depth must be finite and > 0");
+    if (!reserved_zero(out.reserved)) return fail(VMX_ERR_INVALID, "vmx_upsample_params: reserved words must be 0");
     return VMX_OK;
 }
 
-int vmx_upsample_default_params(vmx_upsample_params *out) {
-    if (!out) return fail(VMX_ERR_INVALID, "NULL out");
-    *out = kUpsampleDefaults;
-    return VMX_OK;
-}
+int vmx_upsample_default_params(vmx_upsample_params *out) { return default_params(out, kUpsampleDefaults); }
 
 int vmx_upsample_create(int device, uint32_t low_width, uint32_t low_height, uint32_t width, uint32_t height, vmx_upsample **out) {
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
@@ -39,12 +33,7 @@ int vmx_upsample_create(int device, uint32_t low_width, uint32_t low_height, uin
         return fail(VMX_ERR_INVALID, "the low frame must not be larger than the full one (low_width <= width, low_height <= height)");
     if ((uint64_t)width > 4ull * low_width || (uint64_t)height > 4ull * low_height)
         return fail(VMX_ERR_INVALID, "the full frame must be at most 4 times the low one (width <= 4 * low_width, height <= 4 * low_height)");
-    if ((uint64_t)width * height > 0x7fffffffull / 8) return fail(VMX_ERR_INVALID, "image too large");  // (the low one is no larger)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(VMX_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = image_handle_checks(device, width, height)) return rc;  // (the low image is no larger)
     std::unique_ptr<vmx_upsample> u(new (std::nothrow) vmx_upsample);
     if (!u) return fail(VMX_ERR_NOMEM, "out of host memory");
     u->device = device, u->low_width = low_width, u->low_height = low_height, u->width = width, u->height = height;
@@ -91,14 +80,10 @@ int vmx_upsample_apply_device(vmx_upsample *u, const void *d_low_rgbaz, void *d_
     if (!u) return fail(VMX_ERR_INVALID, "NULL handle");
     std::lock_guard<std::mutex> lock(u->mu);
     {
-        // the sizes differ, so there is no in-place form: no two of the three buffers may meet
-        const uintptr_t nlow = (uintptr_t)u->low_width * u->low_height, npix = (uintptr_t)u->width * u->height;
-        const uintptr_t lo[3] = {(uintptr_t)d_low_rgbaz, (uintptr_t)d_out_rgbaz, (uintptr_t)d_rgba8};
-        const uintptr_t len[3] = {nlow * 20, npix * 20, npix * 4};
-        for (int i = 0; i < 3; ++i)
-            for (int j = i + 1; j < 3; ++j)
-                if (lo[i] && lo[j] && lo[i] < lo[j] + len[j] && lo[j] < lo[i] + len[i])
-                    return fail(VMX_ERR_INVALID, "d_low_rgbaz, d_out_rgbaz and d_rgba8 overlap");
+        // every pair of {low, out, rgba8}: the sizes differ, so there is no in-place form
+        const size_t nlow = (size_t)u->low_width * u->low_height, npix = (size_t)u->width * u->height;
+        const Span low{d_low_rgbaz, nlow * 20}, out{d_out_rgbaz, npix * 20}, q8{d_rgba8, npix * 4};
+        if (meets_any(low, {out, q8}) || spans_meet(out, q8)) return fail(VMX_ERR_INVALID, "d_low_rgbaz, d_out_rgbaz and d_rgba8 overlap");
     }
     if (!u->guides_set) return fail(VMX_ERR_INVALID, "no guides: call vmx_upsample_set_guides_device first");
     HIP_TRY(hipSetDevice(u->device));

@@ -42,6 +42,7 @@ using namespace vmx;
 #include "api_render.inc"      // the pass loop, BruteForceTracer; vmx_render*, vmx_local_rows
 #include "api_scene.inc"       // vmx_scene_create / destroy / bind_texture / describe / timings / bvh
 #include "api_query.inc"       // vmx_trace, vmx_raycast*, vmx_query*, vmx_primary_ids, vmx_radiance, vmx_trig
+#include "api_image.inc"       // shared by the image-space entries below: handle, overlap and params checks; vmx_variance_default_params
 #include "api_filter.inc"      // vmx_filter_*
 #include "api_upsample.inc"    // vmx_upsample_*
 #include "api_albedo.inc"      // vmx_albedo_camera_device

@@ -1,20 +1,19 @@
 // vmx_filter.inc — G-buffer-guided edge-avoiding a-trous filter of frames and progressive previews (vmx_filter_*,
-// vmx_progressive_preview_filtered*).  Included by vmx_kernels.hip (inside its namespace).  The arithmetic is stated
+// vmx_progressive_preview_filtered*).  Included by vmx_kernels.hip (inside its namespace, after vmx_image.inc: the tile,
+// the tap terms and the launch are there).  The arithmetic is stated
 // in include/vermilion_hip.h and restated in tests/filter_spec.py; with -ffp-contract=off every operation below rounds
 // once, in the order written, and `/` is the correctly rounded division with denormals kept: bit for bit the restatement.
 //
 //   k_filter_guide  one lane per pixel: the 64-byte vmx_rayhit becomes the 16-byte guide record (n.xyz, z); z = -1 and
 //                   n = 0 where the ray missed ("a hit" is z >= 0 from here on).
-//   k_atrous        one iteration, one lane per pixel, blocks of 32 x 8 pixels: a wave is two image rows of 32 pixels, so
-//                   each of its tap loads is two runs of 32 consecutive 16-byte records at every step size.  The 25 taps
+//   k_atrous        one iteration, one lane per pixel of an image_tile: each of a wave's tap loads is two runs of 32
+//                   consecutive 16-byte records at every step size.  The 25 taps
 //                   are unrolled; the centre's guide and colour stay in registers; hit / miss and every skip rule are
 //                   selects, not branches (a tap outside the image loads the centre's records and is selected away).
 //                   IN: where the colours come from — 0 a float4 plane (every iteration but the first), 1 the RGBAZ
 //                   frame, 2 the per-pixel state of a progressive render, shown as k_preview shows it.
-//                   LAST: the iteration that writes the caller's buffers.  Alpha and depth are read again from the first
-//                   input (own pixel only) and the block's 256 pixels — eight runs of 160 floats — leave through LDS as
-//                   dword stores of consecutive lanes to consecutive addresses, as in k_preview; rgba8 from the same
-//                   values.  Else the result goes to the other float4 plane.
+//                   LAST: the iteration that writes the caller's buffers (atrous_write_last).  Else the result goes to
+//                   the other float4 plane.
 //                   M: normal_squarings as a constant (the default, 5) or -1: read from the pass.
 //                   DEMOD (vmx_filter_apply_demodulated_device; LAST only): the result is multiplied by the pixel's own
 //                   albedo before it leaves, each channel clamped from below (filter_albedo).
@@ -24,8 +23,6 @@
 //                   against 477 for a five-iteration call on a frame, 119 against 299 for a single iteration, 441 against
 //                   1080 for a filtered preview — the per-tap forms of the first iteration need 300+ VGPRs.  The
 //                   existing instantiations are the instruction streams they were without the parameter.
-constexpr uint32_t kFilterBX = 32, kFilterBY = 8, kFilterBlock = kFilterBX * kFilterBY;
-
 __global__ void __launch_bounds__(256) k_filter_guide(const float4 *__restrict__ rayhit, uint32_t npix,
                                                       float4 *__restrict__ guide) {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
@@ -86,20 +83,35 @@ __global__ void __launch_bounds__(256) k_demod_divide(FilterPass a, uint32_t npi
     ((float4 *)a.out_plane)[p] = make_float4(v[0] / am[0], v[1] / am[1], v[2] / am[2], 0.f);
 }
 
+// the last iteration's way out, for k_atrous and k_atrous_var: o.rgb with the alpha and depth of the first input (own
+// pixel only) into the lane's five words of s_px, rgba8 from the same values, then the block's runs to out_rgbaz.
+// STATE: the first input may be the per-pixel state of a progressive render (a.src.frame NULL)
+template <bool STATE>
+__device__ __forceinline__ void atrous_write_last(const FilterPass &a, const ImageTile &t, const float *o, float *s_px) {
+    if (t.live) {
+        float *v = s_px + threadIdx.x * 5;
+        float src[5];
+        if (!STATE || a.src.frame)
+            filter_src_pixel<false>(a.src, t.p, src);
+        else
+            filter_src_pixel<true>(a.src, t.p, src);
+        v[0] = o[0], v[1] = o[1], v[2] = o[2], v[3] = src[3], v[4] = src[4];  // alpha, depth: the input's bits
+        if (a.rgba8) ((uchar4 *)a.rgba8)[t.p] = quantized_pixel(v);
+    }
+    if (!a.out_rgbaz) return;
+    __syncthreads();
+    tile_store_rgbaz(s_px, a.out_rgbaz, a.width, a.height, t.bx0, t.by0);
+}
+
 template <int IN, bool LAST, int M, bool DEMOD = false>
 __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
     static_assert(!DEMOD || (LAST && IN == 0), "demodulation: the pre-pass divides, the last iteration (from a plane) multiplies");
     __shared__ float s_px[LAST ? kFilterBlock * 5 : 1];
     const uint32_t W = a.width, H = a.height;
-    // (a one-dimensional grid of blocks, row-major over the image: the second grid dimension ends at 65535)
-    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t x = bx * kFilterBX + (threadIdx.x & (kFilterBX - 1));
-    const uint32_t y = by * kFilterBY + threadIdx.x / kFilterBX;
-    const bool live = x < W && y < H;
-    const uint32_t p = y * W + x;  // (W * H <= 2^28: make_frame's size check)
+    const ImageTile tile = image_tile(W, H);
+    const uint32_t x = tile.x, y = tile.y, p = tile.p;
     float o[3] = {0.f, 0.f, 0.f};
-    if (live) {
+    if (tile.live) {
         const float4 *guide = (const float4 *)a.guide;
         const float4 gp = guide[p];
         float cp[3];
@@ -108,7 +120,6 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
         const float isc2 = a.isc2;
         const float isz = 1.f / (a.kz * gp.w);
         const int step = (int)a.step;
-        const uint32_t m = M >= 0 ? (uint32_t)M : a.squarings;
         float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumw = 0.f;
 #pragma unroll
         for (int dy = -2; dy <= 2; ++dy) {
@@ -122,22 +133,13 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
                 const float4 gq = guide[q];
                 float cq[3];
                 filter_colour<IN>(a, q, cq);
-                float d = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-                d = d > 0.f ? d : 0.f;
-                if (M >= 0) {
-#pragma unroll
-                    for (int i = 0; i < M; ++i) d = d * d;
-                } else {
-                    for (uint32_t i = 0; i < m; ++i) d = d * d;
-                }
-                const float t = (gp.w - gq.w) * isz;
-                const float num = hitp ? hh * d : hh;
-                const float g = hitp ? 1.f + t * t : 1.f;
+                const float d = guide_normal_weight<M>(gp, gq, a.squarings);
+                float num, g;
+                guide_depth_terms(hh, d, gp, gq, hitp, isz, num, g);
                 const float dr = cp[0] - cq[0], dg = cp[1] - cq[1], db = cp[2] - cq[2];
                 const float e = dr * dr + dg * dg + db * db;
                 const float w = num / (g * (1.f + e * isc2));
-                // contributes only if positive and finite (a NaN fails both comparisons)
-                const bool ok = inside && ((gq.w >= 0.f) == hitp) && w > 0.f && w <= 3.402823466e+38f;
+                const bool ok = tap_counts(inside, gq, hitp, w);
                 sum0 = ok ? sum0 + w * cq[0] : sum0;
                 sum1 = ok ? sum1 + w * cq[1] : sum1;
                 sum2 = ok ? sum2 + w * cq[2] : sum2;
@@ -155,30 +157,9 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous(FilterPass a) {
         }
     }
     if (!LAST) {
-        if (live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], 0.f);
-        return;
+        if (tile.live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], 0.f);
     } else {
-        if (live) {
-            float *v = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
-            float src[5];
-            if (a.src.frame)
-                filter_src_pixel<false>(a.src, p, src);
-            else
-                filter_src_pixel<true>(a.src, p, src);
-            v[0] = o[0], v[1] = o[1], v[2] = o[2], v[3] = src[3], v[4] = src[4];  // alpha, depth: the input's bits
-            if (a.rgba8) ((uchar4 *)a.rgba8)[p] = quantized_pixel(v);
-        }
-        if (!a.out_rgbaz) return;
-        __syncthreads();
-        // row r of the block is the run of 5 * (its pixels in the image) floats at ((y0 + r) * W + x0) * 5
-        const uint32_t x0 = bx * kFilterBX, y0 = by * kFilterBY;
-        const uint32_t run = min(kFilterBX, W - x0) * 5;
-#pragma unroll
-        for (uint32_t c = 0; c < 5; ++c) {
-            const uint32_t i = c * kFilterBlock + threadIdx.x;
-            const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
-            if (y0 + r < H && col < run) a.out_rgbaz[((size_t)(y0 + r) * W + x0) * 5 + col] = s_px[i];
-        }
+        atrous_write_last<true>(a, tile, o, s_px);
     }
 }
 
@@ -190,21 +171,11 @@ int launch_filter_guide(const void *rayhit, uint32_t npix, void *guide, void *st
 }
 
 template <int IN, bool LAST>
-static void launch_atrous_m(const FilterPass &a, dim3 grid, hipStream_t s) {
+static auto atrous_kernel(const FilterPass &a) -> void (*)(FilterPass) {
     // demodulation touches the iteration that writes the result (k_demod_divide wrote the plane the first one reads)
-    if constexpr (IN == 0 && LAST) {
-        if (a.albedo) {
-            if (a.squarings == 5)
-                hipLaunchKernelGGL((k_atrous<IN, LAST, 5, true>), grid, dim3(kFilterBlock), 0, s, a);
-            else
-                hipLaunchKernelGGL((k_atrous<IN, LAST, -1, true>), grid, dim3(kFilterBlock), 0, s, a);
-            return;
-        }
-    }
-    if (a.squarings == 5)
-        hipLaunchKernelGGL((k_atrous<IN, LAST, 5>), grid, dim3(kFilterBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_atrous<IN, LAST, -1>), grid, dim3(kFilterBlock), 0, s, a);
+    if constexpr (IN == 0 && LAST)
+        if (a.albedo) return for_squarings(a.squarings, [](auto m) { return k_atrous<IN, LAST, decltype(m)::value, true>; });
+    return for_squarings(a.squarings, [](auto m) { return k_atrous<IN, LAST, decltype(m)::value>; });
 }
 
 // the demodulated call's pre-pass: a.src / a.albedo into a.out_plane
@@ -219,18 +190,8 @@ int launch_demod_divide(const FilterPass &a, void *stream) {
 }
 
 int launch_atrous(const FilterPass &a, void *stream) {
-    if (a.width == 0 || a.height == 0) return 0;
-    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    hipStream_t s = (hipStream_t)stream;
     const int in = !a.first ? 0 : (a.src.frame ? 1 : 2);
-    if (a.last) {
-        if (in == 0) launch_atrous_m<0, true>(a, grid, s);
-        else if (in == 1) launch_atrous_m<1, true>(a, grid, s);
-        else launch_atrous_m<2, true>(a, grid, s);
-    } else {
-        if (in == 0) launch_atrous_m<0, false>(a, grid, s);
-        else if (in == 1) launch_atrous_m<1, false>(a, grid, s);
-        else launch_atrous_m<2, false>(a, grid, s);
-    }
-    return launch_status();
+    if (a.last)
+        return launch_image(in == 0 ? atrous_kernel<0, true>(a) : in == 1 ? atrous_kernel<1, true>(a) : atrous_kernel<2, true>(a), a, stream);
+    return launch_image(in == 0 ? atrous_kernel<0, false>(a) : in == 1 ? atrous_kernel<1, false>(a) : atrous_kernel<2, false>(a), a, stream);
 }

@@ -3974,6 +3974,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 // progressive rendering: the displayable frame of unfinished per-pixel state
 #include "vmx_preview.inc"
 
+// what the image-space passes below share: the 32 x 8 tile, the guide's tap terms, the launch
+#include "vmx_image.inc"
 // G-buffer-guided a-trous filter of frames and previews
 #include "vmx_filter.inc"
 // G-buffer-guided upsampling: a low frame reconstructed under a full-size guide

@@ -1,15 +1,14 @@
 // vmx_temporal.inc — temporal accumulation: the previous accumulated frame reprojected into the new camera through the
 // new frame's G-buffer, stale history rejected by normal and plane distance, the new frame blended in (vmx_temporal_*).
-// Included by vmx_kernels.hip (inside its namespace, after vmx_filter.inc: it shares the filter's block shape).  The
+// Included by vmx_kernels.hip (inside its namespace, after vmx_image.inc: the tile and its way through LDS).  The
 // arithmetic is stated in include/vermilion_hip.h and restated in tests/temporal_spec.py; with -ffp-contract=off every
 // operation below rounds once, in the order written, and `/` is the correctly rounded division with denormals kept: bit
 // for bit the restatement.
 //
-//   k_temporal  one call, one lane per pixel, blocks of 32 x 8 pixels like k_atrous: a wave is two image rows of 32
-//               pixels.  The block's input pixels — eight runs of 160 floats — come in through LDS and the output pixels
-//               leave through the same words (as in k_atrous<.., LAST> / k_preview: dword accesses of consecutive lanes to
-//               consecutive addresses instead of five of stride 20 per lane); alpha and depth are never touched there, so
-//               they pass through bitwise, and a call in place reads a run before any lane of the block replaces it.
+//   k_temporal  one call, one lane per pixel of an image_tile.  The block's input pixels come in through LDS
+//               (tile_load_rgbaz) and the output pixels leave through the same words (tile_store_rgbaz); alpha and depth
+//               are never touched there, so they pass through bitwise, and a call in place reads a run before any lane
+//               of the block replaces it.
 //               The record is read as three float4s (as k_filter_guide reads it).  The state is three float4 planes,
 //               (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -): each of the four taps is three loads of 16 bytes per lane from the
 //               old buffer, neighbouring lanes at neighbouring addresses wherever the reprojection is coherent; the new
@@ -46,32 +45,19 @@ template <bool FIRST, bool MOTION, bool MOMENTS = false>
 __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
     __shared__ float s_px[kFilterBlock * 5];
     const uint32_t W = a.width, H = a.height;
-    // (a one-dimensional grid of blocks, row-major over the image, as k_atrous)
-    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t bx0 = bx * kFilterBX, by0 = by * kFilterBY;
-    const uint32_t x = bx0 + (threadIdx.x & (kFilterBX - 1));
-    const uint32_t y = by0 + threadIdx.x / kFilterBX;
-    const bool live = x < W && y < H;
-    const uint32_t p = y * W + x;  // (W * H <= 2^28: make_frame's size check)
-    // row r of the block is the run of 5 * (its pixels in the image) floats at ((by0 + r) * W + bx0) * 5
-    const uint32_t run = min(kFilterBX, W - bx0) * 5;
-#pragma unroll
-    for (uint32_t c = 0; c < 5; ++c) {
-        const uint32_t i = c * kFilterBlock + threadIdx.x;
-        const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
-        if (by0 + r < H && col < run) s_px[i] = a.in_rgbaz[((size_t)(by0 + r) * W + bx0) * 5 + col];
-    }
+    const ImageTile tile = image_tile(W, H);
+    const uint32_t x = tile.x, y = tile.y, p = tile.p;
+    tile_load_rgbaz(s_px, a.in_rgbaz, W, H, tile.bx0, tile.by0);
     __syncthreads();
-    if (live) {
-        float *v = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
+    if (tile.live) {
+        float *v = s_px + threadIdx.x * 5;
         const float c0 = v[0], c1 = v[1], c2 = v[2];
         const float4 *r = (const float4 *)a.rayhit + (size_t)p * 4;  // (location, distance) (normal, tri_id) (uv, tri_t, flags)
         const float4 ra = r[0], rb = r[1], rc = r[2];
         const bool hit = (__float_as_uint(rc.w) & 1u) != 0;
         const size_t npix = (size_t)W * H;
         float o0 = c0, o1 = c1, o2 = c2, n_new = 1.f;
-        const float lum = MOMENTS ? (0.2126f * c0 + 0.7152f * c1) + 0.0722f * c2 : 0.f;
+        const float lum = MOMENTS ? luminance(c0, c1, c2) : 0.f;
         float m1 = lum, m2 = lum * lum;
         if (!FIRST) {
             float Xhx = ra.x, Xhy = ra.y, Xhz = ra.z, mnx = rb.x, mny = rb.y, mnz = rb.z;
@@ -146,29 +132,12 @@ __global__ void __launch_bounds__(kFilterBlock) k_temporal(TemporalPass a) {
     }
     if (!a.out_rgbaz) return;
     __syncthreads();
-#pragma unroll
-    for (uint32_t c = 0; c < 5; ++c) {
-        const uint32_t i = c * kFilterBlock + threadIdx.x;
-        const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
-        if (by0 + r < H && col < run) a.out_rgbaz[((size_t)(by0 + r) * W + bx0) * 5 + col] = s_px[i];
-    }
+    tile_store_rgbaz(s_px, a.out_rgbaz, W, H, tile.bx0, tile.by0);
 }
 
 int launch_temporal(const TemporalPass &a, void *stream) {
-    if (a.width == 0 || a.height == 0) return 0;
-    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    if (a.moments) {
-        if (a.first)
-            hipLaunchKernelGGL((k_temporal<true, false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-        else if (a.motion)
-            hipLaunchKernelGGL((k_temporal<false, true, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-        else
-            hipLaunchKernelGGL((k_temporal<false, false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    } else if (a.first)
-        hipLaunchKernelGGL((k_temporal<true, false>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    else if (a.motion)
-        hipLaunchKernelGGL((k_temporal<false, true>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((k_temporal<false, false>), grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    return launch_status();
+    if (a.moments)
+        return launch_image(a.first ? k_temporal<true, false, true> : a.motion ? k_temporal<false, true, true> : k_temporal<false, false, true>,
+                            a, stream);
+    return launch_image(a.first ? k_temporal<true, false> : a.motion ? k_temporal<false, true> : k_temporal<false, false>, a, stream);
 }

@@ -1,10 +1,11 @@
 // vmx_upsample.inc — G-buffer-guided upsampling of a low-resolution frame under a full-size G-buffer (vmx_upsample_*).
-// Included by vmx_kernels.hip (inside its namespace), after vmx_filter.inc whose k_filter_guide packs both guides.  The
+// Included by vmx_kernels.hip (inside its namespace), after vmx_image.inc (the tile, the tap terms, the launch) and
+// vmx_filter.inc, whose k_filter_guide packs both guides.  The
 // arithmetic is stated in include/vermilion_hip.h ("guided upsampling") and restated in tests/upsample_spec.py; with
 // -ffp-contract=off every operation below rounds once, in the order written, and `/` is the correctly rounded division
 // with denormals kept: bit for bit the restatement.
 //
-//   k_upsample  one lane per full pixel, blocks of 32 x 8 full pixels as k_atrous has them.  The four taps are unrolled;
+//   k_upsample  one lane per full pixel of an image_tile.  The four taps are unrolled;
 //               hit / miss, the skip rules and the anchor are selects, not branches (a tap outside the low image loads
 //               tap (0, 0)'s records and is selected away).  The low frame and guide are NOT staged in LDS: a block's
 //               32 x 8 full pixels touch at most 33 x 9 low pixels of 36 bytes (17 x 5 at ratio 1/2), about 10 KB, which
@@ -13,21 +14,15 @@
 //               records as in k_atrous.  The call is bound by what it must move per full pixel (16 B guide read, 24 B
 //               written) against at most 36 B per low pixel, read from HBM once; staging would add a barrier and, for
 //               the ratios that are no integer, a per-block footprint computed twice, to save cache hits.
-//               The block's 256 pixels — eight runs of 160 floats — leave through LDS as dword stores of consecutive
-//               lanes to consecutive addresses, as k_atrous<.., LAST> writes them; rgba8 from the same values.
+//               The block's pixels leave through LDS (tile_store_rgbaz); rgba8 from the same values.
 //               M: normal_squarings as a constant (the default, 5) or -1: read from the pass.
 template <int M>
 __global__ void __launch_bounds__(kFilterBlock) k_upsample(UpsamplePass a) {
     __shared__ float s_px[kFilterBlock * 5];
     const uint32_t W = a.width, H = a.height, lw = a.low_width, lh = a.low_height;
-    // (a one-dimensional grid of blocks, row-major over the image: the second grid dimension ends at 65535)
-    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t x = bx * kFilterBX + (threadIdx.x & (kFilterBX - 1));
-    const uint32_t y = by * kFilterBY + threadIdx.x / kFilterBX;
-    const bool live = x < W && y < H;
-    const uint32_t p = y * W + x;  // (W * H <= 2^28: vmx_upsample_create's size check)
-    if (live) {
+    const ImageTile tile = image_tile(W, H);
+    const uint32_t x = tile.x, y = tile.y, p = tile.p;
+    if (tile.live) {
         const float4 *glo = (const float4 *)a.guide_low;
         const float4 gp = ((const float4 *)a.guide_full)[p];
         const float rx = (float)lw / (float)W, ry = (float)lh / (float)H;
@@ -37,7 +32,6 @@ __global__ void __launch_bounds__(kFilterBlock) k_upsample(UpsamplePass a) {
         const float fx = u - (float)X0, fy = v - (float)Y0;
         const bool hitp = gp.w >= 0.f;
         const float isz = 1.f / (a.sigma_depth * gp.w);
-        const uint32_t m = M >= 0 ? (uint32_t)M : a.squarings;
         float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f, sumw = 0.f, best = -1.f;
         uint32_t anchor = Y0 * lw + X0;
 #pragma unroll
@@ -53,20 +47,11 @@ __global__ void __launch_bounds__(kFilterBlock) k_upsample(UpsamplePass a) {
                 const float4 gq = glo[q];
                 const float *cq = a.low + (size_t)q * 5;
                 const float c0 = cq[0], c1 = cq[1], c2 = cq[2];
-                float d = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-                d = d > 0.f ? d : 0.f;
-                if (M >= 0) {
-#pragma unroll
-                    for (int k = 0; k < M; ++k) d = d * d;
-                } else {
-                    for (uint32_t k = 0; k < m; ++k) d = d * d;
-                }
-                const float t = (gp.w - gq.w) * isz;
-                const float num = hitp ? b * d : b;
-                const float g = hitp ? 1.f + t * t : 1.f;
+                const float d = guide_normal_weight<M>(gp, gq, a.squarings);
+                float num, g;
+                guide_depth_terms(b, d, gp, gq, hitp, isz, num, g);
                 const float w = num / g;
-                // contributes only if positive and finite (a NaN fails both comparisons)
-                const bool ok = inside && ((gq.w >= 0.f) == hitp) && w > 0.f && w <= 3.402823466e+38f;
+                const bool ok = tap_counts(inside, gq, hitp, w);
                 sum0 = ok ? sum0 + w * c0 : sum0;
                 sum1 = ok ? sum1 + w * c1 : sum1;
                 sum2 = ok ? sum2 + w * c2 : sum2;
@@ -76,7 +61,7 @@ __global__ void __launch_bounds__(kFilterBlock) k_upsample(UpsamplePass a) {
         const float *la = a.low + (size_t)anchor * 5;
         const float l0 = la[0], l1 = la[1], l2 = la[2], l3 = la[3], l4 = la[4];
         const bool any = sumw > 0.f;
-        float *o = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
+        float *o = s_px + threadIdx.x * 5;
         o[0] = any ? sum0 / sumw : l0;
         o[1] = any ? sum1 / sumw : l1;
         o[2] = any ? sum2 / sumw : l2;
@@ -85,23 +70,9 @@ __global__ void __launch_bounds__(kFilterBlock) k_upsample(UpsamplePass a) {
     }
     if (!a.out_rgbaz) return;
     __syncthreads();
-    // row r of the block is the run of 5 * (its pixels in the image) floats at ((y0 + r) * W + x0) * 5
-    const uint32_t x0 = bx * kFilterBX, y0 = by * kFilterBY;
-    const uint32_t run = min(kFilterBX, W - x0) * 5;
-#pragma unroll
-    for (uint32_t c = 0; c < 5; ++c) {
-        const uint32_t i = c * kFilterBlock + threadIdx.x;
-        const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
-        if (y0 + r < H && col < run) a.out_rgbaz[((size_t)(y0 + r) * W + x0) * 5 + col] = s_px[i];
-    }
+    tile_store_rgbaz(s_px, a.out_rgbaz, W, H, tile.bx0, tile.by0);
 }
 
 int launch_upsample(const UpsamplePass &a, void *stream) {
-    if (a.width == 0 || a.height == 0) return 0;
-    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    if (a.squarings == 5)
-        hipLaunchKernelGGL(k_upsample<5>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_upsample<-1>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_image(for_squarings(a.squarings, [](auto m) { return k_upsample<decltype(m)::value>; }), a, stream);
 }

@@ -1,11 +1,11 @@
 // vmx_variance.inc — variance-guided denoising: the per-pixel variance of a moments accumulator's luminance
 // (vmx_temporal_accumulate_variance_device) and the a-trous filter whose colour stop it steers
-// (vmx_filter_apply_variance_device).  Included by vmx_kernels.hip (inside its namespace, after vmx_temporal.inc: it shares
-// the filter's block shape and helpers).  The arithmetic is stated in include/vermilion_hip.h and restated in
-// tests/variance_spec.py; with -ffp-contract=off every operation below rounds once, in the order written, and `/` is the
+// (vmx_filter_apply_variance_device).  Included by vmx_kernels.hip (inside its namespace, after vmx_image.inc and
+// vmx_filter.inc: the tile, the tap terms, the filter's pixel helpers and atrous_write_last).  The arithmetic is stated
+// in include/vermilion_hip.h and restated in tests/variance_spec.py; with -ffp-contract=off every operation below rounds once, in the order written, and `/` is the
 // correctly rounded division with denormals kept: bit for bit the restatement.  No transcendentals.
 //
-//   k_variance       one lane per pixel, blocks of 32 x 8 pixels.  It reads the state k_temporal<.., MOMENTS> just wrote:
+//   k_variance       one lane per pixel of an image_tile.  It reads the state k_temporal<.., MOMENTS> just wrote:
 //                    n' (the colour plane's .w, one dword), the guide and the moments.  A pixel with n' >= min_history
 //                    leaves with its temporal variance; a wave none of whose lanes is younger skips the window
 //                    altogether (one ballot).  The window is 7 x 7 over the same state, rows in a loop and the seven
@@ -23,17 +23,13 @@
 //                    last iteration drops it and writes the caller's buffers as k_atrous<0, LAST> does.
 constexpr float kVarianceEps = 1e-10f;  // VMX_VARIANCE_EPS
 
-__device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
 template <int M>
 __global__ void __launch_bounds__(kFilterBlock) k_variance(VariancePass a) {
     const uint32_t W = a.width, H = a.height;
-    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t x = bx * kFilterBX + (threadIdx.x & (kFilterBX - 1));
-    const uint32_t y = by * kFilterBY + threadIdx.x / kFilterBX;
-    const bool live = x < W && y < H;
-    const uint32_t p = live ? y * W + x : 0u;  // (W * H <= 2^28: make_frame's size check; a lane off the image reads pixel 0)
+    const ImageTile tile = image_tile(W, H);
+    const uint32_t x = tile.x, y = tile.y;
+    const bool live = tile.live;
+    const uint32_t p = live ? tile.p : 0u;  // (a lane off the image reads pixel 0)
     const size_t npix = (size_t)W * H;
     const float4 *st_c = (const float4 *)a.state, *st_g = st_c + npix;
     const float2 *st_m = (const float2 *)(st_g + 2 * npix);
@@ -47,7 +43,6 @@ __global__ void __launch_bounds__(kFilterBlock) k_variance(VariancePass a) {
         const float4 gp = st_g[p];
         const bool hitp = gp.w >= 0.f;
         const float isz = 1.f / (a.sigma_depth * gp.w);
-        const uint32_t m = M >= 0 ? (uint32_t)M : a.squarings;
         float s1 = 0.f, s2 = 0.f, sw = 0.f;
 #pragma unroll 1
         for (int dy = -3; dy <= 3; ++dy) {
@@ -59,18 +54,10 @@ __global__ void __launch_bounds__(kFilterBlock) k_variance(VariancePass a) {
                 const uint32_t q = inside ? (uint32_t)qy * W + (uint32_t)qx : p;
                 const float4 gq = st_g[q];
                 const float2 mq = st_m[q];
-                float d = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-                d = d > 0.f ? d : 0.f;
-                if (M >= 0) {
-#pragma unroll
-                    for (int i = 0; i < M; ++i) d = d * d;
-                } else {
-                    for (uint32_t i = 0; i < m; ++i) d = d * d;
-                }
+                const float d = guide_normal_weight<M>(gp, gq, a.squarings);
                 const float t = (gp.w - gq.w) * isz;
                 const float w = hitp ? d / (1.f + t * t) : 1.f;
-                // counts only if positive and finite (a NaN fails both comparisons)
-                const bool ok = inside && ((gq.w >= 0.f) == hitp) && w > 0.f && w <= 3.402823466e+38f;
+                const bool ok = tap_counts(inside, gq, hitp, w);
                 s1 = ok ? s1 + w * mq.x : s1;
                 s2 = ok ? s2 + w * mq.y : s2;
                 sw = ok ? sw + w : sw;
@@ -86,13 +73,7 @@ __global__ void __launch_bounds__(kFilterBlock) k_variance(VariancePass a) {
 }
 
 int launch_variance(const VariancePass &a, void *stream) {
-    if (a.width == 0 || a.height == 0) return 0;
-    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    if (a.squarings == 5)
-        hipLaunchKernelGGL(k_variance<5>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_variance<-1>, grid, dim3(kFilterBlock), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_image(for_squarings(a.squarings, [](auto m) { return k_variance<decltype(m)::value>; }), a, stream);
 }
 
 template <bool DEMOD>
@@ -116,20 +97,15 @@ template <bool LAST, int M, bool DEMOD>
 __global__ void __launch_bounds__(kFilterBlock) k_atrous_var(FilterPass a) {
     __shared__ float s_px[LAST ? kFilterBlock * 5 : 1];
     const uint32_t W = a.width, H = a.height;
-    const uint32_t nbx = (W + kFilterBX - 1) / kFilterBX;
-    const uint32_t by = blockIdx.x / nbx, bx = blockIdx.x - by * nbx;
-    const uint32_t x = bx * kFilterBX + (threadIdx.x & (kFilterBX - 1));
-    const uint32_t y = by * kFilterBY + threadIdx.x / kFilterBX;
-    const bool live = x < W && y < H;
-    const uint32_t p = y * W + x;  // (W * H <= 2^28: make_frame's size check)
+    const ImageTile tile = image_tile(W, H);
+    const uint32_t x = tile.x, y = tile.y, p = tile.p;
     float o[3] = {0.f, 0.f, 0.f}, vo = 0.f;
-    if (live) {
+    if (tile.live) {
         const float4 *guide = (const float4 *)a.guide, *plane = (const float4 *)a.in_plane;
         const float4 gp = guide[p], cp = plane[p];
         const bool hitp = gp.w >= 0.f;
         const float isz = 1.f / (a.kz * gp.w);
         const int step = (int)a.step;
-        const uint32_t m = M >= 0 ? (uint32_t)M : a.squarings;
         // the 3 x 3 gaussian of the variance around p, at one pixel's distance whatever the step
         float vbar = 0.f;
 #pragma unroll
@@ -156,21 +132,12 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous_var(FilterPass a) {
                 const bool inside = (uint32_t)qx < W && (uint32_t)qy < H;
                 const uint32_t q = inside ? (uint32_t)qy * W + (uint32_t)qx : p;
                 const float4 gq = guide[q], cq = plane[q];
-                float d = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-                d = d > 0.f ? d : 0.f;
-                if (M >= 0) {
-#pragma unroll
-                    for (int i = 0; i < M; ++i) d = d * d;
-                } else {
-                    for (uint32_t i = 0; i < m; ++i) d = d * d;
-                }
-                const float t = (gp.w - gq.w) * isz;
-                const float num = hitp ? hh * d : hh;
-                const float g = hitp ? 1.f + t * t : 1.f;
+                const float d = guide_normal_weight<M>(gp, gq, a.squarings);
+                float num, g;
+                guide_depth_terms(hh, d, gp, gq, hitp, isz, num, g);
                 const float dl = lp - luminance(cq.x, cq.y, cq.z);
                 const float w = num / (g * (1.f + (dl * dl) / den));
-                // contributes only if positive and finite (a NaN fails both comparisons)
-                const bool ok = inside && ((gq.w >= 0.f) == hitp) && w > 0.f && w <= 3.402823466e+38f;
+                const bool ok = tap_counts(inside, gq, hitp, w);
                 sum0 = ok ? sum0 + w * cq.x : sum0;
                 sum1 = ok ? sum1 + w * cq.y : sum1;
                 sum2 = ok ? sum2 + w * cq.z : sum2;
@@ -190,27 +157,9 @@ __global__ void __launch_bounds__(kFilterBlock) k_atrous_var(FilterPass a) {
         }
     }
     if (!LAST) {
-        if (live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], vo);
-        return;
+        if (tile.live) ((float4 *)a.out_plane)[p] = make_float4(o[0], o[1], o[2], vo);
     } else {
-        if (live) {
-            float *v = s_px + threadIdx.x * 5;  // (an odd stride in words: no bank conflict)
-            float src[5];
-            filter_src_pixel<false>(a.src, p, src);
-            v[0] = o[0], v[1] = o[1], v[2] = o[2], v[3] = src[3], v[4] = src[4];  // alpha, depth: the input's bits
-            if (a.rgba8) ((uchar4 *)a.rgba8)[p] = quantized_pixel(v);
-        }
-        if (!a.out_rgbaz) return;
-        __syncthreads();
-        // row r of the block is the run of 5 * (its pixels in the image) floats at ((y0 + r) * W + x0) * 5
-        const uint32_t x0 = bx * kFilterBX, y0 = by * kFilterBY;
-        const uint32_t run = min(kFilterBX, W - x0) * 5;
-#pragma unroll
-        for (uint32_t c = 0; c < 5; ++c) {
-            const uint32_t i = c * kFilterBlock + threadIdx.x;
-            const uint32_t r = i / (kFilterBX * 5), col = i - r * (kFilterBX * 5);
-            if (y0 + r < H && col < run) a.out_rgbaz[((size_t)(y0 + r) * W + x0) * 5 + col] = s_px[i];
-        }
+        atrous_write_last<false>(a, tile, o, s_px);  // (the variance-guided call takes frames only)
     }
 }
 
@@ -225,19 +174,11 @@ int launch_variance_pack(const FilterPass &a, const float *variance, void *strea
 }
 
 template <bool LAST, bool DEMOD>
-static void launch_atrous_var_m(const FilterPass &a, dim3 grid, hipStream_t s) {
-    if (a.squarings == 5)
-        hipLaunchKernelGGL((k_atrous_var<LAST, 5, DEMOD>), grid, dim3(kFilterBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_atrous_var<LAST, -1, DEMOD>), grid, dim3(kFilterBlock), 0, s, a);
+static auto atrous_var_kernel(const FilterPass &a) {
+    return for_squarings(a.squarings, [](auto m) { return k_atrous_var<LAST, decltype(m)::value, DEMOD>; });
 }
 
 int launch_atrous_var(const FilterPass &a, void *stream) {
-    if (a.width == 0 || a.height == 0) return 0;
-    const dim3 grid(((a.width + kFilterBX - 1) / kFilterBX) * ((a.height + kFilterBY - 1) / kFilterBY));
-    hipStream_t s = (hipStream_t)stream;
-    if (!a.last) launch_atrous_var_m<false, false>(a, grid, s);
-    else if (a.albedo) launch_atrous_var_m<true, true>(a, grid, s);
-    else launch_atrous_var_m<true, false>(a, grid, s);
-    return launch_status();
+    return launch_image(!a.last ? atrous_var_kernel<false, false>(a) : a.albedo ? atrous_var_kernel<true, true>(a) : atrous_var_kernel<true, false>(a),
+                        a, stream);
 }
