@@ -127,7 +127,7 @@ typedef struct vmx_opts {
                               per-pixel claims for the camera rays; bit 12: the rays of a claimed pixel go through ray
                               generation, traversal and shading kernels as the others do, instead of being formed, tested
                               and shaded in the shading kernel alone; bit 13: no list claims for the pixels without a
-                              claim),
+                              claim; bit 14: bounce rays walk the reference tree alone, not the scene's guide tree),
                               [1] max paths per pass, [2] tail threshold, [3] refill_min, [4] shade_min,
                               [5] bounce reordering key (A/B library only), [6] LDS stack levels — all forms and
                               settings produce the same frame (see api_render.inc: render_impl, make_tuning) */
@@ -400,6 +400,18 @@ int vmx_pixel_claim_lists(const vmx_scene *scene, const vmx_camera *cam, const v
 /* Debug entry: how many camera rays of the last render call on this scene were settled by a list claim.  0 where no
  * claims were built, with reserved[0] bit 11 or bit 13, and in the counting build. */
 int vmx_list_settled_rays(const vmx_scene *scene, uint64_t *rays);
+/* Debug entry: the bounce rays of the last render call on this scene that the bounce traversal kernel took over the
+ * scene's guide tree.  A VMX_BVH_REFERENCE scene also holds a quality tree of the same triangles (the guide; about
+ * 64 bytes per triangle of device memory, counted by vmx_scene_describe).  A bounce ray walks the guide, and a per-ray
+ * rule decides whether the reference tree returns exactly the pair (t, triangle) that walk found: `settled` counts
+ * those rays, `fallback` the others, which the same kernel then traces over the reference tree; the frame is the same
+ * bit for bit either way.  Both are 0 with reserved[0] bit 14, in the counting build, for a scene built with another
+ * builder, and after a vmx_scene_update that moved vertices without VMX_UPDATE_REBUILD (a refit leaves the guide stale
+ * from then on; a VMX_UPDATE_REBUILD of a host-built reference tree builds the guide of the new positions beside it). */
+int vmx_guide_rays(const vmx_scene *scene, uint64_t *settled, uint64_t *fallback);
+/* Debug entry: the entries of the bounce-generation lists that the last render call on this scene handed to the
+ * guide form of the traversal kernel, counted on the host: settled + fallback of vmx_guide_rays equals it. */
+int vmx_guide_list_entries(const vmx_scene *scene, uint64_t *entries);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

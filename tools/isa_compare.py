@@ -111,11 +111,16 @@ def main():
     ap.add_argument("parent_csrc", type=pathlib.Path)
     ap.add_argument("this_csrc", type=pathlib.Path)
     ap.add_argument("-o", "--out", type=pathlib.Path, help="also write the table here")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=TEXT",
+                    help="a kernel whose signature changed: the parent's symbols are compared under the name re.sub gives them")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(2) as pool:
         jobs = [pool.submit(assembly, d.resolve(), pathlib.Path(tmp) / f"{n}.s")
                 for n, d in (("parent", a.parent_csrc), ("this", a.this_csrc))]
         parent, this = (kernels(j.result()) for j in jobs)
+    for r in a.rename:
+        pat, text = r.split("=", 1)
+        parent = {re.sub(pat, text, sym): v for sym, v in parent.items()}
     rows, bad = compare(parent, this)
     n_image = sum(" image " in r for r in rows)
     head = [f"# tools/isa_compare.py: {len(rows)} kernels, {n_image} image-space; parent/this per figure",

@@ -22,10 +22,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLASSES = [
     # (shade_camera: one timed interval, two launches — the dense form over the unclaimed slots and its CLAIMED
     # instantiation over the claimed ones; a class with several patterns adds their launches' counters and durations up)
-    ("raygen", "k_raygen<0>"), ("trace_camera", "k_trace_w<0, false, false>"),
+    ("raygen", "k_raygen<0>"), ("trace_camera", "k_trace_w<0, false, false, false>"),
     ("shade_camera", ("k_shade<0, false, false, 0, true, false>", "k_shade<0, false, false, 0, true, true>")),
     # (one-phase bounce generations go through dense ray records, all kept: the SORT instantiation with WorkDev::keep_all)
-    ("trace_bounce", "k_trace_w<1, false, true>"), ("shade_bounce", "k_shade<1, false, false, 2, false, false>"),
+    # (with the scene's guide tree, guide_walk.h, the timed interval is two launches as well: the GUIDE instantiation and
+    # the plain one over the fallback list)
+    ("trace_bounce", ("k_trace_w<1, false, true, true>", "k_trace_w<1, false, true, false>")), ("shade_bounce", "k_shade<1, false, false, 2, false, false>"),
     ("tail", "k_paths<false, 2"), ("fused", "k_paths<false, 0"), ("resolve", "k_resolve"),
 ]
 HEADLINE_FORM = 0x100

@@ -194,6 +194,7 @@ int vmx_multi_create(const float *pos, const float *nrm, const float *uv, uint32
             sc->builder = first->builder;
             sc->ntris = first->ntris, sc->leaf_size = first->leaf_size;
             sc->bvh = first->bvh;
+            sc->guide.host = first->guide.host, sc->guide.scene_max = first->guide.scene_max;
             sc->spheres = first->spheres;
             std::memcpy(sc->bounds_lo, first->bounds_lo, sizeof(sc->bounds_lo));
             std::memcpy(sc->bounds_hi, first->bounds_hi, sizeof(sc->bounds_hi));

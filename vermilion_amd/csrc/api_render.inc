@@ -16,6 +16,7 @@ Tuning make_tuning(const vmx_scene *sc, const vmx_opts *o) {
     tn.sorted = false;
     tn.bounce_records = false;
     tn.pool = false;
+    tn.guide = false;
     // LDS stack levels per lane (+1 scratch level), 512 B per level and wave.  Measured on the Sponza
     // stand-in: camera rays rarely go deep and gain from the 8th wave per SIMD that 8 levels leave
     // room for (52.6 -> 50.6 ms); the bounce kernel, once its record fetch is quad-cooperative, prefers
@@ -36,7 +37,7 @@ Tuning make_tuning(const vmx_scene *sc, const vmx_opts *o) {
 
 
 // fills the stack fields of a WorkDev and makes sure the global overflow slab is large enough
-int bind_stack(vmx_scene *sc, const Tuning &tn, uint32_t entries, uint32_t grid, uint64_t items, WorkDev &wk) {
+int bind_stack(vmx_scene *sc, const Tuning &tn, uint32_t entries, uint32_t grid, uint64_t items, WorkDev &wk, bool guided = false) {
     // items a wave reserves from its work source per atomic: 256 when every lane will take >= 256 of them, else 128
     // (measured: early-stop frame 15.6 -> 14.3 ms with 128, whole 256-spp frame unchanged; 64 costs the camera-ray
     // kernel of the big frame 2 ms), 64 for launches of fewer than 64 items per lane: what a wave still holds privately
@@ -47,7 +48,10 @@ int bind_stack(vmx_scene *sc, const Tuning &tn, uint32_t entries, uint32_t grid,
     wk.lds_entries = entries;
     wk.leaf_min = tn.leaf_min;
     // + 1: k_trace_w keeps its bottom entry in LDS level 0
-    wk.overflow_entries = sc->dev.stack_entries + 1 > entries ? sc->dev.stack_entries + 1 - entries : 1u;
+    // (guided: the launch walks the scene's guide tree, guide_walk.h, which may be the deeper of the two, and the launch
+    // over its fallback list the reference tree: the slab is sized for either.  Every other launch is sized as it was.)
+    const uint32_t depth = std::max(sc->dev.stack_entries, guided && sc->guide.valid ? sc->guide.stack_entries : 0u);
+    wk.overflow_entries = depth + 1 > entries ? depth + 1 - entries : 1u;
     const size_t waves = (size_t)grid * (kPathsBlock / 64);
     if (sc->ws.overflow_stack.ensure(waves * wk.overflow_entries * 64 * 8))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the overflow stack");
@@ -67,6 +71,11 @@ LaunchCfg paths_cfg(const vmx_scene *sc, uint32_t entries, uint64_t items, int b
     return c;
 }
 
+// blocks per CU of the launch that traces a guided bounce generation's fallback list over the reference tree (run_ids): the
+// list is a fraction of a per cent of the generation where the guide is worth having, and every wave of the launch may
+// leave the tail of one record chunk unused, which the record lists are padded for
+constexpr uint32_t kGuideFallbackBlocks = 2;
+
 // ---- split wavefront (pipeline 0): k_trace_q + k_shade + id queues ---------------------------
 int ensure_paths(vmx_scene *sc, size_t nslots, PathArrays &pa, IdQueue q[3]) {
     Workspace &ws = sc->ws;
@@ -74,7 +83,8 @@ int ensure_paths(vmx_scene *sc, size_t nslots, PathArrays &pa, IdQueue q[3]) {
     // path slots — or, when the traversal kernels hand their rays on as records (k_trace_w<.., SORT>), the padded record
     // list, which is up to 256 entries per wave of the launch longer (at most 8 blocks of 4 waves per CU): each sub-list
     // holds its share of that, so no append can reach past it by construction
-    const size_t list_pad = (size_t)sc->num_cus * 8 * (kPathsBlock / 64) * 256;
+    // (+ kGuideFallbackBlocks: the second launch of a guided bounce generation appends to the same list, run_ids)
+    const size_t list_pad = (size_t)sc->num_cus * (8 + kGuideFallbackBlocks) * (kPathsBlock / 64) * 256;
     const uint32_t sub_cap = (uint32_t)((nslots + list_pad) / kSubQueues + 1024);
     if (ws.rayA.ensure(nslots * 16) || ws.state.ensure(nslots * 64) || ws.hit.ensure(nslots * 8) ||
         ws.rad.ensure(nslots * 16) ||
@@ -144,7 +154,7 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
         if (rc) return rc;
         const uint32_t entries = tail ? tn.lds_entries : tn.lds_bounce;
         LaunchCfg cfg = paths_cfg(sc, entries, total, tail ? tail_blocks : trace_blocks);
-        rc = bind_stack(sc, tn, entries, cfg.grid, total, wk);
+        rc = bind_stack(sc, tn, entries, cfg.grid, total, wk, !tail && tn.guide);
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, kSubQueues * 32 * 4, s));
         if ((rc = timed_begin(ws, timed, s, 1, tail ? VMX_K_TAIL : VMX_K_TRACE_BOUNCE))) return rc;
@@ -162,7 +172,30 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
                 wk.keep_all = tn.sorted ? 0u : 1u;
                 HIP_TRY(hipMemsetAsync(ws.out_count.p, 0, 4, s));
             }
-            LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, nopx, pa, ctr, count, true, cfg, s));
+            if (tn.guide && sc->guide.valid && ws.guide_fb.p) {
+                // over the guide tree first (guide_walk.h); then today's kernel once more, over the rays the per-ray rule did
+                // not settle: it reads the list's length on the device, appends to the same record list, and every ray is
+                // counted by the launch that settles it.  Both launches are one timed interval.
+                GuideDev gd;
+                gd.base = sc->guide.geom.p, gd.tri_off = sc->guide.tri_off, gd.root_ref = sc->guide.root_ref;
+                gd.scene_max = sc->guide.scene_max;
+                gd.fb_capacity = (uint32_t)std::min<size_t>(ws.guide_fb.n, 0xFFFFFFFFu);
+                gd.fb_ids = ws.guide_fb.p, gd.fb_count = ws.guide_fb_count.p, gd.ctr = ws.guide_ctr.p, gd.overflow = ctr;
+                ws.guide_entries += total;
+                HIP_TRY(hipMemsetAsync(ws.guide_fb_count.p, 0, 4, s));
+                HIP_TRY(hipMemsetAsync(ws.guide_heads.p, 0, 4, s));
+                LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, nopx, pa, ctr, count, true, cfg, s, &gd));
+                WorkDev wf = wk;
+                wf.heads = ws.guide_heads.p, wf.nsrc = 1;
+                wf.qids.ids = ws.guide_fb.p, wf.qids.counts = ws.guide_fb_count.p, wf.qids.sub_capacity = gd.fb_capacity;
+                LaunchCfg cf = cfg;
+                cf.grid = std::min<uint32_t>(cfg.grid, (uint32_t)sc->num_cus * kGuideFallbackBlocks);
+                wf.reserve = 64;  // (cf.grid <= cfg.grid: the overflow slab bound for the first launch holds this one's waves)
+                LAUNCH_TRY(launch_trace_q(sc->dev, fr, wf, nopx, pa, ctr, count, true, cf, s));
+                launches += 1;
+            } else {
+                LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, nopx, pa, ctr, count, true, cfg, s));
+            }
         }
         if ((rc = timed_end(timed, s))) return rc;
         HIP_TRY(hipMemsetAsync(q[cur ^ 1].counts, 0, kSubQueues * 32 * 4, s));
@@ -203,6 +236,10 @@ int finish_stats(vmx_scene *sc, hipStream_t s, std::vector<TimedLaunch> &timed, 
     stats->kernel_launches = launches;
     sc->fused_paths = h.fused;
     sc->list_settled = h.listed;
+    unsigned long long guide_rays[2] = {0, 0};
+    if (ws.guide_ctr.p) HIP_TRY(hipMemcpy(guide_rays, ws.guide_ctr.p, sizeof(guide_rays), hipMemcpyDeviceToHost));
+    sc->guide_settled = guide_rays[0], sc->guide_fallback = guide_rays[1];
+    sc->guide_entries = ws.guide_entries, ws.guide_entries = 0;
     std::memset(&sc->timings, 0, sizeof(sc->timings));
     for (auto &tl : timed) {
         float ms = 0.f;
@@ -250,7 +287,7 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     //   4 split wavefront for every pass (form 0 hands passes of fewer than 4 M paths to form 1's
     //     kernel, which needs no per-generation host round trip)
     const uint32_t pipeline = job.pipeline = opts->reserved[0] & 0xFFu;  // (bit 8: one-phase shading, see two_phase below)
-    if (pipeline > 4 || (opts->reserved[0] & ~0x3FFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims; bit 12: claimed pixels are not fused; bit 13: no list claims)
+    if (pipeline > 4 || (opts->reserved[0] & ~0x7FFFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");  // (bit 11: no per-pixel claims; bit 12: claimed pixels are not fused; bit 13: no list claims; bit 14: no guide tree)
     if ((rc = ab_check_forms(sc, pipeline))) return rc;
     if ((rc = ab_check_pool(opts))) return rc;  // (reserved[0] bit 10)
     const bool split_any = job.split_any = pipeline == 0 || pipeline == 4;
@@ -266,6 +303,10 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     // colour) when they finish, and hands the others on as records; reserved[0] bit 9 keeps k_shade_ends for them
     tn.sorted = tn.two_phase && !(opts->reserved[0] & 0x200u);
     tn.pool = ab_pool_bit(opts) && !tn.sorted && !count;
+    // bounce generations of the split passes walk the scene's guide tree (guide_walk.h) unless reserved[0] bit 14 keeps them
+    // on the reference tree; never the counting build (its visit counts are the oracle's) nor the A/B pool.  The fused
+    // kernels (k_paths: small passes, the tail) and the camera kernel keep the reference tree.
+    tn.guide = sc->guide.valid && !count && !ab_pool_bit(opts) && !(opts->reserved[0] & 0x4000u);
     fr.bounce_bits = tn.sorted ? 1u : 0u;
     fr.camera_bits = tn.two_phase ? 1u : 0u;  // read by k_trace_w<0, .., SORT> / k_shade_ends<0> only
     if (!opts->reserved[2]) {
@@ -295,11 +336,12 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     // consequences other than time.  VMX_MEM_BUDGET_MB lowers the budget (tests, co-tenancy).
     const size_t n_pad_cap = ((size_t)npix + 63u) & ~(size_t)63u;
     if (!opts->samples_per_batch && !legacy) {
-        const size_t per_path = 16 + 64 + 8 + 16 + 12 /* three id lists */ + (sc->dev.tex ? 16 : 0) + (tn.sort_mode ? 12 : 0) + (fr.elide_dead ? 5 : 0) + 32;
+        const size_t per_path = 16 + 64 + 8 + 16 + 12 /* three id lists */ + (sc->dev.tex ? 16 : 0) + (tn.sort_mode ? 12 : 0) + (fr.elide_dead ? 5 : 0) + 32 + (tn.guide ? 4 : 0) /* the fallback list */;
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         const size_t held = ws.rayA.n + ws.state.n + ws.hit.n + ws.rad.n + ws.thr.n + (ws.ids[0].n + ws.ids[1].n + ws.ids[2].n) * 4 +
-                            (ws.sort_keys[0].n + ws.sort_keys[1].n + ws.ids_sorted.n) * 4 + ws.out_rec.n + ws.live_ids.n * 4;
+                            (ws.sort_keys[0].n + ws.sort_keys[1].n + ws.ids_sorted.n) * 4 + ws.out_rec.n + ws.live_ids.n * 4 +
+                            ws.guide_fb.n * 4;
         job.mem_budget = (uint64_t)((free_b + held) / 10 * 9);
         if (const char *e = std::getenv("VMX_MEM_BUDGET_MB")) {
             const uint64_t cap = std::strtoull(e, nullptr, 10) << 20;
@@ -337,7 +379,7 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
         HIP_TRY((hipError_t)query_trace_q_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_primary + 1) * 512, count, false,
                                                         tn.sorted, fr.elide_dead != 0, &job.tb));
         HIP_TRY((hipError_t)query_trace_q_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_bounce + 1) * 512, count, true,
-                                                        tn.sorted || tn.bounce_records, false, &job.tbb));
+                                                        tn.sorted || tn.bounce_records, false, &job.tbb, tn.guide));
         if (job.tb < 1 || job.tbb < 1) return fail(VMX_ERR_HIP, "trace kernel does not fit on a CU");
         job.tbb = ab_bounce_blocks(job.tbb);
     }
@@ -441,11 +483,17 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
     if (job.split_any && (tn.sorted || tn.bounce_records)) {
         // every path of a pass may need a record; each wave of the launch leaves at most the tail of one chunk of 256 unused
         // (camera-ray records are 32 bytes, bounce-ray records 16)
-        const size_t waves = (size_t)sc->num_cus * (size_t)std::max(job.tb, job.tbb) * (kPathsBlock / 64);
+        const size_t waves = (size_t)sc->num_cus * ((size_t)std::max(job.tb, job.tbb) + (tn.guide ? kGuideFallbackBlocks : 0u)) * (kPathsBlock / 64);
         ws.out_capacity = (size_t)n_pad_max * smax + waves * 256 + 1024;
         if (ws.out_capacity > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "pass too large for the sorted ray records");
         if (ws.out_rec.ensure(ws.out_capacity * (tn.sorted ? 32 : 16)) || ws.out_count.ensure(32))
             return fail(VMX_ERR_NOMEM, "hipMalloc failed for the ray records");
+    }
+    if (job.split_any) {
+        // (the counters always: finish_stats reads them; the fallback list holds what a generation's id list holds)
+        if (ws.guide_ctr.ensure(2) || (tn.guide && (ws.guide_fb.ensure((size_t)job.qi[0].sub_capacity * kSubQueues) ||
+                                                    ws.guide_fb_count.ensure(32) || ws.guide_heads.ensure(32))))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the guide tree's fallback list");
     }
     if (job.elide) {
         if (ws.live_mask.ensure(job.live_words_max + 8) || ws.live_u32.ensure(2 * job.live_words_max + 16) ||
@@ -701,6 +749,7 @@ int render_run(vmx_scene *sc, RenderJob &job, uint32_t samples, vmx_stats *stats
     HIP_TRY(hipEventRecord(ev0, s));
     if ((rc = render_bind(sc, job, samples))) return rc;
     HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
     if (!job.initialised && (rc = render_init_pixels(sc, job))) return rc;
     uint32_t left = samples ? samples : 0xFFFFFFFFu;
     while (job.n_active > 0 && left > 0) {
@@ -763,6 +812,7 @@ int bruteforce_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, 
     if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
     HIP_TRY(hipMemcpyAsync(ws.pixels.active[0].p, ws.order.data(), (size_t)npix * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
     HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 4, s));
     HIP_TRY(hipEventRecord(ev0, s));
     // stack as in the traversal kernels: a few levels per lane in LDS, the rest in the global slab (the whole stack
@@ -876,6 +926,22 @@ int vmx_list_settled_rays(const vmx_scene *csc, uint64_t *rays) {
     if (!sc || !rays) return fail(VMX_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lock(sc->mu);
     *rays = sc->list_settled;
+    return VMX_OK;
+}
+
+int vmx_guide_rays(const vmx_scene *csc, uint64_t *settled, uint64_t *fallback) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !settled || !fallback) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *settled = sc->guide_settled, *fallback = sc->guide_fallback;
+    return VMX_OK;
+}
+
+int vmx_guide_list_entries(const vmx_scene *csc, uint64_t *entries) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !entries) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *entries = sc->guide_entries;
     return VMX_OK;
 }
 

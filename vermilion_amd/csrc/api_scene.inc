@@ -37,6 +37,81 @@ static int upload_records(const HostBvh &b, DevBuf<unsigned char> &geom, DevBuf<
     return VMX_OK;
 }
 
+// the guide's records (guide_walk.h) into an allocation of their own, in the upload_records shape
+static int upload_guide(vmx_scene *sc) {
+    vmx_scene::Guide &g = sc->guide;
+    g.valid = false;
+    if (!g.host) return VMX_OK;
+    const HostBvh &b = *g.host;
+    const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
+    const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
+    if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return VMX_OK;  // (no guide: the scene renders as before)
+    if (g.geom.ensure(inner_bytes + tri_bytes + 64)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the guide tree");
+    HIP_TRY(hipMemset(g.geom.p, 0, inner_bytes + tri_bytes + 64));
+    if (b.inner.size()) HIP_TRY(hipMemcpy(g.geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g.geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
+    g.bytes = b.inner.size() * sizeof(InnerRecord) + tri_bytes;
+    g.tri_off = (uint32_t)inner_bytes, g.root_ref = b.root_ref, g.stack_entries = b.max_depth + 2;
+    g.valid = true;
+    return VMX_OK;
+}
+
+// one host build, at creation and at a REBUILD: the scene's tree and, for a reference-tree scene, its guide
+// (guide_walk.h) — the quality tree of the same inputs, built beside it on a second thread.  A quality tree that cannot
+// be built (too deep, no memory, no thread) leaves the scene without a guide; only the scene's own tree can fail.
+struct HostTrees {
+    HostBvh tree;
+    std::shared_ptr<const HostBvh> guide;
+    float scene_max = 0.f;
+};
+static bool host_build_trees(uint32_t builder, const float *pos, const float *nrm, const float *uv, uint32_t ntris,
+                             uint32_t leaf_size, HostTrees &out, std::string &err) {
+    std::shared_ptr<HostBvh> guide;
+    std::thread guide_build;
+    bool guide_ok = false;
+    struct Joiner {  // (an exception of the build below must not meet a joinable thread)
+        std::thread &t;
+        ~Joiner() { if (t.joinable()) t.join(); }
+    } joiner{guide_build};
+    if (builder == VMX_BVH_REFERENCE) {
+        try {
+            guide = std::make_shared<HostBvh>();
+            guide_build = std::thread([&guide_ok, guide, pos, nrm, uv, ntris, leaf_size] {
+                try {
+                    std::string gerr;
+                    guide_ok = build_bvh_sah(pos, nrm, uv, ntris, leaf_size, *guide, gerr);
+                } catch (...) {
+                    guide_ok = false;
+                }
+            });
+        } catch (...) {
+            guide.reset();
+        }
+    }
+    const bool built = builder == VMX_BVH_SAH ? build_bvh_sah(pos, nrm, uv, ntris, leaf_size, out.tree, err)
+                                              : build_bvh(pos, nrm, uv, ntris, leaf_size, out.tree, err);
+    if (guide_build.joinable()) guide_build.join();
+    out.guide.reset();
+    if (built && guide && guide_ok) {
+        try {
+            out.scene_max = make_guide_records(*guide, out.tree, pos, ntris);
+            out.guide = guide;
+        } catch (...) {
+        }
+    }
+    return built;
+}
+
+// after a host REBUILD (sc->bvh is the new tree, nothing in flight reads the old records): the guide that was built
+// beside it, as a fresh scene would have it, or none.  A REFIT only marks the guide stale.
+static int apply_guide(vmx_scene *sc, const HostTrees &t) {
+    vmx_scene::Guide &g = sc->guide;
+    g.valid = false, g.bytes = 0;
+    g.geom = DevBuf<unsigned char>();
+    g.host = t.guide, g.scene_max = t.scene_max;
+    return upload_guide(sc);
+}
+
 // points the kernels' view of the scene (SceneDev) at its records; sizes what follows the tree's depth
 static void bind_records(vmx_scene *sc) {
     if (sc->device_built) {
@@ -98,6 +173,7 @@ static int scene_upload(vmx_scene *sc) {
     sc->dev.ntris = sc->ntris;
     if (!sc->device_built)
         if (int rc = upload_records(sc->bvh, sc->d_geom, sc->d_attrs)) return rc;
+    if (int rc = upload_guide(sc)) return rc;
     bind_records(sc);
     return VMX_OK;
 }
@@ -149,8 +225,12 @@ int vmx_scene_create_ex(const float *pos, const float *nrm, const float *uv, uin
         built = builder == VMX_BVH_PLOC ? build_bvh_ploc_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err)
                                         : build_bvh_lbvh_device(pos, nrm, uv, ntris, sc->leaf_size, device, sc->lbvh, err);
     } else {
-        built = builder == VMX_BVH_SAH ? build_bvh_sah(pos, nrm, uv, ntris, sc->leaf_size, sc->bvh, err)
-                                       : build_bvh(pos, nrm, uv, ntris, sc->leaf_size, sc->bvh, err);
+        HostTrees t;
+        built = host_build_trees(builder, pos, nrm, uv, ntris, sc->leaf_size, t, err);
+        if (built) {
+            sc->bvh = std::move(t.tree);
+            sc->guide.host = t.guide, sc->guide.scene_max = t.scene_max;
+        }
     }
     if (!built) {
         delete sc;
@@ -273,7 +353,8 @@ int vmx_scene_describe(const vmx_scene *sc, vmx_scene_desc *out) {
     out->stack_entries = sc->dev.stack_entries;
     out->device_bytes = (size_t)sc->n_inner * sizeof(InnerRecord) + (size_t)sc->ntris * sizeof(TriRecord) +
                         (size_t)sc->ntris * sizeof(AttrRecord) + sc->spheres.size() * sizeof(SphereDev) +
-                        (sc->device_built ? sc->lbvh.arena_bytes : 0);  // device-built trees keep their hierarchy arrays
+                        (sc->device_built ? sc->lbvh.arena_bytes : 0) +  // device-built trees keep their hierarchy arrays
+                        (sc->guide.geom.p ? sc->guide.bytes : 0);           // a reference-tree scene's guide (guide_walk.h)
     out->device = sc->device;
     return VMX_OK;
 }

@@ -83,6 +83,7 @@ int update_enqueue(vmx_scene *sc, const float *d_pos, const float *d_nrm, const 
         for (const auto &lv : u.levels)
             LAUNCH_TRY(launch_refit_level(plan + lv.first, lv.second, d_pos, tris, inner, u.root_box.p, s));
         u.refitted = true, u.bounds_stale = true;
+        sc->guide.valid = false;  // the guide's boxes are the old positions': not used from here on (guide_walk.h)
         sc->flat_ready.store(false, std::memory_order_release);
     }
     return sc->upd.done.record(s);
@@ -93,6 +94,7 @@ void rebuilt(vmx_scene *sc) {
     bind_records(sc);  // stack_entries, block; the render workspace's overflow stacks follow in bind_stack, the query
                        // workspace in ensure_query_ws
     sc->upd.plan_ready = false, sc->upd.refitted = false;
+    sc->guide.valid = false;
     sc->flat_topology = !sc->device_built;
     sc->flat_ready.store(!sc->device_built, std::memory_order_release);
 }
@@ -112,8 +114,9 @@ int host_attrs_by_id(vmx_scene *sc, std::vector<float> &nrm, std::vector<float> 
     return VMX_OK;
 }
 
-// host builders: build on the host (into a new HostBvh; the scene is untouched on failure)
-int host_rebuild_tree(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, HostBvh &out) {
+// host builders: build on the host (into new trees — a reference-tree scene's guide beside its tree, as at creation; the
+// scene is untouched on failure)
+int host_rebuild_tree(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, HostTrees &out) {
     std::vector<float> kn, ku;
     if (!nrm || !uv) {
         if (int rc = host_attrs_by_id(sc, kn, ku)) return rc;
@@ -121,9 +124,7 @@ int host_rebuild_tree(vmx_scene *sc, const float *pos, const float *nrm, const f
         if (!uv) uv = ku.data();
     }
     std::string err;
-    const bool ok = sc->builder == VMX_BVH_SAH ? build_bvh_sah(pos, nrm, uv, sc->ntris, sc->leaf_size, out, err)
-                                               : build_bvh(pos, nrm, uv, sc->ntris, sc->leaf_size, out, err);
-    return ok ? VMX_OK : build_error(err);
+    return host_build_trees(sc->builder, pos, nrm, uv, sc->ntris, sc->leaf_size, out, err) ? VMX_OK : build_error(err);
 }
 
 // swaps a host-built tree in: new buffers, uploaded, then the old ones freed.  The caller has synchronised `s` after
@@ -172,7 +173,7 @@ int device_rebuild(vmx_scene *sc, const float *d_pos, const float *d_nrm, const 
 
 // vmx_scene_update after the argument checks, under the scene's lock; `tree`: a host build shared by the replicas of
 // a vmx_multi (host builders with REBUILD), else NULL
-int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, uint32_t flags, const HostBvh *tree) {
+int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, uint32_t flags, const HostTrees *tree) {
     if (int rc = bind_device(sc)) return rc;
     hipStream_t s = sc->stream;
     const size_t n = sc->ntris;
@@ -180,12 +181,13 @@ int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *
     if (rebuild && !sc->device_built) {
         if (int rc = update_wait(sc, s)) return rc;
         HIP_TRY(hipStreamSynchronize(s));
-        HostBvh own;
+        HostTrees own;
         if (!tree) {
             if (int rc = host_rebuild_tree(sc, pos, nrm, uv, own)) return rc;
             tree = &own;
         }
-        if (int rc = host_apply_tree(sc, *tree, s)) return rc;
+        if (int rc = host_apply_tree(sc, tree->tree, s)) return rc;
+        if (int rc = apply_guide(sc, *tree)) return rc;  // (the guide of the new positions, built beside the tree)
         vertex_bounds(sc, pos);
         HIP_TRY(hipStreamSynchronize(s));
         sc->generation++;
@@ -242,8 +244,8 @@ int vmx_multi_update(vmx_multi *m, const float *pos, const float *nrm, const flo
     std::lock_guard<std::mutex> mlock(m->mu);
     vmx_scene *first = m->replica[0];
     if (int rc = update_scene_args(first, pos, ntris)) return rc;
-    HostBvh tree;
-    const HostBvh *shared = nullptr;
+    HostTrees tree;
+    const HostTrees *shared = nullptr;
     if ((flags & VMX_UPDATE_REBUILD) && pos && !first->device_built) {
         // host builders: one host build, uploaded to every replica
         std::lock_guard<std::mutex> lock(first->mu);

@@ -11,6 +11,7 @@
 //   * degenerate partition -> split at the middle index (bvh.cpp:258-260)
 //   * leaf when nPrims <= leafSize (bvh.cpp:219); DFS pre-order, left first
 #include "bvh_build.h"
+#include "guide_walk.h"
 
 #include <algorithm>
 #include <cmath>
@@ -212,6 +213,27 @@ bool check_bvh_input(const float *pos, const float *nrm, uint32_t ntris, uint32_
 }
 bool flatten_bvh(const float *pos, const float *nrm, const float *uv, uint32_t ntris, HostBvh &out, std::string &err) {
     return flatten(pos, nrm, uv, ntris, out, err);
+}
+
+// The guide of a reference-tree scene (guide_walk.h): the quality tree's device records with every child box padded
+// (gw_pad) and the triangle's leaf slot in the REFERENCE tree in TriRecord::pad[0].  The attribute table is the
+// reference tree's; the guide keeps none.
+float make_guide_records(HostBvh &guide, const HostBvh &ref, const float *pos, uint32_t ntris) {
+    float scene_max = 0.f;
+    for (size_t i = 0; i < (size_t)ntris * 9; ++i) scene_max = fmax2(scene_max, std::fabs(pos[i]));
+    scene_max *= kGwOriginReach;  // M of guide_walk.h: how far out a ray may start and still walk the guide
+    for (InnerRecord &r : guide.inner) {
+        for (int a = 0; a < 3; ++a) {
+            const float pl = gw_pad(r.lmin[a], r.lmax[a], scene_max), pr = gw_pad(r.rmin[a], r.rmax[a], scene_max);
+            r.lmin[a] -= pl, r.lmax[a] += pl;
+            r.rmin[a] -= pr, r.rmax[a] += pr;
+        }
+    }
+    std::vector<uint32_t> ref_slot(ntris, 0);
+    for (uint32_t s = 0; s < ntris; ++s) ref_slot[ref.prim_order[s]] = s;
+    for (uint32_t s = 0; s < ntris; ++s) guide.tris[s].pad[0] = ref_slot[guide.prim_order[s]];
+    std::vector<AttrRecord>().swap(guide.attrs);
+    return scene_max;
 }
 
 // ---------------------------------------------------------------------------

@@ -32,6 +32,11 @@ bool build_bvh(const float *pos, const float *nrm, const float *uv, uint32_t ntr
 bool build_bvh_sah(const float *pos, const float *nrm, const float *uv, uint32_t ntris,
                    uint32_t leaf_size, HostBvh &out, std::string &err);
 
+// turns `guide` — build_bvh_sah's tree of the triangles `ref` was built from — into the guide of a reference-tree scene
+// (guide_walk.h): padded child boxes, the reference leaf slot of each triangle in TriRecord::pad[0], no attributes.
+// Returns M, the bound on |origin coordinate| that the pad and the per-ray rule share.
+float make_guide_records(HostBvh &guide, const HostBvh &ref, const float *pos, uint32_t ntris);
+
 // linear BVH built ENTIRELY on the GPU (lbvh_build.hip): Morton sort + Karras hierarchy + bottom-up fit +
 // device-record emission.  The product buffers (`geom` = inner records then triangle records, `attrs`) are
 // device memory handed to the scene; the hierarchy arrays stay in `arena` for lbvh_export_flat.

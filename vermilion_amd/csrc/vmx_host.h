@@ -162,6 +162,11 @@ struct Workspace {
     DevBuf<unsigned char> out_rec;   // k_trace_w<.., SORT>: 32-byte records of the camera rays that still need shading
     DevBuf<unsigned int> out_count;
     size_t out_capacity = 0;         // entries out_rec was sized for
+    // k_trace_w<1, .., GUIDE>: the fallback list of a bounce generation (path ids; [0] of guide_fb_count is its length,
+    // which the second launch reads on the device) and the frame's (settled, fallback) ray counts
+    DevBuf<unsigned int> guide_fb, guide_fb_count, guide_heads;
+    DevBuf<unsigned long long> guide_ctr;
+    uint64_t guide_entries = 0;  // entries of the bounce lists handed to the GUIDE launches of the call in progress (host count)
     PixelBufs pixels;                   // vmx_render's frames (a vmx_progressive handle owns its own); active[0]: BruteForceTracer's pixel order
     DevBuf<unsigned int> next_count;
     DevBuf<DevCounters> counters;
@@ -206,6 +211,20 @@ struct vmx_scene {
     vmx_timings timings{};  // per-kernel durations of the last render on this scene
     uint64_t fused_paths = 0;  // ... and its camera paths that took the fused route (vmx_fused_camera_paths)
     uint64_t list_settled = 0;  // ... and its camera rays that a list claim settled (vmx_list_settled_rays)
+    uint64_t guide_settled = 0, guide_fallback = 0;  // ... and its bounce rays that walked the guide (vmx_guide_rays)
+    uint64_t guide_entries = 0;  // ... and the entries of the lists its GUIDE launches were handed (vmx_guide_list_entries)
+    // the guide of a VMX_BVH_REFERENCE scene (guide_walk.h): the binned-SAH tree of the same triangles, its records in an
+    // allocation of their own (the upload_records shape: inner records, then the triangle records); no attribute table.
+    // `host` is the one host build the replicas of a vmx_multi share.  Stale after any update that moves vertices or
+    // rebuilds: then it is not used (refitting it is a follow-up).
+    struct VMX_OPAQUE Guide {
+        std::shared_ptr<const HostBvh> host;
+        DevBuf<unsigned char> geom;
+        size_t bytes = 0;
+        uint32_t tri_off = 0, root_ref = 0, stack_entries = 0;
+        float scene_max = 0.f;
+        bool valid = false;
+    } guide;
     // device ray queries (vmx_query_device): allocated on the first query, then reused.  `done` is recorded after each
     // query's last kernel and waited on by the next one: one query at a time uses the workspace
     struct QueryWs {
@@ -408,6 +427,9 @@ struct Tuning {
                          // scattered 8-byte hit[pid] store that k_shade<1> then gathers — same shading, every ray a full RayCast
     bool pool;           // A/B library, reserved[0] bit 10: the bounce generations of a pass through k_trace_pool (phase-pure
                          // steps, ray state in LDS; profiles/r04_state_pool.txt) — unsorted passes only
+    bool guide;          // the bounce generations of a render pass walk the scene's guide tree (k_trace_w<1, .., GUIDE>, guide_walk.h)
+                         // and a second launch of today's kernel traces the fallback list: a reference-tree scene with a valid
+                         // guide; not the counting build, the A/B pool or reserved[0] bit 14
 };
 
 constexpr uint32_t kPathsBlock = 256;

@@ -110,6 +110,19 @@ struct WorkDev {
     uint32_t fused;
 };
 
+// the guide of a reference-tree scene as k_trace_w<1, .., GUIDE> reads it (guide_walk.h); base = NULL: no guide, the
+// launch is today's
+struct GuideDev {
+    const void *base;         // the guide's InnerRecord[], then (tri_off bytes on) its TriRecord[]; pad[0] = reference leaf slot
+    uint32_t tri_off, root_ref;
+    float scene_max;          // the pad's and the rule's M: no ray that starts beyond it on an axis walks the guide
+    uint32_t fb_capacity;     // entries fb_ids holds
+    unsigned int *fb_ids;     // fallback list: path ids of the rays the rule did not settle
+    unsigned int *fb_count;   // device scalar: its length
+    unsigned long long *ctr;  // [0] rays settled by the guide, [1] fallback rays
+    DevCounters *overflow;    // the frame's counters: a fallback entry that does not fit is reported (DevCounters::overflow)
+};
+
 // explicit ray batch of k_query (vmx_query.inc): device pointers, any output may be NULL
 struct QueryDev {
     const float *o, *d;     // [n*3] origins / directions
@@ -216,8 +229,10 @@ int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, u
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
                            unsigned long long *mask, unsigned int *cnt, void *stream);
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
-                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream);
-int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks);
+                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide = nullptr);
+// (guide: the GUIDE form of the bounce kernel, which launch_trace_q launches when it is handed a guide)
+int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks,
+                                bool guide = false);
 // ... and the wide shading kernel: RayCast tail + Radiance step + id compaction
 int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
                  IdQueue qout, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream);

@@ -37,6 +37,7 @@
 
 #include "vmx_kernels.h"
 #include "pixel_claim.h"
+#include "guide_walk.h"
 #include <type_traits>
 
 #ifndef VMX_CAM_BATCH
@@ -2399,10 +2400,19 @@ __device__ __forceinline__ uint32_t uniform_descent(int &sp, uint32_t &cur, floa
 // others get a 32-byte record (direction, flag word | t, leaf slot, position) appended to a dense list — the wave
 // reserves 256 entries at a time with one atomic, fills them to the last one, and pads the tail of its last chunk with
 // position = ~0 when it ends — which k_shade reads front to back.
+// GUIDE (SRC 1, a reference-tree scene with a valid guide; guide_walk.h): the rays walk the GUIDE's records (gd.base,
+// gd.tri_off, gd.root_ref) with the prune on near > cut = best (1 + kGwKappa) and keep `second`.  A finished ray is held
+// until the next refill, as SORT holds it; there the rule runs for the wave's finished lanes together (one 48-byte record
+// fetch per ray): a settled ray takes the winner's REFERENCE slot from its record and goes where it goes today (hit_out,
+// or sort_finished's decision and record); a fallback ray's path id is appended to gd.fb_ids — one atomic per wave and
+// refill that has any, the count stays on the device — and the existing instantiation traces that list over the
+// reference tree in a second launch.  Rays with non-finite inputs or an origin beyond the scene's |coordinates| are
+// appended at refill without a walk, so the NaN-exact box form never meets the guide.
 constexpr uint32_t kOutChunk = 256;
-template <int SRC, bool LIVE = false, bool SORT = false>
+template <int SRC, bool LIVE = false, bool SORT = false, bool GUIDE = false>
 __global__ void __launch_bounds__(256, VMX_TRACE_WAVES_PER_SIMD) __attribute__((amdgpu_num_sgpr(VMX_TRACE_SGPRS)))
-k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
+k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa, GuideDev gd) {
+    static_assert(!GUIDE || (SRC == 1 && !LIVE), "the guide is for bounce rays");
     extern __shared__ uint2 lds_stack[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const int lds_entries = (int)wk.lds_entries;
@@ -2415,14 +2425,19 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
     uint2 *stk = lds_stack + (size_t)wave * (lds_entries + 1) * 64 + lane;
     uint2 *ovf = (uint2 *)wk.overflow_stack +
                  ((size_t)(blockIdx.x * (blockDim.x >> 6) + wave) * wk.overflow_entries) * 64 + lane;
-    const float4 *__restrict__ inner = SRC == 0 ? (const float4 *)wk.cam_inner : (const float4 *)sc.inner;
+    const float4 *__restrict__ inner = SRC == 0 ? (const float4 *)wk.cam_inner : (GUIDE ? (const float4 *)gd.base : (const float4 *)sc.inner);
     const float4 *__restrict__ tris = SRC == 0 ? (const float4 *)wk.cam_tris : (const float4 *)sc.tris;
     float2 *__restrict__ hit_out = (float2 *)pa.hit;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t kReserve = wk.reserve;
     const uint32_t nsrc = wk.nsrc, refill_min = wk.refill_min;
     const uint32_t band_slots = wk.band_slots, band_items = wk.band_items;
-    const uint32_t root_ref = sc.root_ref;
+    const uint32_t root_ref = GUIDE ? gd.root_ref : sc.root_ref;
+    const uint32_t tri_off = GUIDE ? gd.tri_off : sc.tri_off;
+    // GUIDE: the prune bound and the smallest accepted distance of any triangle but the nearest (guide_walk.h); `slot` is
+    // the winner's slot in the GUIDE until the rule has run
+    float cut = 0.f, second = 0.f;
+    uint32_t n_settled = 0, n_fallback = 0;  // (wave-uniform)
 
     uint32_t src = blockIdx.x % nsrc, res_lo = 0, res_hi = 0, tried = 0;
     bool exhausted = false;
@@ -2482,6 +2497,47 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
         }
         rflags &= 0x7FFFFFFFu;
     };
+    // GUIDE: the path ids of the lanes with `fb` go to the fallback list (wave-uniform code)
+    auto fallback_append = [&](bool fb) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(fb);
+        if (m == 0) return;
+        const uint32_t n = (uint32_t)__popcll(m);
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(gd.fb_count, n);
+        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t at = base + (uint32_t)__popcll(m & lt_mask);
+        // (the list holds every path id of the pass, and a path is appended once per launch: `at` stays below its end; an
+        // entry that would not is reported instead of written, as sort_finished reports a record)
+        if (fb && at < gd.fb_capacity) gd.fb_ids[at] = pid;
+        else if (fb) atomicAdd(&gd.overflow->overflow, 1ull);
+        n_fallback += n;
+    };
+    // GUIDE: the rule (gw_settle) for the finished rays the wave's lanes hold, before sort_finished / the hit records
+    auto guide_finished = [&]() {
+        const bool fin = (rflags >> 31) != 0;
+        bool fb = false;
+        if (fin) {
+            const bool have = slot >= 0;
+            float r[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int ref_slot = -1;
+            if (have) {
+                const float4 *rec = (const float4 *)((const char *)inner + (tri_off + (uint32_t)slot * 48u));
+                const float4 a = rec[0], b = rec[1], c = rec[2];
+                r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w, r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w, r[8] = c.x;
+                ref_slot = __float_as_int(c.z);  // TriRecord::pad[0]: the triangle's leaf slot in the reference tree
+            }
+            const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz}, inv[3] = {ix, iy, iz};
+            if (gw_settle(have, r, best, second, o, d, inv, gd.scene_max)) slot = ref_slot;
+            else fb = true;
+        }
+        n_settled += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(fin && !fb));
+        fallback_append(fb);
+        if (fb) rflags &= 0x7FFFFFFFu;  // the second launch settles it
+        if (!SORT) {
+            if (fin && !fb) hit_out[pid] = make_float2(best, __int_as_float(slot));
+            rflags &= 0x7FFFFFFFu;
+        }
+    };
 
     // One traversal step of every active lane.  The NaN-exact box form runs only while one of the
     // wave's rays needs it.
@@ -2510,20 +2566,23 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
             // selects — was measured in the kernel as well: its 4 KB of staging per wave cost waves or LDS stack levels,
             // 50.5 ms for the bounce stage against 42.9; profiles/r03_lds_transpose.txt, tools/ta_probe.hip)
             quad_fetch_record((const char *)inner,
-                              cur == kIdle ? 0u : (leaf ? sc.tri_off + (cur & kLeafStartMask) * 48u : (cur << 6)),
+                              cur == kIdle ? 0u : (leaf ? tri_off + (cur & kLeafStartMask) * 48u : (cur << 6)),
                               lane, q0, q1, q2, q3);
             if (cur != kIdle) {
                 if (!leaf) {
                     float tn0, tf0, tn1, tf1;
                     child_boxes<EXACT>(q0, q1, q2, ox, oy, oz, ix, iy, iz, tn0, tf0, tn1, tf1);
-                    cur = choose_child(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, push);
+                    cur = choose_child(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), GUIDE ? cut : best, push);
                 } else {
                     // one triangle of the leaf (triangle.cpp:4-54)
                     float dist;
                     const bool hit = tri_test(q0, q1, q2.x, ox, oy, oz, dx, dy, dz, dist);
                     if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
+                        if (GUIDE) second = best, cut = dist * kGwCut;
                         best = dist;
                         slot = (int)(cur & kLeafStartMask);
+                    } else if (GUIDE && hit) {
+                        second = fminf(second, dist);
                     }
                     cur = leaf_advance(cur);
                 }
@@ -2578,9 +2637,9 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
             }
         }
         if (cur == kPop) {
-            cur = pop_to_next(stk, ovf, lds_entries, sp, best);
+            cur = pop_to_next(stk, ovf, lds_entries, sp, GUIDE ? cut : best);
             if (cur == kBottom) {
-                if (SORT) rflags |= 0x80000000u;  // settled at the next refill (the lane keeps t, slot, direction until then)
+                if (SORT || GUIDE) rflags |= 0x80000000u;  // settled at the next refill (the lane keeps t, slot, direction until then)
                 else hit_out[pid] = make_float2(best, __int_as_float(slot));
                 cur = kIdle;
             }
@@ -2591,6 +2650,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
         // ---- refill idle lanes -------------------------------------------------------
         const unsigned long long idle = __builtin_amdgcn_ballot_w64(cur == kIdle);
         if (idle != 0 && !exhausted && ((uint32_t)__popcll(idle) >= refill_min || idle == ~0ull)) {
+            if (GUIDE) guide_finished();
             if (SORT) sort_finished();
             for (;;) {
                 if (res_lo == res_hi) {
@@ -2626,6 +2686,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                 const uint32_t item = res_lo + rank;
                 res_lo = __builtin_amdgcn_readfirstlane(res_lo + min((uint32_t)__popcll(want), avail));
                 bool listed = false;  // this lane's ray was settled by its pixel's list
+                bool unwalked = false;  // GUIDE: this lane's ray goes to the fallback list as it is
                 if (take) {
                     bool valid = true;
                     uint32_t claim = kClaimNone;  // (camera rays: the pixel's claim, pixel_claim.h)
@@ -2693,8 +2754,14 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
                     if (valid) {
                         ray_start(dx, dy, dz, root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
                         exact = !(finite3(ix, iy, iz) && finite3(ox, oy, oz));
+                        if (GUIDE) {
+                            cut = best * kGwCut, second = 3.0e38f;
+                            exact = false;
+                            if (!gw_ray_ok(ox, oy, oz, dx, dy, dz, ix, iy, iz, gd.scene_max)) cur = kIdle, unwalked = true;
+                        }
                     }
                 }
+                if (GUIDE) fallback_append(unwalked);
                 if (SRC == 0 && !LIVE && wk.claim_lists) n_listed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(listed));
                 if (SRC == 0 && !LIVE && SORT && wk.claims) {
                     if (__builtin_amdgcn_ballot_w64((rflags >> 31) != 0) != 0) sort_finished();
@@ -2718,7 +2785,7 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
             const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)oct, (int)__ffsll((long long)active) - 1);
             wave_octant = __builtin_amdgcn_ballot_w64(cur != kIdle && oct != o0) == 0 ? o0 : 8u;
         }
-        if (__builtin_amdgcn_ballot_w64(exact && cur != kIdle) != 0) {
+        if (!GUIDE && __builtin_amdgcn_ballot_w64(exact && cur != kIdle) != 0) {
 #pragma unroll 1
             for (int act = 0; act < 8; ++act) VMX_PROF_STEP(std::true_type{}, std::false_type{});
         } else if (SRC == 0 && wave_octant < 8) {
@@ -2768,6 +2835,13 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa) {
 #endif
     }
     if (SRC == 0 && !LIVE && lane == 0 && n_listed) atomicAdd(&wk.list_ctr->listed, (unsigned long long)n_listed);
+    if (GUIDE) {
+        guide_finished();
+        if (lane == 0) {
+            if (n_settled) atomicAdd(&gd.ctr[0], (unsigned long long)n_settled);
+            if (n_fallback) atomicAdd(&gd.ctr[1], (unsigned long long)n_fallback);
+        }
+    }
     if (SORT) {
         sort_finished();
         float4 *__restrict__ rec = (float4 *)wk.out_rec;
@@ -3788,10 +3862,14 @@ int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk
 // ELIDE_DEAD list form of the camera kernel), with counters the first form k_trace_q (same tests per ray).
 // launch_trace_q launches what these name and query_trace_q_blocks_per_cu sizes the persistent grid and the record-list
 // padding from its occupancy: the figure is by construction that of the kernel launched.
-using TraceWKernel = void (*)(SceneDev, FrameDev, WorkDev, PathArrays);
+using TraceWKernel = void (*)(SceneDev, FrameDev, WorkDev, PathArrays, GuideDev);
 using TraceQKernel = void (*)(SceneDev, FrameDev, WorkDev, PixelStateDev, PathArrays, DevCounters *);
-static TraceWKernel trace_w_kernel(bool from_queue, bool sorted, bool live) {
+static TraceWKernel trace_w_kernel(bool from_queue, bool sorted, bool live, bool guide) {
     if (from_queue) {
+        if (guide) {  // bounce rays over the scene's guide tree (guide_walk.h)
+            if (sorted) return k_trace_w<1, false, true, true>;
+            return k_trace_w<1, false, false, true>;
+        }
         if (sorted) return k_trace_w<1, false, true>;
         return k_trace_w<1>;
     }
@@ -3808,18 +3886,22 @@ static TraceQKernel trace_q_kernel(bool from_queue) {
 }
 
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
-                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream) {
+                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide) {
     hipStream_t s = (hipStream_t)stream;
     dim3 g(cfg.grid), b(cfg.block);
+    const bool guided = guide && guide->base && from_queue && !count;
+    GuideDev gd{};
+    if (guided) gd = *guide;
     if (count) hipLaunchKernelGGL(trace_q_kernel(from_queue), g, b, cfg.lds_bytes, s, sc, fr, wk, px, pa, counters);
-    else hipLaunchKernelGGL(trace_w_kernel(from_queue, wk.out_rec != nullptr, wk.live_ids != nullptr), g, b, cfg.lds_bytes, s, sc, fr, wk, pa);
+    else hipLaunchKernelGGL(trace_w_kernel(from_queue, wk.out_rec != nullptr, wk.live_ids != nullptr, guided), g, b, cfg.lds_bytes, s, sc, fr, wk, pa, gd);
     return launch_status();
 }
 
-int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks) {
+int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks,
+                                bool guide) {
     int a = 0;
     const hipError_t e = count ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, trace_q_kernel(from_queue), (int)block, lds_bytes)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, trace_w_kernel(from_queue, sorted, live), (int)block, lds_bytes);
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, trace_w_kernel(from_queue, sorted, live, guide && from_queue), (int)block, lds_bytes);
     if (blocks) *blocks = a;
     return (int)e;
 }

@@ -92,7 +92,7 @@ def make_opts(seed=1, early_stop=True, sampling=L.VMX_SAMPLING_PARITY, rank=0, w
     o.rank, o.world, o.stripe_rows = int(rank), int(world), int(stripe_rows)
     o.samples_per_batch = int(samples_per_batch)
     o.collect_counters = 1 if collect_counters else 0
-    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims, | 0x1000 claimed pixels are not fused into the shading kernel, | 0x2000 no list claims
+    o.reserved[0] = int(pipeline)      # 0 default routing, 1 fused kernel for every pass, 4 split wavefront for every pass; 2/3 first-generation kernels (A/B library only); | 0x100 one-phase shading, | 0x200 two-phase shading (k_shade_ends) instead of sorted rays, | 0x800 no per-pixel claims, | 0x1000 claimed pixels are not fused into the shading kernel, | 0x2000 no list claims, | 0x4000 no guide tree for the bounce rays
     o.reserved[1] = int(max_paths)     # paths in flight per pass (0 -> 16M)
     o.reserved[2] = int(tail_threshold)
     o.reserved[3] = int(refill_min)    # k_paths: refill when this many lanes idle (0 -> 16)
@@ -599,6 +599,18 @@ class Scene:
         """vmx_list_settled_rays: the camera rays of the last render on this scene that a list claim settled"""
         n = C.c_uint64(0)
         self._check(self._lib.vmx_list_settled_rays(self._h, C.byref(n)))
+        return int(n.value)
+
+    def guide_rays(self):
+        """vmx_guide_rays: (settled, fallback) bounce rays of the last render on this scene that walked its guide tree"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vmx_guide_rays(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def guide_list_entries(self):
+        """vmx_guide_list_entries: entries of the bounce lists the last render handed to the guide form of the trace kernel"""
+        n = C.c_uint64(0)
+        self._check(self._lib.vmx_guide_list_entries(self._h, C.byref(n)))
         return int(n.value)
 
     def render(self, cam, opts):
