@@ -412,6 +412,21 @@ int vmx_guide_rays(const vmx_scene *scene, uint64_t *settled, uint64_t *fallback
 /* Debug entry: the entries of the bounce-generation lists that the last render call on this scene handed to the
  * guide form of the traversal kernel, counted on the host: settled + fallback of vmx_guide_rays equals it. */
 int vmx_guide_list_entries(const vmx_scene *scene, uint64_t *entries);
+/* Debug entry: the guide form of the bounce traversal kernel on n explicit rays (host buffers), so that a test can hold
+ * the device's guide walk against the host program of guide_walk.h ray by ray.  The rays become path state and one id
+ * list as vmx_radiance forms them; one launch walks the guide as a render's guided bounce generation does (same stack
+ * binding, same lists; opts' tuning words act as in a render).  flags bit 0: the form that hands every ray on as a dense
+ * record (what the default frame's bounce generations run) instead of the form that writes a hit record per path; bit 1:
+ * the render's second launch follows, the unchanged kernel over the fallback list, so every ray has an answer.
+ * grid_blocks caps the blocks of the guided launch (0: what a render launches), so that few rays still pass many refills.
+ * settled[i]: 1 if the guided launch settled ray i, 0 if it went to the fallback list; slot[i]: the leaf slot in the
+ * scene's tree (vmx_scene_bvh's prim_order index), 0xFFFFFFFF for no hit; t[i]: the kernel's t.  Without bit 1 a fallback
+ * ray has slot 0xFFFFFFFF and t 0.  The entry itself checks that every ray was settled or listed, never both, and listed
+ * and answered at most once: a violation is VMX_ERR_HIP with the counts in the message.  VMX_ERR_INVALID: a NULL
+ * argument, an unknown flag, opts->collect_counters, a scene without a valid guide (see vmx_guide_rays).  n = 0 does
+ * nothing.  Afterwards vmx_guide_rays reports this call's counts and vmx_guide_list_entries n. */
+int vmx_guide_trace(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                    uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

@@ -3,7 +3,8 @@
 //   guide_walk_test IN OUT
 // IN : uint32 ntris, n_nodes, nrays; float pos[ntris*9]; the reference tree's flat layout (uint32 start, nprims,
 //      right_offset [n_nodes]; float bbox[n_nodes*6]; uint32 prim_order[ntris]); nrays x (float o[3], float d[3])
-// OUT: uint64 guide visits (inner, triangle) at kappa = 2^-10, 2^-8, 2^-6 over the rays that walk [6]; then per ray
+// OUT: uint64 guide visits (inner, triangle) at kappa = 2^-10, 2^-8, 2^-6 over the rays that walk [6]; uint64 depth of
+//      the guide's and of the reference tree's deepest node (the root is 0) [2]; then per ray
 //      uint32 verdict (GwVerdict), uint32 reference leaf slot of the winner (0xFFFFFFFF: none), float best,
 //      uint32 guide inner visits, guide triangle tests, reference inner visits, reference triangle tests
 // tests/guide_spec.py builds and runs it; the oracle judges what it settles.
@@ -111,7 +112,9 @@ int main(int argc, char **argv) {
     }
     f = std::fopen(argv[2], "wb");
     if (!f) return 2;
+    const uint64_t depths[2] = {guide.max_depth, ref.max_depth};
     std::fwrite(visits, 8, 6, f);
+    std::fwrite(depths, 8, 2, f);
     std::fwrite(out.data(), 4, out.size(), f);
     std::fclose(f);
     return 0;

@@ -1,6 +1,7 @@
-"""Shared by test_guide_walk.py (CPU): the stand-alone host program of vermilion_amd/csrc/guide_walk.h
-(tests/cpp/guide_walk_test.cpp), built once per session as claim_list_spec.py builds its own, the bounce rays the tests
-feed it, and the oracle's verdict on what the per-ray rule settles."""
+"""Shared by test_guide_walk.py (CPU) and test_gpu_guide_rays.py (the device's walk, ray by ray): the stand-alone host
+program of vermilion_amd/csrc/guide_walk.h (tests/cpp/guide_walk_test.cpp), built once per session as claim_list_spec.py
+builds its own, the bounce rays and the adversarial scenes both tests feed it, and the oracle's verdict on what the
+per-ray rule settles."""
 import os
 import shutil
 import subprocess
@@ -34,8 +35,9 @@ def host_program(sanitize=False):
 
 def host_guide(pos, tree, o, d, sanitize=False):
     """Walk and rule for the rays (o, d) [n, 3] over the guide of the triangles pos, beside the reference tree `tree`.
-    Returns a dict: verdict, slot (reference leaf slot of the winner, NONE: no hit), t, visits on both trees per ray, and
-    kappa: the guide's (inner, triangle) visits per walking ray at kappa = 2^-10, 2^-8, 2^-6."""
+    Returns a dict: verdict, slot (reference leaf slot of the winner, NONE: no hit), t, visits on both trees per ray,
+    kappa: the guide's (inner, triangle) visits per walking ray at kappa = 2^-10, 2^-8, 2^-6, and guide_depth / ref_depth:
+    the depth of the deepest node of either tree (the root is 0), as the builders count it."""
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
     rays = np.ascontiguousarray(np.concatenate([np.asarray(o, np.float32).reshape(-1, 3), np.asarray(d, np.float32).reshape(-1, 3)], axis=1))
     n = rays.shape[0]
@@ -54,12 +56,13 @@ def host_guide(pos, tree, o, d, sanitize=False):
         raw = np.fromfile(fout, np.uint8)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    visits = raw[:48].view(np.uint64).astype(np.float64)
-    rec = raw[48:].view(np.uint32).reshape(n, 7)
+    head = raw[:64].view(np.uint64)
+    visits = head[:6].astype(np.float64)
+    rec = raw[64:].view(np.uint32).reshape(n, 7)
     walking = max(int(np.sum(rec[:, 0] != INPUT)), 1)
     return {"verdict": rec[:, 0].copy(), "slot": rec[:, 1].copy(), "t": rec[:, 2].copy().view(np.float32),
             "guide_inner": rec[:, 3].copy(), "guide_tris": rec[:, 4].copy(), "ref_inner": rec[:, 5].copy(), "ref_tris": rec[:, 6].copy(),
-            "kappa": (visits / walking).reshape(3, 2)}
+            "kappa": (visits / walking).reshape(3, 2), "guide_depth": int(head[6]), "ref_depth": int(head[7])}
 
 
 def verdict(osc, tree, o, d, res):
@@ -124,3 +127,116 @@ def bounce_rays(osc, cam, seed, kind):
         nd = u * (np.cos(r1) * r2s)[:, None] + v * (np.sin(r1) * r2s)[:, None] + w * np.sqrt(f32(1) - r2)[:, None]
         nd = (nd / np.linalg.norm(nd, axis=1, keepdims=True)).astype(f32)
     return start, nd
+
+
+def flat_normals(pos):
+    """the face normal of every triangle at its three vertices [n, 9] (a zero-area triangle: +y)"""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
+    e1, e2 = pos[:, 3:6] - pos[:, 0:3], pos[:, 6:9] - pos[:, 0:3]
+    nr = np.cross(e1, e2)
+    ln = np.linalg.norm(nr, axis=1, keepdims=True)
+    nr = np.where(ln > 0, nr / np.maximum(ln, 1e-30), np.float32([0, 1, 0])).astype(np.float32)
+    return np.repeat(nr[:, None, :], 3, axis=1).reshape(-1, 9)
+
+
+def _dirs(rng, n):
+    v = rng.normal(size=(n, 3))
+    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+
+
+def _towards(rng, o, target, spread, n):
+    """n rays from o (one origin or [n, 3]) towards points within `spread` of target"""
+    o = np.broadcast_to(np.asarray(o, np.float64), (n, 3))
+    p = np.asarray(target, np.float64) + rng.uniform(-spread, spread, (n, 3))
+    v = p - o
+    return o.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+
+
+ADVERSARIAL_SEED = 17
+
+
+def adversarial_cases(seed=ADVERSARIAL_SEED):
+    """Yields (kind, pos, o, d): the constructions of tests/test_claim_lists.py (its _tri and fan_scene, imported; the
+    coplanar pair, the T-junction and the two planes a few floats apart built as it builds them) under free origins, and
+    the cases a free origin adds: rays that start on a triangle or on a shared edge, grazing rays, a zero direction
+    component, origins outside the scene's bounds.  One seeded generator draws everything, in this order, so the host
+    program and the device see the same rays.  "close planes" comes three times (1, 4 and 64 floats apart), "sliver fan in
+    a coordinate plane" eight times."""
+    from test_claim_lists import _tri, fan_scene
+    rng = np.random.default_rng(seed)
+    r, u, f = np.array([1.0, 0.2, 0.1]), np.array([-0.1, 1.0, 0.3]), np.array([0.2, -0.3, 1.0])
+    r, u, f = r / np.linalg.norm(r), u / np.linalg.norm(u), f / np.linalg.norm(f)
+    # the shared edge of a coplanar pair, rays aimed at and around the edge
+    c = np.array([3.0, 2.0, 51.0])
+    a, b = c - 40 * u, c + 40 * u
+    pair = np.concatenate([_tri(a, b, c - 60 * r), _tri(b, a, c + 60 * r)])
+    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 0.01, 4000)
+    o2, d2 = _towards(rng, (3.0, 2.0, 1.0), c, 30.0, 2000)
+    yield "coplanar pair", pair, np.concatenate([o, o2]), np.concatenate([d, d2])
+    # ... and rays that hit the edge itself: points of the edge from the float vertices, t near 50
+    k = rng.uniform(-0.9, 0.9, (2000, 1))
+    edge = (np.float32(c) + k * np.float32(40 * u)).astype(np.float64)
+    o = np.broadcast_to(np.array([3.0, 2.0, 1.0]), edge.shape)
+    v = edge - o
+    yield "coplanar pair, edge points", pair, o.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+    # a T-junction
+    a, b = c - 50 * r, c + 50 * r
+    tj = np.concatenate([_tri(a, b, c - 60 * u), _tri(a, c, c + 60 * u), _tri(c, b, c + 60 * u)])
+    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 0.02, 3000)
+    o2, d2 = _towards(rng, (3.0, 2.0, 1.0), c, 30.0, 1000)
+    yield "T-junction", tj, np.concatenate([o, o2]), np.concatenate([d, d2])
+    # two parallel planes 1, 4 and 64 floats apart: every ray that hits both is a tie within 2^-16
+    for steps in (1, 4, 64):
+        big = _tri(c - 25 * r - 25 * u, c + 50 * r - 25 * u, c - 25 * r + 50 * u).astype(np.float32)
+        other = (big.view(np.int32) + np.int32(steps) * np.sign(big).astype(np.int32)).view(np.float32)
+        o, d = _towards(rng, (3.0, 2.0, 1.0), c, 8.0, 2000)
+        yield "close planes", np.concatenate([big, other]).astype(np.float64), o, d
+    # sliver fans in a coordinate plane, coordinates of magnitude 3, 1000 and 4096, every plane
+    for width, axis, x0 in ((0.1, 1, 0.0), (0.02, 1, 0.0), (0.5, 1, 0.0), (0.1, 0, 0.0), (0.1, 2, 0.0), (0.1, 1, 1000.0),
+                            (0.1, 1, -4096.0), (0.5, 2, 1000.0)):
+        eye = np.array([x0 + 3.0, 2.0, 1.0]) + rng.uniform(-1, 1, 3)
+        dd = np.array([0.5, 0.6, 0.62])
+        dd /= np.linalg.norm(dd)
+        fan = fan_scene(eye, dd, 100.0, width, 141.0, axis)
+        hitp = eye + 100.0 * dd
+        o, d = _towards(rng, eye, hitp, 4 * width, 3000)
+        o2, d2 = _towards(rng, eye, hitp, 150.0, 1000)
+        yield "sliver fan in a coordinate plane", fan, np.concatenate([o, o2]), np.concatenate([d, d2])
+
+    # ---- free origins
+    # rays that start ON a triangle or on the shared edge of the pair (t near 0), into the half space of a second wall
+    wall = _tri(c + 30 * f - 200 * r - 200 * u, c + 30 * f + 400 * r - 200 * u, c + 30 * f - 200 * r + 400 * u)
+    room = np.concatenate([pair, wall])
+    k = rng.uniform(-0.9, 0.9, (1500, 1))
+    on_edge = (np.float32(c) + k * np.float32(40 * u)).astype(np.float32)
+    on_face = (np.float32(c) + k * np.float32(30 * u) + rng.uniform(-20, 20, (1500, 1)) * np.float32(r)).astype(np.float32)
+    o = np.concatenate([on_edge, on_face])
+    yield "origins on a triangle", room, o, _dirs(rng, len(o))
+    # grazing rays: within 1e-4 of the plane of the pair, from beside it
+    side = c - 70 * r + rng.uniform(-1e-4, 1e-4, (3000, 1)) * np.cross(r, u)
+    tgt = c + 70 * r + rng.uniform(-30, 30, (3000, 1)) * u + rng.uniform(-1e-4, 1e-4, (3000, 1)) * np.cross(r, u)
+    v = tgt - side
+    yield "grazing rays", room, side.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+    # a direction with a zero component must fall back (its reciprocal is infinite)
+    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 20.0, 600)
+    d = d.copy()
+    d[:200, 0], d[200:400, 1], d[400:, 2] = 0.0, 0.0, -0.0
+    yield "zero direction component", room, o, d
+    # origins outside the scene's bounds: beyond M = four times the largest |coordinate| (about 450 here) the rule falls
+    # back; inside it, it may settle
+    o, d = _towards(rng, (9000.0, -7000.0, 8000.0), c, 30.0, 1000)
+    yield "origins outside the bounds", room, o, d
+    o, d = _towards(rng, (-900.0, 700.0, -800.0), c, 30.0, 1000)  # outside the vertex box, within M
+    yield "origins outside the vertex box", room, o, d
+    # a tie across subtrees: a patch of 16 small triangles in z = 100 in front of two large ones in z = 100.005.  SAH
+    # parts the patch from the large pair at the root.  From z = -390 (inside M = 400) the patch is hit at t = 490 and the
+    # large pair 0.005 farther: beyond the pad of the pair's box (0.0023), so its node's near exceeds best, and within the
+    # tie band 2^-16 t = 0.0075.  The pair's node waits on the stack while the patch is hit: only a pop that prunes on
+    # cut, not on best, still visits it and sees the tie.  (Drawn last, so the cases above keep their rays.)
+    xs, ys = np.linspace(-10.0, 10.0, 3), np.linspace(-10.0, 10.0, 5)
+    patch = [_tri((xs[i], ys[j], 100.0), (xs[i + 1], ys[j], 100.0), (xs[i + 1], ys[j + 1], 100.0)) for i in range(2) for j in range(4)]
+    patch += [_tri((xs[i], ys[j], 100.0), (xs[i + 1], ys[j + 1], 100.0), (xs[i], ys[j + 1], 100.0)) for i in range(2) for j in range(4)]
+    far = [_tri((-100.0, -100.0, 100.005), (100.0, -100.0, 100.005), (100.0, 100.0, 100.005)),
+           _tri((-100.0, -100.0, 100.005), (100.0, 100.0, 100.005), (-100.0, 100.0, 100.005))]
+    o, d = _towards(rng, (0.5, -0.7, -390.0), (0.0, 0.0, 100.0), 12.0, 2000)
+    yield "tie across subtrees", np.concatenate(patch + far), o, d

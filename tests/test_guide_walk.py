@@ -18,15 +18,6 @@ import guide_spec as G
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _normals(pos):
-    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
-    e1, e2 = pos[:, 3:6] - pos[:, 0:3], pos[:, 6:9] - pos[:, 0:3]
-    nr = np.cross(e1, e2)
-    ln = np.linalg.norm(nr, axis=1, keepdims=True)
-    nr = np.where(ln > 0, nr / np.maximum(ln, 1e-30), np.float32([0, 1, 0])).astype(np.float32)
-    return np.repeat(nr[:, None, :], 3, axis=1).reshape(-1, 9)
-
-
 def _run(name, osc, tree, pos, o, d, sanitize=False):
     res = G.host_guide(pos, tree, o, d, sanitize=sanitize)
     bad, hits, misses = G.verdict(osc, tree, o, d, res)
@@ -91,108 +82,30 @@ def test_soup_settles_no_duplicated_triangle():
 def _scene(pos):
     import oracle_lib as O
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
-    osc = O.OracleScene(pos, _normals(pos), None)
+    osc = O.OracleScene(pos, G.flat_normals(pos), None)
     return pos, osc, osc.bvh()
 
 
-def _dirs(rng, n):
-    v = rng.normal(size=(n, 3))
-    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
-
-
-def _towards(rng, o, target, spread, n):
-    """n rays from o (one origin or [n, 3]) towards points within `spread` of target"""
-    o = np.broadcast_to(np.asarray(o, np.float64), (n, 3))
-    p = np.asarray(target, np.float64) + rng.uniform(-spread, spread, (n, 3))
-    v = p - o
-    return o.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
-
-
 def test_adversarial_scenes():
-    """The constructions of tests/test_claim_lists.py (its _tri and fan_scene, imported; the coplanar pair, the T-junction
-    and the two planes a few floats apart built as it builds them) under free origins, and the cases a free origin adds:
-    rays that start on a triangle or on a shared edge, grazing rays, a zero direction component, origins outside the
-    scene's bounds."""
-    from test_claim_lists import _tri, fan_scene
-    rng = np.random.default_rng(17)
+    """The scenes and rays of guide_spec.adversarial_cases (one seeded generator, shared with the device's test): the
+    constructions of tests/test_claim_lists.py under free origins, and the cases a free origin adds: rays that start on a
+    triangle or on a shared edge, grazing rays, a zero direction component, origins outside the scene's bounds."""
     settled, rays = {}, {}
-
-    def run(kind, pos, o, d):
+    for kind, pos, o, d in G.adversarial_cases():
         pos, osc, tree = _scene(pos)
         bad, hits, misses, share, res, tri = _run(kind, osc, tree, pos, o, d)
         assert bad == 0, (kind, bad)
         settled[kind] = settled.get(kind, 0) + hits
         rays[kind] = rays.get(kind, 0) + int(np.sum(tri >= 0))
-        return res, tri
-
-    r, u, f = np.array([1.0, 0.2, 0.1]), np.array([-0.1, 1.0, 0.3]), np.array([0.2, -0.3, 1.0])
-    r, u, f = r / np.linalg.norm(r), u / np.linalg.norm(u), f / np.linalg.norm(f)
-    # the shared edge of a coplanar pair, rays aimed at and around the edge
-    c = np.array([3.0, 2.0, 51.0])
-    a, b = c - 40 * u, c + 40 * u
-    pair = np.concatenate([_tri(a, b, c - 60 * r), _tri(b, a, c + 60 * r)])
-    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 0.01, 4000)
-    o2, d2 = _towards(rng, (3.0, 2.0, 1.0), c, 30.0, 2000)
-    run("coplanar pair", pair, np.concatenate([o, o2]), np.concatenate([d, d2]))
-    # ... and rays that hit the edge itself: points of the edge from the float vertices, t near 50
-    k = rng.uniform(-0.9, 0.9, (2000, 1))
-    edge = (np.float32(c) + k * np.float32(40 * u)).astype(np.float64)
-    o = np.broadcast_to(np.array([3.0, 2.0, 1.0]), edge.shape)
-    v = edge - o
-    run("coplanar pair, edge points", pair, o.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32))
-    # a T-junction
-    a, b = c - 50 * r, c + 50 * r
-    tj = np.concatenate([_tri(a, b, c - 60 * u), _tri(a, c, c + 60 * u), _tri(c, b, c + 60 * u)])
-    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 0.02, 3000)
-    o2, d2 = _towards(rng, (3.0, 2.0, 1.0), c, 30.0, 1000)
-    run("T-junction", tj, np.concatenate([o, o2]), np.concatenate([d, d2]))
-    # two parallel planes 1, 4 and 64 floats apart: every ray that hits both is a tie within 2^-16
-    for steps in (1, 4, 64):
-        big = _tri(c - 25 * r - 25 * u, c + 50 * r - 25 * u, c - 25 * r + 50 * u).astype(np.float32)
-        other = (big.view(np.int32) + np.int32(steps) * np.sign(big).astype(np.int32)).view(np.float32)
-        o, d = _towards(rng, (3.0, 2.0, 1.0), c, 8.0, 2000)
-        res, tri = run("close planes", np.concatenate([big, other]).astype(np.float64), o, d)
+        # a direction with a zero component must fall back (its reciprocal is infinite); so must an origin beyond M = four
+        # times the largest |coordinate| (about 450 here)
+        if kind in ("zero direction component", "origins outside the bounds"):
+            assert np.all(res["verdict"] == G.INPUT)
+        if kind == "tie across subtrees":  # the patch is triangles 0-15: each of its hits ties with the pair behind it
+            on_patch = (tri >= 0) & (tri < 16)
+            assert on_patch.sum() > 1000 and np.all(res["verdict"][on_patch] == G.TIE)
     assert settled["close planes"] == 0 and rays["close planes"] > 0
-    # sliver fans in a coordinate plane, coordinates of magnitude 3, 1000 and 4096, every plane
-    for width, axis, x0 in ((0.1, 1, 0.0), (0.02, 1, 0.0), (0.5, 1, 0.0), (0.1, 0, 0.0), (0.1, 2, 0.0), (0.1, 1, 1000.0),
-                            (0.1, 1, -4096.0), (0.5, 2, 1000.0)):
-        eye = np.array([x0 + 3.0, 2.0, 1.0]) + rng.uniform(-1, 1, 3)
-        dd = np.array([0.5, 0.6, 0.62])
-        dd /= np.linalg.norm(dd)
-        fan = fan_scene(eye, dd, 100.0, width, 141.0, axis)
-        hitp = eye + 100.0 * dd
-        o, d = _towards(rng, eye, hitp, 4 * width, 3000)
-        o2, d2 = _towards(rng, eye, hitp, 150.0, 1000)
-        run("sliver fan in a coordinate plane", fan, np.concatenate([o, o2]), np.concatenate([d, d2]))
     assert 0 < settled["sliver fan in a coordinate plane"] < rays["sliver fan in a coordinate plane"]
-
-    # ---- free origins
-    # rays that start ON a triangle or on the shared edge of the pair (t near 0), into the half space of a second wall
-    wall = _tri(c + 30 * f - 200 * r - 200 * u, c + 30 * f + 400 * r - 200 * u, c + 30 * f - 200 * r + 400 * u)
-    room = np.concatenate([pair, wall])
-    k = rng.uniform(-0.9, 0.9, (1500, 1))
-    on_edge = (np.float32(c) + k * np.float32(40 * u)).astype(np.float32)
-    on_face = (np.float32(c) + k * np.float32(30 * u) + rng.uniform(-20, 20, (1500, 1)) * np.float32(r)).astype(np.float32)
-    o = np.concatenate([on_edge, on_face])
-    run("origins on a triangle", room, o, _dirs(rng, len(o)))
-    # grazing rays: within 1e-4 of the plane of the pair, from beside it
-    side = c - 70 * r + rng.uniform(-1e-4, 1e-4, (3000, 1)) * np.cross(r, u)
-    tgt = c + 70 * r + rng.uniform(-30, 30, (3000, 1)) * u + rng.uniform(-1e-4, 1e-4, (3000, 1)) * np.cross(r, u)
-    v = tgt - side
-    run("grazing rays", room, side.astype(np.float32), (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32))
-    # a direction with a zero component must fall back (its reciprocal is infinite)
-    o, d = _towards(rng, (3.0, 2.0, 1.0), c, 20.0, 600)
-    d = d.copy()
-    d[:200, 0], d[200:400, 1], d[400:, 2] = 0.0, 0.0, -0.0
-    res, tri = run("zero direction component", room, o, d)
-    assert np.all(res["verdict"] == G.INPUT)
-    # origins outside the scene's bounds: beyond M = four times the largest |coordinate| (about 450 here) the rule falls
-    # back; inside it, it may settle
-    o, d = _towards(rng, (9000.0, -7000.0, 8000.0), c, 30.0, 1000)
-    res, tri = run("origins outside the bounds", room, o, d)
-    assert np.all(res["verdict"] == G.INPUT)
-    o, d = _towards(rng, (-900.0, 700.0, -800.0), c, 30.0, 1000)  # outside the vertex box, within M
-    res, tri = run("origins outside the vertex box", room, o, d)
     for kind in sorted(rays):
         print("%-36s settled %d of %d hit rays" % (kind, settled[kind], rays[kind]))
     for kind in ("coplanar pair", "T-junction", "origins on a triangle", "origins outside the vertex box"):

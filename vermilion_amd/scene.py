@@ -613,6 +613,24 @@ class Scene:
         self._check(self._lib.vmx_guide_list_entries(self._h, C.byref(n)))
         return int(n.value)
 
+    def guide_trace(self, origin, direction, opts=None, records=False, complete=False, grid_blocks=0):
+        """vmx_guide_trace (debug entry): the guide form of the bounce traversal kernel on explicit rays.  Returns
+        (settled uint8 [n], slot uint32 [n], t float32 [n]): settled 1 where the guided launch settled the ray, slot the
+        leaf slot in the scene's tree (bvh()'s prim_order index, 0xFFFFFFFF: no hit).  records: the form that hands the
+        rays on as dense records; complete: the launch over the fallback list follows, so every ray has its answer
+        (else a fallback ray has slot 0xFFFFFFFF, t 0); grid_blocks: cap of the guided launch's blocks (0: a render's)."""
+        o, d = _f32(origin, 3), _f32(direction, 3)
+        n = o.shape[0]
+        if opts is None:
+            opts = make_opts()
+        settled = np.zeros(n, np.uint8)
+        slot = np.full(n, 0xFFFFFFFF, np.uint32)
+        t = np.zeros(n, np.float32)
+        flags = (1 if records else 0) | (2 if complete else 0)
+        self._check(self._lib.vmx_guide_trace(self._h, o.ctypes.data, d.ctypes.data, n, C.byref(opts), flags, int(grid_blocks),
+                                              settled.ctypes.data, slot.ctypes.data, t.ctypes.data))
+        return settled, slot, t
+
     def render(self, cam, opts):
         """PathTracer::Render into a host array [local_rows, W, 5] (RGBAZ)."""
         rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
