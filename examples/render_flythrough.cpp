@@ -15,7 +15,7 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough [--moving] [--textured] [--variance] [--upsample N/D] fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] [--textured] [--variance] [--adaptive] [--upsample N/D] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
@@ -41,6 +41,12 @@
 // It composes with --moving (the motion records go to the variance call) and with --textured (the albedo plane goes to
 // the variance-guided call, which then works on colour / albedo as the demodulated call does).  The mean variance of each
 // frame is printed beside its history length.
+//
+// --adaptive: the accumulate step becomes
+//   vmx_temporal_accumulate_adaptive_device  the same accumulation with the history cut where the lighting changed: the
+//                                            moved block's shadow and bounce light under --moving
+// on either kind of handle, so it composes with --moving (the motion records go to it) and --variance (it writes the
+// variance too).  Beside each frame's mean history length the share of pixels whose change ratio r exceeds 1 is printed.
 //
 // --upsample N/D (1 <= N <= D <= 4 N): every frame is rendered at N/D of the size with (D/N)^2 times the samples, rounded
 // down to a multiple of 4 — the same ray count — and accumulated and filtered at that low size; then
@@ -110,12 +116,13 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool moving = false, textured = false, variance = false;
+    bool moving = false, textured = false, variance = false, adaptive = false;
     uint32_t up_n = 0, up_d = 0;  // --upsample N/D
     for (; argc > 1 && std::strncmp(argv[1], "--", 2) == 0; --argc, ++argv) {
         if (std::strcmp(argv[1], "--moving") == 0) moving = true;
         else if (std::strcmp(argv[1], "--textured") == 0) textured = true;
         else if (std::strcmp(argv[1], "--variance") == 0) variance = true;
+        else if (std::strcmp(argv[1], "--adaptive") == 0) adaptive = true;
         else if (std::strcmp(argv[1], "--upsample") == 0 && argc > 2) {
             if (std::sscanf(argv[2], "%u/%u", &up_n, &up_d) != 2 || up_n < 1 || up_n > up_d || up_d > 4 * up_n) {
                 std::fprintf(stderr, "flythrough: --upsample N/D needs 1 <= N <= D <= 4 N\n");
@@ -187,11 +194,12 @@ int main(int argc, char **argv) {
     void *d_pos[2] = {nullptr, nullptr}, *d_motion = nullptr, *d_acc_plain = nullptr, *d_hist_plain = nullptr;
     void *d_albedo = nullptr;  // --textured: the frame's albedo plane, float4 per pixel
     void *d_var = nullptr;     // --variance: the variance of each pixel's luminance, one float per pixel
+    void *d_change = nullptr;  // --adaptive: each pixel's change ratio r, one float per pixel
     // --upsample: the handle, the full-size G-buffer and the filtered low frame (RGBAZ: the upsampler's input)
     vmx_upsample *upsampler = nullptr;
     void *d_rec_full = nullptr, *d_filtered = nullptr;
     const size_t full_pix = (size_t)FW * FH;
-    std::vector<float> var(variance ? (size_t)W * H : 0);
+    std::vector<float> var(variance ? (size_t)W * H : 0), change(adaptive ? (size_t)W * H : 0);
     std::vector<float> moved = pos, hist_plain(moving ? (size_t)W * H : 0);
     std::vector<unsigned char> rgba(full_pix * 4);
     std::vector<float> hist(npix);
@@ -207,6 +215,7 @@ int main(int argc, char **argv) {
     }
     if (textured && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_albedo, npix * 16) == 0;
     if (variance && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_var, npix * 4) == 0;
+    if (adaptive && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_change, npix * 4) == 0;
     if (moving && hip_ok && rc == VMX_OK) {
         hip_ok = hip.malloc_(&d_pos[0], pos.size() * 4) == 0 && hip.malloc_(&d_pos[1], pos.size() * 4) == 0 &&
                  hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0 && hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
@@ -250,7 +259,12 @@ int main(int argc, char **argv) {
                                               stream)) != VMX_OK)
             break;
         if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
-        if (variance) {
+        if (adaptive) {  // (d_var is NULL without --variance, as a handle without moments wants it)
+            if ((rc = vmx_temporal_accumulate_adaptive_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+                                                              nullptr, d_hist, d_var, d_change, nullptr, nullptr, nullptr,
+                                                              stream)) != VMX_OK)
+                break;
+        } else if (variance) {
             if ((rc = vmx_temporal_accumulate_variance_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
                                                               nullptr, d_hist, d_var, nullptr, nullptr, stream)) != VMX_OK)
                 break;
@@ -301,6 +315,12 @@ int main(int argc, char **argv) {
             for (float v : var) mean_var += v;
             std::printf("frame %u: mean luminance variance %.6f\n", i, mean_var / (double)npix);
         }
+        if (adaptive) {
+            if (!(hip_ok = hip.memcpy_(change.data(), d_change, npix * 4, 2) == 0)) break;
+            size_t cut = 0;
+            for (float r : change) cut += r > 1.f;
+            std::printf("frame %u: adaptive, r > 1 in %.2f %% of the pixels\n", i, 100.0 * (double)cut / (double)npix);
+        }
         if (moving) {
             if (!(hip_ok = hip.memcpy_(hist_plain.data(), d_hist_plain, npix * 4, 2) == 0)) break;
             double mean_plain = 0;
@@ -328,7 +348,7 @@ int main(int argc, char **argv) {
     if (filter) vmx_filter_destroy(filter);
     if (temporal) vmx_temporal_destroy(temporal);
     if (plain) vmx_temporal_destroy(plain);
-    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo, d_var, d_rec_full, d_filtered})
+    for (void *p : {d_frame, d_rec, d_acc, d_rgba8, d_hist, d_pos[0], d_pos[1], d_motion, d_acc_plain, d_hist_plain, d_albedo, d_var, d_change, d_rec_full, d_filtered})
         if (p) hip.free_(p);
     if (stream) hip.stream_destroy(stream);
     vmx_scene_destroy(scene);

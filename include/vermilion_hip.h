@@ -662,7 +662,9 @@ typedef struct vmx_temporal vmx_temporal;
 
 int vmx_temporal_default_params(vmx_temporal_params *out);
 /* An accumulator for width x height frames on `device`, checked and refused as vmx_filter_create does.  It owns its
- * two state buffers (48 B per pixel each); nothing is allocated after creation. */
+ * two state buffers (48 B per pixel each); nothing is allocated after creation, except that the first
+ * vmx_temporal_accumulate_adaptive_device on a handle allocates that call's reprojection plane (below), which
+ * vmx_temporal_destroy frees. */
 int vmx_temporal_create(int device, uint32_t width, uint32_t height, vmx_temporal **out);
 int vmx_temporal_destroy(vmx_temporal *t);
 /* Forgets the history: the next call is a first call.  A first call reads none of the state, so nothing is enqueued
@@ -805,6 +807,64 @@ int vmx_temporal_accumulate_variance_device(vmx_temporal *t, const vmx_camera *c
 int vmx_filter_apply_variance_device(vmx_filter *f, const void *d_in_rgbaz, const void *d_variance,
                                      const void *d_albedo /* or NULL */, void *d_out_rgbaz, void *d_rgba8,
                                      const vmx_filter_params *params, float sigma_luminance, void *stream);
+
+/* ---- adaptive temporal accumulation: cut history where lighting changed ---------------------------------
+ * The calls above blend with a = 1/min(n_h + 1, max_history) wherever the geometry test passes: the world's lighting is
+ * taken as static.  A static pixel whose illumination changed — a light dimmed or recoloured, the shadow and bounce
+ * light of a block moved by vmx_scene_update, a texture rebound — keeps its old colour and sheds it at 1/9, 1/10, ... per
+ * frame.  vmx_temporal_accumulate_adaptive_device carries a change detector: over a 7 x 7 window of like surface it
+ * compares the mean of the new frame with the mean of the reprojected history, per colour channel, in standard errors of
+ * the new frame's window mean, and where they differ by more than gamma it shortens the history length before the blend.
+ * The state layout does not change, so this call and the existing ones may alternate frame by frame on one handle.
+ *
+ * Everything is float, one rounding per written operation, left to right; `/` is correctly rounded, denormals are kept.
+ * Per pixel p the motion call computes any_p = sum_w > 0, h_p, nh_p, and on a moments handle the variance call g1_p = h1,
+ * g2_p = h2; all exactly as above.  hh_p = h_p where any_p, else 0.
+ * On a first call, on a miss, or where !any_p, the result is the existing call's, and d_change[p] = 0.  Otherwise a
+ * 7 x 7 window, dy = -3..3 (outer), dx = -3..3 (inner), q = p + (dx, dy); a tap outside the image, a tap with z_q < 0
+ * (this frame's guide) and a tap with !any_q are skipped;
+ *     d = n_p.x*n_q.x + n_p.y*n_q.y + n_p.z*n_q.z;  d = d > 0 ? d : 0;  normal_squarings times d = d*d;
+ *     t = (z_p - z_q) * (1.f/(sigma_depth*z_p));  w = d / (1.f + t*t)        (the variance window's weight for a hit)
+ *     if w > 0 and finite:  sw = sw + w;  sww = sww + w*w;  per channel k, c the input frame's colour:
+ *       sc.k = sc.k + w*c_q.k;  scc.k = scc.k + w*(c_q.k*c_q.k);  sh.k = sh.k + w*hh_q.k                    (all from 0)
+ *   support = sw > 0 && sw*sw >= min_support*sww                  (sw*sw/sww: the window's effective number of taps)
+ *   per channel:  mc = sc/sw;  mh = sh/sw;  v = scc/sw - mc*mc;  v = v > 0 ? v : 0;
+ *                 s2 = (2.f*v)*(sww/(sw*sw)) + VMX_ADAPTIVE_EPS;  dm = mc - mh;  k = (dm*dm)/s2
+ *                 (the factor 2 bounds the noise of the history's window mean by that of the input's)
+ *   K = k.r;  if (k.g > K) K = k.g;  if (k.b > K) K = k.b;  r = K/(gamma*gamma)
+ *   cut = support && r > 1.f      (false for NaN: a NaN colour in the window never cuts; an infinite one follows the
+ *                                  arithmetic)
+ *   nh_e = cut ? nh/r : nh;  t = nh_e + 1.f;  n' = t < max_history ? t : max_history;  a = 1.f/n';  out. = h. + (c. - h.)*a
+ *   the moments blend with the same a:  m1' = g1 + (l - g1)*a;  m2' = g2 + (l*l - g2)*a
+ *   d_change[p] = support ? r : 0
+ * and the variance is then computed from the new state, as in the variance call.  With gamma*gamma = +inf (gamma = 3e38f)
+ * r is 0 or NaN and the call is the existing one bit for bit.
+ * Arguments: on a handle without moments the call is vmx_temporal_accumulate_motion_device with the changes above;
+ * d_variance and vparams must be NULL.  On a VMX_TEMPORAL_MOMENTS handle it is vmx_temporal_accumulate_variance_device
+ * with them; d_variance is required.  The existing calls stay allowed or refused on each kind of handle as before.
+ * aparams (NULL: the defaults) is checked right after vparams; d_change — W*H floats or NULL, DEVICE memory of the
+ * handle's device, 4-byte aligned, overlapping no other buffer of the call — after d_variance; what depends on the kind of
+ * handle (a missing or a surplus d_variance) is checked with the handle.  Every other rule, message and order of checks
+ * is the motion or variance call's.
+ * The first adaptive call on a handle allocates one reprojection plane, 16 B per pixel (24 B with moments): the only
+ * allocation after creation; if it fails the call is VMX_ERR_NOMEM and the handle is untouched.  A call in place
+ * (d_out_rgbaz == d_in_rgbaz) costs one more dense pass, because the window reads neighbouring blocks' input.
+ * tests/adaptive_spec.py restates it; the kernels hold to it bit for bit. */
+#define VMX_ADAPTIVE_EPS 1e-10f
+typedef struct vmx_adaptive_params {
+    float gamma;               /* finite, > 0;  default 3.f   (standard errors)   */
+    float min_support;         /* finite, >= 1; default 4.f   (effective taps)    */
+    uint32_t normal_squarings; /* 0..8;         default 5                         */
+    float sigma_depth;         /* finite, > 0;  default 0.1f                      */
+    uint32_t reserved[4];      /* must be 0                                       */
+} vmx_adaptive_params;
+int vmx_adaptive_default_params(vmx_adaptive_params *out);
+int vmx_temporal_accumulate_adaptive_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit,
+                                            const void *d_motion /* or NULL */, const void *d_in_rgbaz,
+                                            void *d_out_rgbaz, void *d_rgba8, void *d_history_len, void *d_variance,
+                                            void *d_change /* W*H floats or NULL */, const vmx_temporal_params *tparams,
+                                            const vmx_variance_params *vparams, const vmx_adaptive_params *aparams,
+                                            void *stream);
 
 /* ---- guided upsampling: render small, reconstruct at full size ----------------------------------------------
  * A render costs rays = pixels x samples, a G-buffer one camera ray per pixel at any size.  So paths are traced at a

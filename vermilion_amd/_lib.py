@@ -37,6 +37,7 @@ VMX_ALBEDO_FLOOR = 2.0 ** -10  # the demodulated filter's lower clamp of an albe
 VMX_TEMPORAL_MOMENTS = 1  # vmx_temporal_create_ex: the handle keeps luminance moments (vmx_temporal_accumulate_variance_device)
 VMX_VARIANCE_EPS = 1e-10  # the variance-guided filter's floor of sigma_luminance^2 * variance
 VMX_SIGMA_LUMINANCE_DEFAULT = 4.0
+VMX_ADAPTIVE_EPS = 1e-10  # the adaptive accumulation's floor of the window mean's squared standard error
 VMX_UPDATE_REFIT = 0
 VMX_UPDATE_REBUILD = 1
 
@@ -228,6 +229,20 @@ class VarianceParams(C.Structure):
                 "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [
+        ("gamma", C.c_float),
+        ("min_support", C.c_float),
+        ("normal_squarings", C.c_uint32),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+    def as_dict(self):
+        return {"gamma": self.gamma, "min_support": self.min_support, "normal_squarings": self.normal_squarings,
+                "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
+
+
 class UpsampleParams(C.Structure):
     _fields_ = [
         ("normal_squarings", C.c_uint32),
@@ -308,6 +323,10 @@ SYMBOLS = {
     "vmx_temporal_accumulate_variance_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P,
                                                           C.POINTER(TemporalParams), C.POINTER(VarianceParams), _P]),
     "vmx_filter_apply_variance_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(FilterParams), C.c_float, _P]),
+    "vmx_adaptive_default_params": (C.c_int, [C.POINTER(AdaptiveParams)]),
+    "vmx_temporal_accumulate_adaptive_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P, _P,
+                                                          C.POINTER(TemporalParams), C.POINTER(VarianceParams),
+                                                          C.POINTER(AdaptiveParams), _P]),
     "vmx_upsample_default_params": (C.c_int, [C.POINTER(UpsampleParams)]),
     "vmx_upsample_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "vmx_upsample_destroy": (C.c_int, [_P]),

@@ -70,3 +70,16 @@ static int variance_params(const vmx_variance_params *in, vmx_variance_params &o
 }
 
 extern "C" int vmx_variance_default_params(vmx_variance_params *out) { return default_params(out, kVarianceDefaults); }
+
+static const vmx_adaptive_params kAdaptiveDefaults = {3.f, 4.f, 5u, 0.1f, {0u, 0u, 0u, 0u}};
+
+static int adaptive_params(const vmx_adaptive_params *in, vmx_adaptive_params &out) {
+    out = in ? *in : kAdaptiveDefaults;
+    if (!finite_positive(out.gamma)) return fail(VMX_ERR_INVALID, "vmx_adaptive_params: gamma must be finite and > 0");
+    if (!(std::isfinite(out.min_support) && out.min_support >= 1.f))
+        return fail(VMX_ERR_INVALID, "vmx_adaptive_params: min_support must be finite and >= 1");
+    if (!squarings_ok(out.normal_squarings)) return fail(VMX_ERR_INVALID, "vmx_adaptive_params: normal_squarings must be 0..8");
+    if (!finite_positive(out.sigma_depth)) return fail(VMX_ERR_INVALID, "vmx_adaptive_params: sigma_depth must be finite and > 0");
+    if (!reserved_zero(out.reserved)) return fail(VMX_ERR_INVALID, "vmx_adaptive_params: reserved words must be 0");
+    return VMX_OK;
+}

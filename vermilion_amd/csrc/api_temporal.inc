@@ -7,6 +7,8 @@ struct VMX_OPAQUE vmx_temporal {
     uint32_t width = 0, height = 0;
     DevBuf<unsigned char> state[2];  // three float4 planes per buffer: (c_h.rgb, n_h) (n.xyz, z) (X.xyz, -)
     bool moments = false;            // VMX_TEMPORAL_MOMENTS: a fourth plane of float2 (m1, m2) follows them
+    DevBuf<unsigned char> plane;     // vmx_temporal_accumulate_adaptive_device's reprojection plane, float4 (hh.rgb, nh) and with moments
+                                     // float2 (g1, g2) per pixel: allocated by the first such call, never by any other
     int cur = 0;                     // the buffer the last call wrote
     bool has_history = false;        // false after create and reset: the next call is a first call
     TemporalCam hist_cam{};          // the last call's camera
@@ -89,28 +91,45 @@ struct TemporalVariance {
     const vmx_variance_params *params;
 };
 
-// the three accumulate entries; var: the variance entry's own arguments, NULL for the other two
+// what vmx_temporal_accumulate_adaptive_device takes besides the others' arguments
+struct TemporalAdaptive {
+    void *d_change;  // an output, or NULL
+    const vmx_adaptive_params *params;
+};
+
+// the four accumulate entries; var: the variance entry's own arguments, NULL for the motion entries; ad: the adaptive
+// entry's — it takes both kinds of handle, so `var` is then non-NULL and whether the call is a variance call is the
+// handle's to say
 static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
                                const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
-                               const vmx_temporal_params *params, void *stream, const TemporalVariance *var) {
-    const bool variance = var != nullptr;
+                               const vmx_temporal_params *params, void *stream, const TemporalVariance *var,
+                               const TemporalAdaptive *ad = nullptr) {
+    const bool adaptive = ad != nullptr;
+    bool variance = var != nullptr && !adaptive;
     void *d_variance = var ? var->d_variance : nullptr;
+    void *d_change = ad ? ad->d_change : nullptr;
     // checks that need no device, in the filter's order so that each can be seen alone; the handle comes last
     vmx_temporal_params prm;
     if (int rc = temporal_params(params, prm)) return rc;
     vmx_variance_params vprm = kVarianceDefaults;
-    if (variance)
+    if (var)
         if (int rc = variance_params(var->params, vprm)) return rc;
+    vmx_adaptive_params aprm = kAdaptiveDefaults;
+    if (adaptive)
+        if (int rc = adaptive_params(ad->params, aprm)) return rc;
     if (!cam) return fail(VMX_ERR_INVALID, "NULL camera");
     if (!d_rayhit) return fail(VMX_ERR_INVALID, "NULL d_rayhit");
     if (!d_in_rgbaz) return fail(VMX_ERR_INVALID, "NULL d_in_rgbaz");
     if (variance && !d_variance) return fail(VMX_ERR_INVALID, "NULL d_variance");
-    if (!variance && !d_out_rgbaz && !d_rgba8) return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
+    // (the adaptive call: a variance it was given counts as an output; whether it needs one is the handle's to say)
+    if (!variance && !(adaptive && d_variance) && !d_out_rgbaz && !d_rgba8)
+        return fail(VMX_ERR_INVALID, "no output: d_out_rgbaz and d_rgba8 are both NULL");
     if ((uintptr_t)d_rayhit & 15u) return fail(VMX_ERR_INVALID, "d_rayhit must be 16-byte aligned");
     if ((uintptr_t)d_motion & 15u) return fail(VMX_ERR_INVALID, "d_motion must be 16-byte aligned");
     if (((uintptr_t)d_in_rgbaz | (uintptr_t)d_out_rgbaz | (uintptr_t)d_rgba8 | (uintptr_t)d_history_len) & 3u)
         return fail(VMX_ERR_INVALID, "d_in_rgbaz, d_out_rgbaz, d_rgba8 and d_history_len must be 4-byte aligned");
     if ((uintptr_t)d_variance & 3u) return fail(VMX_ERR_INVALID, "d_variance must be 4-byte aligned");
+    if ((uintptr_t)d_change & 3u) return fail(VMX_ERR_INVALID, "d_change must be 4-byte aligned");
     FrameDev fr;
     {
         const vmx_opts none{};  // (make_frame reads a camera's opts too: the defaults of a zeroed struct)
@@ -118,6 +137,13 @@ static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const voi
     }
     if (!t) return fail(VMX_ERR_INVALID, "NULL handle");
     std::lock_guard<std::mutex> lock(t->mu);
+    if (adaptive) {
+        variance = t->moments;
+        if (variance && !d_variance) return fail(VMX_ERR_INVALID, "NULL d_variance");
+        if (!variance && (d_variance || var->params))
+            return fail(VMX_ERR_INVALID, "the handle keeps no moments: d_variance and vparams must be NULL (or create it with "
+                                         "vmx_temporal_create_ex(.., VMX_TEMPORAL_MOMENTS, ..))");
+    }
     if (variance && !t->moments)
         return fail(VMX_ERR_INVALID, "the handle keeps no moments: create it with vmx_temporal_create_ex(.., VMX_TEMPORAL_MOMENTS, ..)");
     if (!variance && t->moments)
@@ -139,12 +165,23 @@ static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const voi
         // d_variance against every other buffer of the call
         if (meets_any(Span{d_variance, npix * 4}, {motion, rayhit, in, out, q8, hist}))
             return fail(VMX_ERR_INVALID, "d_variance overlaps another buffer of the call");
+        // d_change against every other buffer of the call
+        if (meets_any(Span{d_change, npix * 4}, {motion, rayhit, in, out, q8, hist, Span{d_variance, npix * 4}}))
+            return fail(VMX_ERR_INVALID, "d_change overlaps another buffer of the call");
     }
     HIP_TRY(hipSetDevice(t->device));
     if (int rc = check_device_ptrs(t->device, {{d_rayhit, "d_rayhit"}, {d_in_rgbaz, "d_in_rgbaz"}, {d_out_rgbaz, "d_out_rgbaz"},
                                                {d_rgba8, "d_rgba8"}, {d_history_len, "d_history_len"}, {d_motion, "d_motion"},
-                                               {d_variance, "d_variance"}}))
+                                               {d_variance, "d_variance"}, {d_change, "d_change"}}))
         return rc;
+    // the one allocation after creation: the reprojection plane, by the first adaptive call (a failure leaves the handle
+    // as it was)
+    if (adaptive && !t->plane.p) {
+        DevBuf<unsigned char> plane;
+        if (plane.ensure((size_t)t->width * t->height * (t->moments ? 24 : 16)))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the reprojection plane");
+        t->plane = std::move(plane);
+    }
     hipStream_t s = (hipStream_t)stream;
     if (int rc = t->done.wait(s)) return rc;  // after the previous call on this handle
     TemporalPass a{};
@@ -160,7 +197,21 @@ static int temporal_accumulate(vmx_temporal *t, const vmx_camera *cam, const voi
     a.first = !t->has_history;
     a.motion = d_motion;
     a.moments = t->moments;
-    LAUNCH_TRY(launch_temporal(a, s));
+    if (adaptive && !a.first) {
+        // k_temporal_gather and k_rectify; a call in place leaves the frame to k_adaptive_store (vmx_adaptive.inc)
+        AdaptivePass ap{};
+        ap.t = a;
+        const bool in_place = d_out_rgbaz && d_out_rgbaz == d_in_rgbaz;
+        if (in_place) ap.t.out_rgbaz = nullptr;
+        ap.plane = t->plane.p, ap.change = (float *)d_change;
+        ap.gamma2 = aprm.gamma * aprm.gamma;
+        ap.min_support = aprm.min_support, ap.sigma_depth = aprm.sigma_depth, ap.squarings = aprm.normal_squarings;
+        LAUNCH_TRY(launch_adaptive(ap, in_place ? (float *)d_out_rgbaz : nullptr, s));
+    } else {
+        // (a first call has no history to test: the existing call, and no pixel changed)
+        if (adaptive && d_change) HIP_TRY(hipMemsetAsync(d_change, 0, (size_t)t->width * t->height * 4, s));
+        LAUNCH_TRY(launch_temporal(a, s));
+    }
     if (variance) {
         VariancePass v{};
         v.width = t->width, v.height = t->height;
@@ -190,6 +241,18 @@ int vmx_temporal_accumulate_variance_device(vmx_temporal *t, const vmx_camera *c
                                             const vmx_variance_params *vparams, void *stream) {
     const TemporalVariance var{d_variance, vparams};
     return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, params, stream, &var);
+}
+
+int vmx_adaptive_default_params(vmx_adaptive_params *out) { return default_params(out, kAdaptiveDefaults); }
+
+int vmx_temporal_accumulate_adaptive_device(vmx_temporal *t, const vmx_camera *cam, const void *d_rayhit, const void *d_motion,
+                                            const void *d_in_rgbaz, void *d_out_rgbaz, void *d_rgba8, void *d_history_len,
+                                            void *d_variance, void *d_change, const vmx_temporal_params *tparams,
+                                            const vmx_variance_params *vparams, const vmx_adaptive_params *aparams, void *stream) {
+    const TemporalVariance var{d_variance, vparams};
+    const TemporalAdaptive ad{d_change, aparams};
+    return temporal_accumulate(t, cam, d_rayhit, d_motion, d_in_rgbaz, d_out_rgbaz, d_rgba8, d_history_len, tparams, stream, &var,
+                               &ad);
 }
 
 } /* extern "C" */

@@ -329,6 +329,20 @@ struct TemporalPass {  // one call
     bool moments;          // a fourth plane of float2 (m1, m2) follows the three in both states (after `motion`, for the same reason)
 };
 int launch_temporal(const TemporalPass &pass, void *stream);
+// adaptive temporal accumulation (vmx_adaptive.inc; the arithmetic is stated in include/vermilion_hip.h): a call that is
+// no first call, as two passes — k_temporal_gather, the reprojection alone, into `plane`, and k_rectify, the window test,
+// the cut and the blend
+struct AdaptivePass {
+    TemporalPass t;        // as launch_temporal takes it (first == false); out_rgbaz NULL for a call in place
+    void *plane;           // float4 (hh.rgb, any ? nh : 0) per pixel, then with moments float2 (g1, g2) per pixel
+    float *change;         // W*H floats or NULL
+    float gamma2;          // gamma * gamma
+    float min_support, sigma_depth;
+    uint32_t squarings;    // normal_squarings
+};
+// store_in_place: the frame of a call in place (k_rectify leaves it alone, its r, g, b are copied from the new state
+// afterwards) or NULL
+int launch_adaptive(const AdaptivePass &pass, float *store_in_place, void *stream);
 // the variance of a moments state (vmx_variance.inc; the arithmetic is stated in include/vermilion_hip.h)
 struct VariancePass {
     uint32_t width, height;

@@ -4065,6 +4065,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 
 // temporal accumulation: reprojected history blended with each new frame
 #include "vmx_temporal.inc"
+// adaptive temporal accumulation: the reprojection alone, then the window test that cuts stale history before the blend
+#include "vmx_adaptive.inc"
 // variance-guided denoising: the variance of a moments accumulator and the filter it steers
 #include "vmx_variance.inc"
 // motion records for refitted geometry: where each pixel's surface point was before an update

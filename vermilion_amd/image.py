@@ -183,7 +183,7 @@ class Temporal(_Handle):
         self._h = h
 
     def accumulate(self, cam, raw, rgbaz, out=None, rgba8=None, history=None, params=None, stream=None, motion=None,
-                   variance=None, variance_params=None):
+                   variance=None, variance_params=None, adaptive=None, change=None):
         """vmx_temporal_accumulate_device: one frame.  `cam` is that frame's camera (make_camera), `raw` its G-buffer —
         the ["raw"] tensor of Scene.raycast_camera(cam, opts, 0), float32 [height, width, 16] — and `rgbaz` the float32
         [height, width, 5] frame.  The accumulated frame goes to `out` (same shape; may be `rgbaz` itself) and / or
@@ -195,6 +195,10 @@ class Temporal(_Handle):
         `variance` (vmx_temporal_accumulate_variance_device): float32 [height, width], receives the variance of each
         pixel's luminance, for Filter.apply(..., variance=...); required on a handle made with moments=True and refused
         on any other.  variance_params: make_variance_params(...), default the library's.
+        `adaptive` (vmx_temporal_accumulate_adaptive_device): True, or make_adaptive_params(...) — the history is cut
+        where the lighting changed (on either kind of handle, with or without `motion`); None or False is the call
+        without.  `change`: float32 [height, width], receives each pixel's change ratio r (0 without support); it
+        needs `adaptive`.
         Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised; returns (out, rgba8)."""
         import torch
         dev = torch.device("cuda", self.device)
@@ -203,10 +207,18 @@ class Temporal(_Handle):
             raise ValueError("variance is required: the handle was made with moments=True")
         if not moments and (variance is not None or variance_params is not None):
             raise ValueError("variance needs a handle made with moments=True")
+        if adaptive is False:
+            adaptive = None
+        if adaptive is not None and adaptive is not True and not isinstance(adaptive, L.AdaptiveParams):
+            raise ValueError("adaptive must be None, True or make_adaptive_params(...)")
+        if change is not None and adaptive is None:
+            raise ValueError("change needs adaptive")
         _frame_tensor(raw, "raw", torch.float32, self.shape + (16,), dev)
         _frame_tensor(rgbaz, "rgbaz", torch.float32, self.shape + (5,), dev)
         if variance is not None:
             _frame_tensor(variance, "variance", torch.float32, self.shape, dev)
+        if change is not None:
+            _frame_tensor(change, "change", torch.float32, self.shape, dev)
         if motion is not None:
             _frame_tensor(motion, "motion", torch.float32, self.shape + (8,), dev)
         out, rgba8 = _out_pair(out, rgba8, self.shape, dev)
@@ -214,7 +226,13 @@ class Temporal(_Handle):
             _frame_tensor(history, "history", torch.float32, self.shape, dev)
         with _SideStream(dev, stream) as run:
             prm, s = None if params is None else C.byref(params), C.c_void_p(run.cuda_stream)
-            if moments:
+            if adaptive is not None:
+                vprm = None if variance_params is None else C.byref(variance_params)
+                aprm = None if adaptive is True else C.byref(adaptive)
+                self._check(self._lib.vmx_temporal_accumulate_adaptive_device(self._h, C.byref(cam), _ptr(raw), _ptr(motion),
+                                                                              _ptr(rgbaz), _ptr(out), _ptr(rgba8), _ptr(history),
+                                                                              _ptr(variance), _ptr(change), prm, vprm, aprm, s))
+            elif moments:
                 vprm = None if variance_params is None else C.byref(variance_params)
                 self._check(self._lib.vmx_temporal_accumulate_variance_device(self._h, C.byref(cam), _ptr(raw), _ptr(motion),
                                                                               _ptr(rgbaz), _ptr(out), _ptr(rgba8), _ptr(history),

@@ -143,6 +143,21 @@ def make_variance_params(min_history=None, normal_squarings=None, sigma_depth=No
     return p
 
 
+def make_adaptive_params(gamma=None, min_support=None, normal_squarings=None, sigma_depth=None):
+    """vmx_adaptive_params: the library's defaults (vmx_adaptive_default_params) with the given fields replaced"""
+    p = L.AdaptiveParams()
+    L.check(L.lib().vmx_adaptive_default_params(C.byref(p)))
+    if gamma is not None:
+        p.gamma = float(gamma)
+    if min_support is not None:
+        p.min_support = float(min_support)
+    if normal_squarings is not None:
+        p.normal_squarings = int(normal_squarings)
+    if sigma_depth is not None:
+        p.sigma_depth = float(sigma_depth)
+    return p
+
+
 def make_upsample_params(normal_squarings=None, sigma_depth=None):
     """vmx_upsample_params: the library's defaults (vmx_upsample_default_params) with the given fields replaced"""
     p = L.UpsampleParams()
