@@ -412,6 +412,15 @@ int vmx_guide_rays(const vmx_scene *scene, uint64_t *settled, uint64_t *fallback
 /* Debug entry: the entries of the bounce-generation lists that the last render call on this scene handed to the
  * guide form of the traversal kernel, counted on the host: settled + fallback of vmx_guide_rays equals it. */
 int vmx_guide_list_entries(const vmx_scene *scene, uint64_t *entries);
+/* Debug entry: the same two counts for the FUSED launches of the last render call on this scene (the kernel that keeps
+ * paths to their end: the tail of a split pass, the passes of pipeline form 1 and the small passes of form 0), where
+ * rays of any depth, camera rays included, walk the guide.  `settled` counts the traversals the rule settled;
+ * `fallback` those that ran over the reference tree: the rule's fallbacks, which start again there in the same lane,
+ * and the rays that may not walk the guide at all (a non-finite origin, direction or reciprocal, an origin beyond the
+ * rule's reach).  Every traversal of those launches is counted once, one with a non-finite direction too, which is no
+ * ray of vmx_stats.  Both are 0 wherever vmx_guide_rays' are; vmx_guide_rays and vmx_guide_list_entries do not
+ * count these launches. */
+int vmx_guide_fused_rays(const vmx_scene *scene, uint64_t *settled, uint64_t *fallback);
 /* Debug entry: the guide form of the bounce traversal kernel on n explicit rays (host buffers), so that a test can hold
  * the device's guide walk against the host program of guide_walk.h ray by ray.  The rays become path state and one id
  * list as vmx_radiance forms them; one launch walks the guide as a render's guided bounce generation does (same stack

@@ -402,6 +402,7 @@ int vmx_radiance(const vmx_scene *csc, const float *origin, const float *dir, ui
         HIP_TRY(hipEventRecord(ev0, s));
         HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
         if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
         int r;
         if (legacy) {
             r = ab_radiance_enqueue(sc, fr, q, d_o.p, d_d.p, n, opts->seed, count, tn.tail_threshold, s, timed, launches, bb);

@@ -76,6 +76,20 @@ LaunchCfg paths_cfg(const vmx_scene *sc, uint32_t entries, uint64_t items, int b
 // leave the tail of one record chunk unused, which the record lists are padded for
 constexpr uint32_t kGuideFallbackBlocks = 2;
 
+// the scene's guide as the fused kernel's GUIDE forms read it (k_paths<.., GuidePathsDev>: the tail of run_ids, the fused passes of
+// render_pass), where tn.guide holds, the guide is still valid and the call has its counters; else off = 0: the launch is
+// the reference-tree instantiation.  A launch that is handed this must have its stack bound with guided = true.
+GuidePathsDev guide_paths(const vmx_scene *sc, const Tuning &tn) {
+    GuidePathsDev g{};
+    const vmx_scene::Guide &sg = sc->guide;
+    if (tn.guide && sg.valid && sg.base && sg.off && sc->ws.guide_fused_ctr.p) {
+        g.off = sg.off, g.tri_off = sg.off + sg.tri_off, g.root_ref = sg.root_ref;
+        g.scene_max = sg.scene_max;
+        g.ctr = sc->ws.guide_fused_ctr.p;
+    }
+    return g;
+}
+
 // ---- split wavefront (pipeline 0): k_trace_q + k_shade + id queues ---------------------------
 int ensure_paths(vmx_scene *sc, size_t nslots, PathArrays &pa, IdQueue q[3]) {
     Workspace &ws = sc->ws;
@@ -154,12 +168,14 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
         if (rc) return rc;
         const uint32_t entries = tail ? tn.lds_entries : tn.lds_bounce;
         LaunchCfg cfg = paths_cfg(sc, entries, total, tail ? tail_blocks : trace_blocks);
-        rc = bind_stack(sc, tn, entries, cfg.grid, total, wk, !tail && tn.guide);
+        // (guided for the tail too: a lane of the GUIDE form changes tree in mid-launch, so its slab holds the deeper one)
+        rc = bind_stack(sc, tn, entries, cfg.grid, total, wk, tn.guide);
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, kSubQueues * 32 * 4, s));
         if ((rc = timed_begin(ws, timed, s, 1, tail ? VMX_K_TAIL : VMX_K_TRACE_BOUNCE))) return rc;
         if (tail) {
-            LAUNCH_TRY(launch_tail(sc->dev, fr, wk, pa, ctr, count, cfg, s));
+            const GuidePathsDev gp = guide_paths(sc, tn);
+            LAUNCH_TRY(launch_tail(sc->dev, fr, wk, pa, ctr, count, cfg, s, &gp));
             if ((rc = timed_end(timed, s))) return rc;
             launches += 2;
             break;
@@ -177,7 +193,7 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
                 // not settle: it reads the list's length on the device, appends to the same record list, and every ray is
                 // counted by the launch that settles it.  Both launches are one timed interval.
                 GuideDev gd;
-                gd.base = sc->guide.geom.p, gd.tri_off = sc->guide.tri_off, gd.root_ref = sc->guide.root_ref;
+                gd.base = sc->guide.base, gd.tri_off = sc->guide.tri_off, gd.root_ref = sc->guide.root_ref;
                 gd.scene_max = sc->guide.scene_max;
                 gd.fb_capacity = (uint32_t)std::min<size_t>(ws.guide_fb.n, 0xFFFFFFFFu);
                 gd.fb_ids = ws.guide_fb.p, gd.fb_count = ws.guide_fb_count.p, gd.ctr = ws.guide_ctr.p, gd.overflow = ctr;
@@ -239,6 +255,9 @@ int finish_stats(vmx_scene *sc, hipStream_t s, std::vector<TimedLaunch> &timed, 
     unsigned long long guide_rays[2] = {0, 0};
     if (ws.guide_ctr.p) HIP_TRY(hipMemcpy(guide_rays, ws.guide_ctr.p, sizeof(guide_rays), hipMemcpyDeviceToHost));
     sc->guide_settled = guide_rays[0], sc->guide_fallback = guide_rays[1];
+    unsigned long long fused_rays[2] = {0, 0};
+    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemcpy(fused_rays, ws.guide_fused_ctr.p, sizeof(fused_rays), hipMemcpyDeviceToHost));
+    sc->guide_fused_settled = fused_rays[0], sc->guide_fused_fallback = fused_rays[1];
     sc->guide_entries = ws.guide_entries, ws.guide_entries = 0;
     std::memset(&sc->timings, 0, sizeof(sc->timings));
     for (auto &tl : timed) {
@@ -304,8 +323,9 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     tn.sorted = tn.two_phase && !(opts->reserved[0] & 0x200u);
     tn.pool = ab_pool_bit(opts) && !tn.sorted && !count;
     // bounce generations of the split passes walk the scene's guide tree (guide_walk.h) unless reserved[0] bit 14 keeps them
-    // on the reference tree; never the counting build (its visit counts are the oracle's) nor the A/B pool.  The fused
-    // kernels (k_paths: small passes, the tail) and the camera kernel keep the reference tree.
+    // on the reference tree; never the counting build (its visit counts are the oracle's) nor the A/B pool.  So do the
+    // rays of the fused launches (k_paths' GUIDE forms: small passes, the tail; guide_paths).  The camera kernel keeps
+    // the reference tree.
     tn.guide = sc->guide.valid && !count && !ab_pool_bit(opts) && !(opts->reserved[0] & 0x4000u);
     fr.bounce_bits = tn.sorted ? 1u : 0u;
     fr.camera_bits = tn.two_phase ? 1u : 0u;  // read by k_trace_w<0, .., SORT> / k_shade_ends<0> only
@@ -360,7 +380,8 @@ int render_setup(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, Pix
     }
     job.smax = job.smax_alloc = smax;  // buffers are sized for this many samples per pixel and pass
 
-    HIP_TRY((hipError_t)query_paths_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, count, &job.rb));
+    // (tn.guide: the fused launches of this job are the GUIDE forms, whose occupancy sizes their persistent grid)
+    HIP_TRY((hipError_t)query_paths_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, count, &job.rb, tn.guide));
     if (job.rb < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
 
     job.n_pad_max = (npix + 63u) & ~63u;
@@ -500,7 +521,8 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
             ws.live_ids.ensure((size_t)n_pad_max * smax + 64) || ws.live_tmp.ensure(job.live_tmp_bytes + 256))
             return fail(VMX_ERR_NOMEM, "hipMalloc failed for the live-path list");
     }
-    if (ws.rad.ensure((size_t)n_pad_max * smax * 16) || ws.next_count.ensure(32) || ws.counters.ensure(1))
+    if (ws.rad.ensure((size_t)n_pad_max * smax * 16) || ws.next_count.ensure(32) || ws.counters.ensure(1) ||
+        (tn.guide && ws.guide_fused_ctr.ensure(2)))  // (the fused kernel's GUIDE forms: every pipeline form has a fused launch)
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the render workspace");
     job.px = PixelStateDev{job.pixels->accum.p, job.pixels->count.p, job.pixels->cursor.p};
     if (job.split_any) {
@@ -704,11 +726,12 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         if (rc) return rc;
     } else if (refill) {
         LaunchCfg cfg = paths_cfg(sc, tn.lds_entries, (uint64_t)n_pad * S, job.rb);
-        rc = bind_stack(sc, tn, tn.lds_entries, cfg.grid, (uint64_t)n_pad * S, wk);
+        rc = bind_stack(sc, tn, tn.lds_entries, cfg.grid, (uint64_t)n_pad * S, wk, tn.guide);  // (guided: as the tail of run_ids)
         if (rc) return rc;
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, kSubQueues * 32 * 4, s));
         if ((rc = timed_begin(ws, timed, s, 0, VMX_K_FUSED))) return rc;
-        LAUNCH_TRY(launch_paths(sc->dev, fr, wk, px, ws.rad.p, ws.counters.p, count, cfg, s));
+        const GuidePathsDev gp = guide_paths(sc, tn);
+        LAUNCH_TRY(launch_paths(sc->dev, fr, wk, px, ws.rad.p, ws.counters.p, count, cfg, s, &gp));
         if ((rc = timed_end(timed, s))) return rc;
         launches += 2;
     } else {  // forms 2 and 3
@@ -750,6 +773,7 @@ int render_run(vmx_scene *sc, RenderJob &job, uint32_t samples, vmx_stats *stats
     if ((rc = render_bind(sc, job, samples))) return rc;
     HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
     if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
     if (!job.initialised && (rc = render_init_pixels(sc, job))) return rc;
     uint32_t left = samples ? samples : 0xFFFFFFFFu;
     while (job.n_active > 0 && left > 0) {
@@ -813,6 +837,7 @@ int bruteforce_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, 
     HIP_TRY(hipMemcpyAsync(ws.pixels.active[0].p, ws.order.data(), (size_t)npix * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
     if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
     HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 4, s));
     HIP_TRY(hipEventRecord(ev0, s));
     // stack as in the traversal kernels: a few levels per lane in LDS, the rest in the global slab (the whole stack
@@ -937,6 +962,14 @@ int vmx_guide_rays(const vmx_scene *csc, uint64_t *settled, uint64_t *fallback) 
     return VMX_OK;
 }
 
+int vmx_guide_fused_rays(const vmx_scene *csc, uint64_t *settled, uint64_t *fallback) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc || !settled || !fallback) return fail(VMX_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *settled = sc->guide_fused_settled, *fallback = sc->guide_fused_fallback;
+    return VMX_OK;
+}
+
 int vmx_guide_list_entries(const vmx_scene *csc, uint64_t *entries) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
     if (!sc || !entries) return fail(VMX_ERR_INVALID, "NULL argument");
@@ -955,7 +988,7 @@ int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir,
     if (opts->collect_counters) return fail(VMX_ERR_INVALID, "vmx_guide_trace: the counting build never walks the guide");
     const bool records = (flags & 1u) != 0, complete = (flags & 2u) != 0;
     std::lock_guard<std::mutex> lock(sc->mu);
-    if (!sc->guide.valid || !sc->guide.geom.p)
+    if (!sc->guide.valid || !sc->guide.base)
         return fail(VMX_ERR_INVALID, "vmx_guide_trace: the scene has no valid guide (another builder, or vertices moved without a rebuild)");
     if (n == 0) return VMX_OK;
     int rc = bind_device(sc);
@@ -998,7 +1031,7 @@ int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir,
         wk.keep_all = 1u;
     }
     GuideDev gd;
-    gd.base = sc->guide.geom.p, gd.tri_off = sc->guide.tri_off, gd.root_ref = sc->guide.root_ref;
+    gd.base = sc->guide.base, gd.tri_off = sc->guide.tri_off, gd.root_ref = sc->guide.root_ref;
     gd.scene_max = sc->guide.scene_max;
     gd.fb_capacity = n;
     gd.fb_ids = ws.guide_fb.p, gd.fb_count = ws.guide_fb_count.p, gd.ctr = ws.guide_ctr.p, gd.overflow = ws.counters.p;

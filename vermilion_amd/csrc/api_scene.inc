@@ -22,36 +22,63 @@ int vmx_scene_create(const float *pos, const float *nrm, const float *uv, uint32
     return vmx_scene_create_ex(pos, nrm, uv, ntris, spheres, nspheres, leaf_size, VMX_BVH_REFERENCE, device, out);
 }
 
-// the device records of a host-built tree, into `geom` (inner records, then the triangle records) and `attrs`
-static int upload_records(const HostBvh &b, DevBuf<unsigned char> &geom, DevBuf<AttrRecord> &attrs) {
-    const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
-    const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
-    // + 64: the quad-cooperative fetch reads 64 bytes from a 48-byte triangle record's start
-    if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "scene too large for 32-bit record offsets");
-    if (geom.ensure(inner_bytes + tri_bytes + 64) || attrs.ensure(b.attrs.size()))
+// Where the records of a host-built scene lie in its ONE allocation (d_geom): the tree's inner records, its triangle
+// records and 64 bytes of slack (the quad-cooperative fetch reads 64 bytes from a 48-byte triangle record's start); then,
+// for a reference-tree scene with a guide (guide_walk.h), 64-byte aligned, the guide's records in the same shape with the
+// same slack.  Offsets of the tree's own records do not depend on the guide.  guide_off = 0: no room is laid out for a
+// guide — there is none, or the two trees together pass what a 32-bit record offset reaches (the scene then renders
+// without one).  fits = false: the tree alone does.
+struct GeomLayout {
+    size_t inner_bytes, tri_bytes;              // the tree's records: [0, inner_bytes), then tri_bytes from there
+    size_t guide_off, guide_inner_bytes, guide_tri_bytes;
+    size_t total;                               // bytes of the allocation
+    bool fits;
+};
+static GeomLayout geom_layout(size_t n_inner, size_t n_tris, bool guide, size_t guide_n_inner, size_t guide_n_tris) {
+    GeomLayout l{};
+    l.inner_bytes = std::max<size_t>(n_inner, 1) * sizeof(InnerRecord);
+    l.tri_bytes = n_tris * sizeof(TriRecord);
+    l.total = l.inner_bytes + l.tri_bytes + 64;
+    l.fits = l.total <= 0xFFFFFFFFull;
+    if (guide && l.fits) {
+        const size_t off = (l.total + 63) & ~(size_t)63;
+        const size_t gi = std::max<size_t>(guide_n_inner, 1) * sizeof(InnerRecord), gt = guide_n_tris * sizeof(TriRecord);
+        if (off + gi + gt + 64 <= 0xFFFFFFFFull)
+            l.guide_off = off, l.guide_inner_bytes = gi, l.guide_tri_bytes = gt, l.total = off + gi + gt + 64;
+    }
+    return l;
+}
+
+// the device records of a host-built tree, into `geom` (geom_layout; with room for `guide`'s records, which upload_guide
+// writes) and `attrs`
+static int upload_records(const HostBvh &b, const HostBvh *guide, DevBuf<unsigned char> &geom, DevBuf<AttrRecord> &attrs) {
+    const GeomLayout l = geom_layout(b.inner.size(), b.tris.size(), guide != nullptr, guide ? guide->inner.size() : 0,
+                                     guide ? guide->tris.size() : 0);
+    if (!l.fits) return fail(VMX_ERR_INVALID, "scene too large for 32-bit record offsets");
+    if (geom.ensure(l.total) || attrs.ensure(b.attrs.size()))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
-    HIP_TRY(hipMemset(geom.p, 0, inner_bytes + tri_bytes + 64));
+    HIP_TRY(hipMemset(geom.p, 0, l.total));
     if (b.inner.size()) HIP_TRY(hipMemcpy(geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(geom.p + l.inner_bytes, b.tris.data(), l.tri_bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(attrs.p, b.attrs.data(), b.attrs.size() * sizeof(AttrRecord), hipMemcpyHostToDevice));
     return VMX_OK;
 }
 
-// the guide's records (guide_walk.h) into an allocation of their own, in the upload_records shape
+// the guide's records (guide_walk.h) into the room upload_records left for them behind the records of sc->bvh in
+// sc->d_geom (the same geom_layout of the same two trees; an allocation without that room: no guide)
 static int upload_guide(vmx_scene *sc) {
     vmx_scene::Guide &g = sc->guide;
-    g.valid = false;
-    if (!g.host) return VMX_OK;
+    g.valid = false, g.base = nullptr, g.off = 0, g.bytes = 0;
+    if (!g.host || sc->device_built) return VMX_OK;
     const HostBvh &b = *g.host;
-    const size_t inner_bytes = std::max<size_t>(b.inner.size(), 1) * sizeof(InnerRecord);
-    const size_t tri_bytes = b.tris.size() * sizeof(TriRecord);
-    if (inner_bytes + tri_bytes + 64 > 0xFFFFFFFFull) return VMX_OK;  // (no guide: the scene renders as before)
-    if (g.geom.ensure(inner_bytes + tri_bytes + 64)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the guide tree");
-    HIP_TRY(hipMemset(g.geom.p, 0, inner_bytes + tri_bytes + 64));
-    if (b.inner.size()) HIP_TRY(hipMemcpy(g.geom.p, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.geom.p + inner_bytes, b.tris.data(), tri_bytes, hipMemcpyHostToDevice));
-    g.bytes = b.inner.size() * sizeof(InnerRecord) + tri_bytes;
-    g.tri_off = (uint32_t)inner_bytes, g.root_ref = b.root_ref, g.stack_entries = b.max_depth + 2;
+    const GeomLayout l = geom_layout(sc->bvh.inner.size(), sc->bvh.tris.size(), true, b.inner.size(), b.tris.size());
+    if (!l.guide_off || sc->d_geom.n < l.total) return VMX_OK;  // (no guide: the scene renders as before)
+    unsigned char *at = sc->d_geom.p + l.guide_off;
+    if (b.inner.size()) HIP_TRY(hipMemcpy(at, b.inner.data(), b.inner.size() * sizeof(InnerRecord), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(at + l.guide_inner_bytes, b.tris.data(), l.guide_tri_bytes, hipMemcpyHostToDevice));
+    g.base = at, g.off = (uint32_t)l.guide_off;
+    g.bytes = b.inner.size() * sizeof(InnerRecord) + l.guide_tri_bytes;
+    g.tri_off = (uint32_t)l.guide_inner_bytes, g.root_ref = b.root_ref, g.stack_entries = b.max_depth + 2;
     g.valid = true;
     return VMX_OK;
 }
@@ -102,12 +129,11 @@ static bool host_build_trees(uint32_t builder, const float *pos, const float *nr
     return built;
 }
 
-// after a host REBUILD (sc->bvh is the new tree, nothing in flight reads the old records): the guide that was built
-// beside it, as a fresh scene would have it, or none.  A REFIT only marks the guide stale.
+// after a host REBUILD (sc->bvh is the new tree and sc->d_geom its allocation, laid out with room for t.guide; nothing in
+// flight reads the old records): the guide that was built beside it, as a fresh scene would have it, or none.  A REFIT
+// only marks the guide stale.
 static int apply_guide(vmx_scene *sc, const HostTrees &t) {
     vmx_scene::Guide &g = sc->guide;
-    g.valid = false, g.bytes = 0;
-    g.geom = DevBuf<unsigned char>();
     g.host = t.guide, g.scene_max = t.scene_max;
     return upload_guide(sc);
 }
@@ -172,7 +198,7 @@ static int scene_upload(vmx_scene *sc) {
         if (sd[i].flags & 1u) sc->dev.emit_prefix = (uint32_t)i + 1;
     sc->dev.ntris = sc->ntris;
     if (!sc->device_built)
-        if (int rc = upload_records(sc->bvh, sc->d_geom, sc->d_attrs)) return rc;
+        if (int rc = upload_records(sc->bvh, sc->guide.host.get(), sc->d_geom, sc->d_attrs)) return rc;
     if (int rc = upload_guide(sc)) return rc;
     bind_records(sc);
     return VMX_OK;
@@ -354,7 +380,7 @@ int vmx_scene_describe(const vmx_scene *sc, vmx_scene_desc *out) {
     out->device_bytes = (size_t)sc->n_inner * sizeof(InnerRecord) + (size_t)sc->ntris * sizeof(TriRecord) +
                         (size_t)sc->ntris * sizeof(AttrRecord) + sc->spheres.size() * sizeof(SphereDev) +
                         (sc->device_built ? sc->lbvh.arena_bytes : 0) +  // device-built trees keep their hierarchy arrays
-                        (sc->guide.geom.p ? sc->guide.bytes : 0);           // a reference-tree scene's guide (guide_walk.h)
+                        (sc->guide.base ? sc->guide.bytes : 0);             // a reference-tree scene's guide (guide_walk.h)
     out->device = sc->device;
     return VMX_OK;
 }

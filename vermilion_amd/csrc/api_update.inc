@@ -94,7 +94,7 @@ void rebuilt(vmx_scene *sc) {
     bind_records(sc);  // stack_entries, block; the render workspace's overflow stacks follow in bind_stack, the query
                        // workspace in ensure_query_ws
     sc->upd.plan_ready = false, sc->upd.refitted = false;
-    sc->guide.valid = false;
+    sc->guide.valid = false, sc->guide.base = nullptr, sc->guide.off = 0, sc->guide.bytes = 0;  // (its records went with the old allocation)
     sc->flat_topology = !sc->device_built;
     sc->flat_ready.store(!sc->device_built, std::memory_order_release);
 }
@@ -129,10 +129,11 @@ int host_rebuild_tree(vmx_scene *sc, const float *pos, const float *nrm, const f
 
 // swaps a host-built tree in: new buffers, uploaded, then the old ones freed.  The caller has synchronised `s` after
 // update_wait, so nothing in flight reads the old records.
-int host_apply_tree(vmx_scene *sc, const HostBvh &b, hipStream_t s) {
+// (guide: the guide built beside it or NULL — the allocation gets room for its records, which apply_guide then writes)
+int host_apply_tree(vmx_scene *sc, const HostBvh &b, const HostBvh *guide, hipStream_t s) {
     DevBuf<unsigned char> geom;
     DevBuf<AttrRecord> attrs;
-    if (int rc = upload_records(b, geom, attrs)) return rc;
+    if (int rc = upload_records(b, guide, geom, attrs)) return rc;
     sc->d_geom = std::move(geom), sc->d_attrs = std::move(attrs);
     sc->bvh = b;
     rebuilt(sc);
@@ -186,7 +187,7 @@ int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *
             if (int rc = host_rebuild_tree(sc, pos, nrm, uv, own)) return rc;
             tree = &own;
         }
-        if (int rc = host_apply_tree(sc, tree->tree, s)) return rc;
+        if (int rc = host_apply_tree(sc, tree->tree, tree->guide.get(), s)) return rc;
         if (int rc = apply_guide(sc, *tree)) return rc;  // (the guide of the new positions, built beside the tree)
         vertex_bounds(sc, pos);
         HIP_TRY(hipStreamSynchronize(s));

@@ -1,15 +1,24 @@
 // guide_walk.h — "the reference's tree returns exactly this (t, slot) for this bounce ray", decided per ray after a
 // nearest-hit walk over ANOTHER hierarchy of the same triangles (the guide: the binned-SAH tree of bvh_build.cpp).
 //
-// Plain float C++ for host and device, compiled with -ffp-contract=off on both sides, like pixel_claim.h: the GUIDE form
-// of k_trace_w<1> (vmx_kernels.hip) and the stand-alone host program tests/cpp/guide_walk_test.cpp run the same
-// arithmetic.  eps = 2^-24 below.
+// Plain float C++ for host and device, compiled with -ffp-contract=off on both sides, like pixel_claim.h: the GUIDE forms
+// of k_trace_w<1> and of k_paths (vmx_kernels.hip) and the stand-alone host program tests/cpp/guide_walk_test.cpp run
+// the same arithmetic.  eps = 2^-24 below.
+//
+// Who runs the walk.  k_trace_w<1, .., GUIDE>: the bounce generations of a split pass; every ray of the launch walks the
+// guide, the rule runs at the refill, and the fallback rays go to a list that the unchanged kernel traces in a second
+// launch.  k_paths<false, .., GuidePathsDev> (the fused kernel: the tail of a split pass, the passes of pipeline form 1,
+// the small passes of form 0): a ray of any depth that passes gw_ray_ok, camera rays included — the rule does not ask
+// where a ray comes from — walks the guide, whose records lie behind the reference's in the same allocation; the rule
+// runs for the wave's finished guide lanes before they are shaded, and a fallback ray starts again over the reference
+// tree in its own lane (ray_start with the reference's root, the reference's own prune), so one wave holds lanes on
+// either tree.  A ray that fails gw_ray_ok starts on the reference tree in both kernels.
 //
 // Contract of gw_settle: whenever it returns true for a ray that finished the guide walk with (best, winner), then
 // BVH::getIntersection (bvh.cpp:47-145) over the REFERENCE tree returns the winner's triangle with t = best, bit for bit;
 // a guide walk that ends with no hit means the reference returns no hit.  Every other ray is a fallback ray: it is
-// traced over the reference tree by the unchanged kernel.  A rule that settles nothing is sound; tests/test_guide_walk.py
-// holds both the soundness (0 wrong rays) and the share.
+// traced over the reference tree (by the unchanged kernel, or in its lane of the fused one).  A rule that settles nothing
+// is sound; tests/test_guide_walk.py holds both the soundness (0 wrong rays) and the share.
 //
 // The guide walk (gw_walk here; the GUIDE step of k_trace_w<1>) is the step of k_trace_w<1> over the guide's records —
 // nearer child first, one triangle per step, tri_test untouched, so a triangle's t has the bits the reference computes —

@@ -166,6 +166,7 @@ struct Workspace {
     // which the second launch reads on the device) and the frame's (settled, fallback) ray counts
     DevBuf<unsigned int> guide_fb, guide_fb_count, guide_heads;
     DevBuf<unsigned long long> guide_ctr;
+    DevBuf<unsigned long long> guide_fused_ctr;  // k_paths<.., GuidePathsDev>: the frame's (settled, reference-tree) ray counts
     uint64_t guide_entries = 0;  // entries of the bounce lists handed to the GUIDE launches of the call in progress (host count)
     PixelBufs pixels;                   // vmx_render's frames (a vmx_progressive handle owns its own); active[0]: BruteForceTracer's pixel order
     DevBuf<unsigned int> next_count;
@@ -213,13 +214,16 @@ struct vmx_scene {
     uint64_t list_settled = 0;  // ... and its camera rays that a list claim settled (vmx_list_settled_rays)
     uint64_t guide_settled = 0, guide_fallback = 0;  // ... and its bounce rays that walked the guide (vmx_guide_rays)
     uint64_t guide_entries = 0;  // ... and the entries of the lists its GUIDE launches were handed (vmx_guide_list_entries)
-    // the guide of a VMX_BVH_REFERENCE scene (guide_walk.h): the binned-SAH tree of the same triangles, its records in an
-    // allocation of their own (the upload_records shape: inner records, then the triangle records); no attribute table.
-    // `host` is the one host build the replicas of a vmx_multi share.  Stale after any update that moves vertices or
-    // rebuilds: then it is not used (refitting it is a follow-up).
+    uint64_t guide_fused_settled = 0, guide_fused_fallback = 0;  // ... and the rays of its fused launches' GUIDE forms (vmx_guide_fused_rays)
+    // the guide of a VMX_BVH_REFERENCE scene (guide_walk.h): the binned-SAH tree of the same triangles, its records in
+    // d_geom behind the reference's (geom_layout: `off` bytes from d_geom.p, in the upload_records shape: inner records,
+    // then the triangle records), so that a lane of the fused kernel addresses either tree with a 32-bit offset from
+    // dev.inner; no attribute table.  `host` is the one host build the replicas of a vmx_multi share.  Stale after any
+    // update that moves vertices or rebuilds: then it is not used (refitting it is a follow-up).
     struct VMX_OPAQUE Guide {
         std::shared_ptr<const HostBvh> host;
-        DevBuf<unsigned char> geom;
+        const unsigned char *base = nullptr;  // d_geom.p + off, or NULL: d_geom has no room for a guide
+        uint32_t off = 0;
         size_t bytes = 0;
         uint32_t tri_off = 0, root_ref = 0, stack_entries = 0;
         float scene_max = 0.f;

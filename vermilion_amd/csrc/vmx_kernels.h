@@ -123,6 +123,17 @@ struct GuideDev {
     DevCounters *overflow;    // the frame's counters: a fallback entry that does not fit is reported (DevCounters::overflow)
 };
 
+// ... and as the GUIDE forms of the fused kernel read it (k_paths<.., GuidePathsDev>): the guide's records lie in the scene's own
+// record allocation, behind the reference's, so a lane addresses either tree with a 32-bit offset from SceneDev::inner
+struct GuidePathsDev {
+    uint32_t off;             // the guide's InnerRecord[]: bytes from SceneDev::inner (a multiple of 64, never 0)
+    uint32_t tri_off;         // its TriRecord[]: bytes from SceneDev::inner; pad[0] = reference leaf slot
+    uint32_t root_ref;
+    float scene_max;
+    unsigned long long *ctr;  // [0] rays settled by the guide, [1] rays traced over the reference tree: the rule's
+                              // fallbacks and the rays that never walked the guide
+};
+
 // explicit ray batch of k_query (vmx_query.inc): device pointers, any output may be NULL
 struct QueryDev {
     const float *o, *d;     // [n*3] origins / directions
@@ -206,9 +217,11 @@ int query_trace_pool(uint32_t block, uint32_t pool_slots, uint32_t lds_levels, u
 #endif
 // per-pixel accumulation in sample order, early-stop rule, pixel write, next active list
 // persistent fused kernel with per-lane refill (ray generation source): every lane keeps its path to the end
+// (guide: the GUIDE form, k_paths<false, .., GuidePathsDev>, which launch_paths / launch_tail launch when they are handed a guide and do not
+// count; query_paths_blocks_per_cu then reports that form's occupancy)
 int launch_paths(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, void *rad,
-                 DevCounters *counters, bool count, LaunchCfg cfg, void *stream);
-int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, int *blocks);
+                 DevCounters *counters, bool count, LaunchCfg cfg, void *stream, const GuidePathsDev *guide = nullptr);
+int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, int *blocks, bool guide = false);
 // split wavefront: persistent trace kernel (per-lane refill) ...
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
                          void *cam_tris, void *stream);
@@ -240,7 +253,7 @@ int launch_shade_ends(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk,
                       unsigned int *full_cnt, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream);
 // follows every queued path (ids) to its end in one launch
 int launch_tail(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathArrays pa, DevCounters *counters,
-                bool count, LaunchCfg cfg, void *stream);
+                bool count, LaunchCfg cfg, void *stream, const GuidePathsDev *guide = nullptr);
 int launch_radiance_init_ids(const float *o, const float *d, uint32_t n, uint64_t seed, PathArrays pa,
                              IdQueue qout, void *stream);
 int launch_resolve(const FrameDev &fr, const unsigned int *active, uint32_t n_active, uint32_t samples,

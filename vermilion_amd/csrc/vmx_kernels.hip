@@ -1471,10 +1471,26 @@ __device__ __forceinline__ uint2 stack_pop(const uint2 *stk, const uint2 *ovf, i
 #ifndef VMX_PATHS_WPS
 #define VMX_PATHS_WPS 6  // waves per SIMD the fused kernel is compiled for (80 VGPRs): tail 8.8 -> 7.9 ms, early-stop frame 14.3 -> 13.8 ms (5: 8.1, 7: 8.4, 8: 8.9)
 #endif
-template <bool COUNT, int SRC, bool TEX>
+// GUIDE (COUNT false; a reference-tree scene with a valid guide, guide_walk.h): a ray of any depth that passes gw_ray_ok
+// walks the GUIDE's records, which lie in the scene's own record allocation gd.off bytes behind sc.inner, so a lane's
+// tree is one 32-bit offset (`toff`) folded into its record offset and guide lanes and reference lanes share a wave.  The
+// step is the GUIDE step of k_trace_w<1>: the prune on near > cut = best (1 + kGwKappa) in the child choice and in the
+// pop, `second` kept; a reference lane keeps cut == best, so the step has no branch on the tree.  A finished guide walk
+// waits for shading like any finished ray; there, before the wave shades, the rule (gw_settle, one 48-byte fetch of the
+// winner's guide record) runs for the wave's finished guide lanes together: a settled lane takes the winner's REFERENCE
+// slot and is shaded, the others start the same ray again over the reference tree, in the lane, and are shaded when
+// that walk ends.  A ray that fails gw_ray_ok starts on the reference tree, so the NaN-exact box form meets guide records
+// only in finite lanes of a mixed wave, where both box forms agree (guide_walk.h).
+// (the form's one extra kernel argument, a GuidePathsDev, is the pack G: the other instantiations keep their signature)
+__device__ __forceinline__ GuidePathsDev guide_arg() { return GuidePathsDev{}; }
+__device__ __forceinline__ GuidePathsDev guide_arg(GuidePathsDev g) { return g; }
+template <bool COUNT, int SRC, bool TEX, class... G>
 __global__ void __launch_bounds__(256, VMX_PATHS_WPS)
 k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restrict__ rad, PathArrays pa,
-        DevCounters *ctr) {
+        DevCounters *ctr, G... guide) {
+    constexpr bool GUIDE = sizeof...(G) != 0;
+    static_assert(!GUIDE || !COUNT, "the counting build's visits are the reference tree's");
+    const GuidePathsDev gd = guide_arg(guide...);
     extern __shared__ uint2 lds_stack[];
     __shared__ float4 s_geom[kLdsSpheres];  // spheres' (centre, rad*rad): read by every RayCast
     if (threadIdx.x < min(sc.nspheres, kLdsSpheres)) {
@@ -1506,11 +1522,26 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
     stk[0] = make_uint2(kBottom, 0xFF800000u);
     Cnt c0 = {0, 0}, c1 = {0, 0};
     Tally tl = {{0, 0}, {0, 0}, {0, 0}};
+    // GUIDE: the prune bound, the smallest accepted distance of any triangle but the nearest (guide_walk.h) and the byte
+    // offset of the lane's tree from sc.inner (0: the reference tree; gd.off: the guide, and `slot` is a guide slot)
+    float cut = 0.f, second = 0.f;
+    uint32_t toff = 0;
+    uint32_t n_settled = 0, n_fallback = 0;  // (wave-uniform)
 
-    auto start_traversal = [&]() {
+    // returns false for a ray that may not walk the guide (GUIDE only): it starts on the reference tree
+    auto start_traversal = [&]() -> bool {
         ray_start(P.dx, P.dy, P.dz, sc.root_ref, 999999999.f, ix, iy, iz, best, slot, sp, cur);
         exact = !(finite3(ix, iy, iz) && finite3(P.ox, P.oy, P.oz));
         is_ray = (P.depth == 0) || finite3(P.dx, P.dy, P.dz);
+        if (GUIDE) {
+            const bool walks = gw_ray_ok(P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, ix, iy, iz, gd.scene_max);
+            cur = walks ? gd.root_ref : cur;
+            toff = walks ? gd.off : 0u;
+            cut = walks ? best * kGwCut : best;
+            second = 3.0e38f;
+            return walks;
+        }
+        return true;
     };
 
     for (;;) {
@@ -1519,6 +1550,33 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
             const unsigned long long fin = __builtin_amdgcn_ballot_w64(has && cur == kIdle);
             const unsigned long long trav = __builtin_amdgcn_ballot_w64(cur != kIdle);
             if (fin != 0 && ((uint32_t)__popcll(fin) >= wk.shade_min || trav == 0)) {
+                if (GUIDE) {
+                    // the rule for the finished guide walks among them: settled -> the reference slot, shaded below;
+                    // not settled -> the same ray over the reference tree, with the reference's own prune (cut == best)
+                    const bool walked = has && cur == kIdle && toff != 0;
+                    bool fb = false;
+                    if (walked) {
+                        const bool have = slot >= 0;
+                        float r[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                        int ref_slot = -1;
+                        if (have) {
+                            const float4 *rec = (const float4 *)((const char *)inner + (gd.tri_off + (uint32_t)slot * 48u));
+                            const float4 a = rec[0], b = rec[1], c = rec[2];
+                            r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w, r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w, r[8] = c.x;
+                            ref_slot = __float_as_int(c.z);  // TriRecord::pad[0]: the triangle's leaf slot in the reference tree
+                        }
+                        const float o[3] = {P.ox, P.oy, P.oz}, d[3] = {P.dx, P.dy, P.dz}, inv[3] = {ix, iy, iz};
+                        toff = 0;
+                        if (gw_settle(have, r, best, second, o, d, inv, gd.scene_max)) {
+                            slot = ref_slot;
+                        } else {
+                            fb = true;
+                            best = cut = 999999999.f, slot = -1, sp = 1, cur = sc.root_ref;
+                        }
+                    }
+                    n_settled += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(walked && !fb));
+                    n_fallback += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(fb));
+                }
                 const bool shaded = has && cur == kIdle;
                 bool alive = false;
                 StepFlags fl = {false, false, false};
@@ -1537,7 +1595,9 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                     }
                 }
                 tally_add(tl, fl, shaded, depth0);
-                if (shaded && alive) start_traversal();  // the lane keeps its path to the end
+                bool unwalked = false;  // GUIDE: the lane's next ray never walks the guide (counted with the fallback rays)
+                if (shaded && alive) unwalked = !start_traversal();  // the lane keeps its path to the end
+                if (GUIDE) n_fallback += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(unwalked));
             }
         }
         // ---- 2. refill idle lanes from the work source ---------------------------
@@ -1569,6 +1629,7 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                     const bool take = !has && rank < avail;
                     const uint32_t item = res_lo + rank;
                     res_lo += min((uint32_t)__popcll(want), avail);
+                    bool unwalked = false;  // (GUIDE, as above)
                     if (take) {
                         bool valid = true;
                         if (SRC == 0) {
@@ -1603,9 +1664,10 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                         }
                         if (valid) {
                             has = true;
-                            start_traversal();
+                            unwalked = !start_traversal();
                         }
                     }
+                    if (GUIDE) n_fallback += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(unwalked));
                 }
             }
         }
@@ -1621,9 +1683,11 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
             // the node or triangle record of every traversing lane, fetched quad-cooperatively in one phase
             // (quad_fetch_record; inner and triangle records share one allocation, SceneDev::tri_off)
             float4 q0, q1, q2, q3;
+            // (GUIDE: a guide lane's records lie toff bytes on, its triangle records at gd.tri_off)
             quad_fetch_record((const char *)inner,
                               cur >= kPop && (int)cur >= 0 ? 0u
-                              : ((int)cur < 0 ? sc.tri_off + (cur & kLeafStartMask) * 48u : (cur << 6)),
+                              : ((int)cur < 0 ? (GUIDE && toff != 0 ? gd.tri_off : sc.tri_off) + (cur & kLeafStartMask) * 48u
+                                              : (GUIDE ? toff + (cur << 6) : (cur << 6))),
                               lane, q0, q1, q2, q3);
             if (cur < kPop) {
                 if (COUNT) {
@@ -1632,7 +1696,7 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                 }
                 float tn0, tf0, tn1, tf1;
                 child_boxes<EXACT>(q0, q1, q2, P.ox, P.oy, P.oz, ix, iy, iz, tn0, tf0, tn1, tf1);
-                cur = choose_child_masks(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), best, push);
+                cur = choose_child_masks(tn0, tf0, tn1, tf1, __float_as_uint(q3.x), __float_as_uint(q3.y), GUIDE ? cut : best, push);
             } else if ((int)cur < 0) {
                 // one triangle (triangle.cpp:4-54); the leaf ref itself carries the progress
                 if (COUNT) {
@@ -1642,14 +1706,17 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
                 float dist;
                 const bool hit = tri_test(q0, q1, q2.x, P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, dist);
                 if (hit && dist < best) {  // strict <: first tested wins ties (bvh.cpp:90)
+                    if (GUIDE) second = best, cut = toff != 0 ? dist * kGwCut : dist;
                     best = dist;
                     slot = (int)(cur & kLeafStartMask);
+                } else if (GUIDE && hit) {
+                    second = fminf(second, dist);
                 }
                 cur = leaf_advance(cur);
             }
             if (cur == kPop) {
                 // the bottom entry ends the traversal: the lane then waits for shading
-                const uint32_t ref = pop_to_next(stk, ovf, lds_entries, sp, best);
+                const uint32_t ref = pop_to_next(stk, ovf, lds_entries, sp, GUIDE ? cut : best);
                 cur = ref == kBottom ? kIdle : ref;
             }
         };
@@ -1662,7 +1729,12 @@ k_paths(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, float4 *__restri
         }
     }
     tally_flush<COUNT>(ctr, tl, c0, c1);
+    if (GUIDE && lane == 0) {
+        if (n_settled) atomicAdd(&gd.ctr[0], (unsigned long long)n_settled);
+        if (n_fallback) atomicAdd(&gd.ctr[1], (unsigned long long)n_fallback);
+    }
 }
+
 
 
 
@@ -3780,13 +3852,16 @@ int launch_zero_u32(unsigned int *p, uint32_t n, void *stream) {
 }
 
 int launch_paths(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, void *rad,
-                 DevCounters *counters, bool count, LaunchCfg cfg, void *stream) {
+                 DevCounters *counters, bool count, LaunchCfg cfg, void *stream, const GuidePathsDev *guide) {
     hipStream_t s = (hipStream_t)stream;
     dim3 g(cfg.grid), b(cfg.block);
 #define VMX_GO(C, T) \
     hipLaunchKernelGGL((k_paths<C, 0, T>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)rad, pa, counters)
     PathArrays pa{};
-    if (sc.tex) {
+    if (guide && guide->off && !count) {
+        if (sc.tex) hipLaunchKernelGGL((k_paths<false, 0, true, GuidePathsDev>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)rad, pa, counters, *guide);
+        else hipLaunchKernelGGL((k_paths<false, 0, false, GuidePathsDev>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)rad, pa, counters, *guide);
+    } else if (sc.tex) {
         if (count) VMX_GO(true, true);
         else VMX_GO(false, true);
     } else {
@@ -3798,13 +3873,16 @@ int launch_paths(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
 }
 
 int launch_tail(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathArrays pa, DevCounters *counters,
-                bool count, LaunchCfg cfg, void *stream) {
+                bool count, LaunchCfg cfg, void *stream, const GuidePathsDev *guide) {
     hipStream_t s = (hipStream_t)stream;
     dim3 g(cfg.grid), b(cfg.block);
     PixelStateDev px{nullptr, nullptr, nullptr};
 #define VMX_GO(C, T) \
     hipLaunchKernelGGL((k_paths<C, 2, T>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)pa.rad, pa, counters)
-    if (sc.tex) {
+    if (guide && guide->off && !count) {
+        if (sc.tex) hipLaunchKernelGGL((k_paths<false, 2, true, GuidePathsDev>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)pa.rad, pa, counters, *guide);
+        else hipLaunchKernelGGL((k_paths<false, 2, false, GuidePathsDev>), g, b, cfg.lds_bytes, s, sc, fr, wk, px, (float4 *)pa.rad, pa, counters, *guide);
+    } else if (sc.tex) {
         if (count) VMX_GO(true, true);
         else VMX_GO(false, true);
     } else {
@@ -3987,10 +4065,13 @@ int launch_radiance_init_ids(const float *o, const float *d, uint32_t n, uint64_
     return launch_status();
 }
 
-int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, int *blocks) {
+int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, int *blocks, bool guide) {
     int a = 0, b = 0;
     hipError_t e;
-    if (count) {
+    if (guide && !count) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_paths<false, 0, true, GuidePathsDev>, (int)block, lds_bytes);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_paths<false, 2, true, GuidePathsDev>, (int)block, lds_bytes);
+    } else if (count) {
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_paths<true, 0, true>, (int)block, lds_bytes);
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_paths<true, 2, true>, (int)block, lds_bytes);
     } else {

@@ -622,6 +622,12 @@ class Scene:
         self._check(self._lib.vmx_guide_rays(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def guide_fused_rays(self):
+        """vmx_guide_fused_rays: (settled, fallback) traversals of the last render's fused launches, whose rays walk the guide tree"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.vmx_guide_fused_rays(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def guide_list_entries(self):
         """vmx_guide_list_entries: entries of the bounce lists the last render handed to the guide form of the trace kernel"""
         n = C.c_uint64(0)
