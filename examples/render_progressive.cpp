@@ -7,6 +7,12 @@
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_progressive     (done by __graft_entry__.build())
 //   ./examples/render_progressive out.ppm 256 256 64 [seed [samples_per_step [frame.f32]]]
 //
+//   ./examples/render_progressive --adaptive out.ppm 256 256 16 [seed [samples_per_step [frame.f32]]]
+//     adaptive sampling: a handle with four times the given spp as its ceiling (fixed spp, VMX_PROGRESSIVE_MOMENTS) takes 8
+//     uniform samples, then vmx_progressive_step_adaptive of samples_per_step (default 4) — only the pixels whose mean is
+//     still uncertain, by the library's default parameters — until the mean count per pixel reaches the given spp or
+//     nothing is selected any more, and the final PREVIEW is written: unfinished pixels show the mean of their own samples.
+//
 // Writes the last preview's rgba8 form as a binary PPM (Camera::saveFrame's quantisation, done on the device) and,
 // if a third file name is given, the RGBAZ floats of the frame as they are.
 #include <cmath>
@@ -36,6 +42,13 @@ void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &
 }  // namespace
 
 int main(int argc, char **argv) {
+    bool adaptive = false;
+    for (int i = 1; i < argc; ++i)
+        if (!std::strcmp(argv[i], "--adaptive")) {
+            adaptive = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            --argc, --i;
+        }
     const char *out = argc > 1 ? argv[1] : "cornell.ppm";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 64;
@@ -65,14 +78,14 @@ int main(int argc, char **argv) {
     cam.back_distance = 6.0f;  // renderEngine.cpp:135
     cam.back_size[0] = 3.6f, cam.back_size[1] = 3.6f * (float)H / (float)W;
     cam.image_res[0] = W, cam.image_res[1] = H;
-    cam.rays_per_pixel = spp;
+    cam.rays_per_pixel = adaptive ? 4 * spp : spp;  // (adaptive: the ceiling of a pixel's count; the mean ends at spp)
     vmx_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.seed = seed;
-    opts.early_stop = 1;
+    opts.early_stop = adaptive ? 0 : 1;  // (selected steps need the fixed-spp schedule)
     opts.sampling = VMX_SAMPLING_PARITY;
     vmx_progressive *job = nullptr;
-    if (vmx_progressive_begin(scene, &cam, &opts, nullptr, &job) != VMX_OK) {
+    if (vmx_progressive_begin_ex(scene, &cam, &opts, adaptive ? VMX_PROGRESSIVE_MOMENTS : 0u, nullptr, &job) != VMX_OK) {
         std::fprintf(stderr, "begin: %s\n", vmx_last_error());
         vmx_scene_destroy(scene);
         return 1;
@@ -82,9 +95,18 @@ int main(int argc, char **argv) {
     vmx_progressive_info info;
     double ms = 0;
     int rc = vmx_progressive_info_get(job, &info);
-    while (rc == VMX_OK && info.pixels_active > 0) {
+    const uint64_t target = (uint64_t)spp * W * H;  // (adaptive: the samples of a uniform frame at the given spp)
+    while (rc == VMX_OK && info.pixels_active > 0 && !(adaptive && info.samples >= target)) {
         vmx_stats st;
-        if ((rc = vmx_progressive_step(job, per_step, &st)) != VMX_OK) break;
+        if (adaptive && info.steps > 0) {
+            uint32_t selected = 0;
+            if ((rc = vmx_progressive_step_adaptive(job, per_step, nullptr, &st, &selected)) != VMX_OK) break;
+            if (selected == 0) {  // every pixel is below the threshold: more steps would select nothing either
+                std::printf("converged: no pixel selected\n");
+                break;
+            }
+            std::printf("selected %u pixels; ", selected);
+        } else if ((rc = vmx_progressive_step(job, adaptive ? 8u : per_step, &st)) != VMX_OK) break;
         if ((rc = vmx_progressive_preview(job, frame.data(), rgba.data())) != VMX_OK) break;  // what a viewer would show
         if ((rc = vmx_progressive_info_get(job, &info)) != VMX_OK) break;
         ms += st.ms_device;

@@ -776,8 +776,9 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
  * is refused (VMX_ERR_INVALID, "... VMX_TEMPORAL_MOMENTS ..."); on a moments handle the two calls above are
  * VMX_ERR_INVALID, because they would leave the moments stale.  Reset and frames work on both kinds of handle.
  * tests/variance_spec.py restates it; the kernels hold to it bit for bit.
- * Out of scope: the progressive previews (a vmx_progressive handle keeps no second moment), the analytic spheres'
- * motion, and a variance output of the filter. */
+ * A progressive preview gets its variance plane from the handle itself: vmx_progressive_error_device on a
+ * VMX_PROGRESSIVE_MOMENTS handle (the adaptive sampling section below) writes d_variance in this layout.
+ * Out of scope: the analytic spheres' motion, and a variance output of the filter. */
 #define VMX_TEMPORAL_MOMENTS 1u
 typedef struct vmx_variance_params {
     float min_history;         /* finite, >= 1; default 4.f                       */
@@ -987,6 +988,78 @@ int vmx_multi_render_device(vmx_multi *m, const vmx_camera *cam, const vmx_opts 
                             vmx_stats *stats);
 int vmx_multi_render_bruteforce(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags,
                                 float *out_rgbaz, vmx_stats *stats);
+
+/* ---- adaptive sampling: progressive steps that trace only the unconverged pixels ---------------------------------
+ * vmx_progressive_step gives every active pixel the same samples.  The entries below let a step take samples for a
+ * subset of the pixels, keep the second moment from which to choose that subset, and choose it.  Sample k of local pixel
+ * p is what it always was, keyed (seed, p, k), and a pixel's samples are folded in its own order: whatever the steps and
+ * maps, a handle that is run to completion holds vmx_render's frame, bit for bit.
+ *
+ * begin_ex: flags 0 is vmx_progressive_begin exactly; VMX_PROGRESSIVE_MOMENTS makes the handle keep, per pixel, the sum m2
+ *   of the squared luminance of its samples: right after the three colour adds of a taken sample s,
+ *     l = lum(s.r, s.g, s.b);  m2 = m2 + l*l         (lum as in the variance section; a black path adds an exact +0)
+ *   Sums, counts, frames and previews of a moments handle are a plain handle's, bit for bit.  Any other bit of `flags` is
+ *   VMX_ERR_INVALID.
+ * state_device: the handle's raw state per local pixel, copied on the handle's stream without synchronising: d_sums
+ *   float4 (r, g, b sums; w = m2 on a moments handle, else 0) and / or d_counts uint32; at least one must be non-NULL;
+ *   DEVICE pointers of the scene's device, 4-byte aligned, not overlapping.
+ * step_selected_device: a step in which only the pixels with d_select[p] != 0 (one byte per local pixel, a DEVICE
+ *   pointer, read during the call) take samples.  A pixel takes samples only if it is active (fewer than kmax samples so
+ *   far) and selected; it takes min(samples, kmax - its count) of them, the next ones in its own order; samples == 0 runs
+ *   the selected pixels to kmax.  Unselected pixels keep their state bit for bit and stay active.  A step with no selected
+ *   active pixel is VMX_OK, issues nothing and does not count as a step.  *selected (may be NULL) is the number of pixels
+ *   that took samples; stats and vmx_scene_timings report this step alone, stats.samples the samples folded.
+ *   Afterwards the handle is ragged — its pixels hold different counts.  vmx_progressive_step still works on it: every
+ *   active pixel takes at least one sample and at most `samples`, 0 runs everyone to kmax; pixels_active is the number of
+ *   pixels below kmax; the previews show an unfinished pixel as the clamped mean of its own n samples with depth n.
+ *   Works under rank / world / stripe_rows (maps are indexed by LOCAL pixel), VMX_SAMPLING_ELIDE_DEAD,
+ *   VMX_SAMPLING_CORRECTED and every pipeline form of the product.  A handle that never takes a selected step
+ *   schedules, renders and previews exactly as before.
+ * Error, variance and selection, per local pixel p, n = count, (sr, sg, sb, m2) = sums, fn = (float)n.  All float, one
+ * rounding per written operation, `/` and sqrtf correctly rounded, denormals kept:
+ *   n < 2:  e = 3.402823466e+38f;  var = 0.f
+ *   else:   m1 = lum(sr, sg, sb) / fn
+ *           v = m2/fn - m1*m1;  v = v > 0 ? v : 0                        (a NaN gives 0)
+ *           var = v / (fn - 1.f)                                         (the variance of the pixel's mean luminance)
+ *           e = sqrtf(var) / (fabsf(m1) + floor)
+ *   error_device: d_error[p] = e and / or d_variance[p] = var (W * rows floats each, the layout
+ *     vmx_filter_apply_variance_device reads; at least one non-NULL; 4-byte aligned, not overlapping).
+ *   select_device: d_select[p] = cursor_p < kmax && (n_p < min_samples || max over q of e_q > threshold) ? 1 : 0, q over the
+ *     (2*radius+1)^2 window around p, taps clipped to the handle's local rows and width — under world > 1 the window is
+ *     taken in the rank's packed rows and never sees another rank's pixels, so it does not cross stripe borders as the
+ *     full image would.  Comparisons with a NaN are false.  d_count (one uint32, or NULL) receives the number of selected
+ *     pixels.  d_select is one byte per local pixel and may not overlap d_count.
+ *   step_adaptive: select_device into a map the handle owns, then step_selected_device with it: the same state as the
+ *     two calls by hand.
+ * Order of checks: params, then the pointers (NULL, alignment, buffers that meet in their first element), then the handle
+ * and how it was begun, then what needs the device (pointer kinds, overlaps at the image's size), then the handle's state.  The selection entries (step_selected_device,
+ * select_device, step_adaptive) are VMX_ERR_INVALID on a handle begun with opts.early_stop == 1: the early-stop schedule
+ * assumes that all pixels advance together, and the reference's rule is a different stopping rule.  error_device,
+ * select_device and step_adaptive are VMX_ERR_INVALID on a handle begun without VMX_PROGRESSIVE_MOMENTS.
+ * Defaults (vmx_sampling_default_params): threshold 0.5f, floor 0.05f, min_samples 8, radius 1 — threshold and floor as
+ * chosen from the grid of profiles/sampling_quality.txt.  tests/sampling_spec.py restates the arithmetic.
+ * Out of scope: selection on early-stop handles, per-pixel sample budgets within one step, windows across ranks, adaptive
+ * sampling inside vmx_render and vmx_multi_*. */
+#define VMX_PROGRESSIVE_MOMENTS 1u
+int vmx_progressive_begin_ex(vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                             vmx_progressive **out);
+int vmx_progressive_state_device(vmx_progressive *p, void *d_sums /* or NULL */, void *d_counts /* or NULL */);
+int vmx_progressive_step_selected_device(vmx_progressive *p, uint32_t samples, const void *d_select, vmx_stats *stats,
+                                         uint32_t *selected /* or NULL */);
+typedef struct vmx_sampling_params {
+    float threshold;      /* finite, >= 0; default 0.5f  */
+    float floor;          /* finite, > 0;  default 0.05f */
+    uint32_t min_samples; /* >= 2;         default 8     */
+    uint32_t radius;      /* 0..3;         default 1     */
+    uint32_t reserved[4]; /* must be 0                   */
+} vmx_sampling_params;
+int vmx_sampling_default_params(vmx_sampling_params *out);
+int vmx_progressive_error_device(vmx_progressive *p, const vmx_sampling_params *params, void *d_error /* or NULL */,
+                                 void *d_variance /* or NULL */);
+int vmx_progressive_select_device(vmx_progressive *p, const vmx_sampling_params *params, void *d_select,
+                                  void *d_count /* one uint32, or NULL */);
+int vmx_progressive_step_adaptive(vmx_progressive *p, uint32_t samples, const vmx_sampling_params *params,
+                                  vmx_stats *stats, uint32_t *selected /* or NULL */);
 
 /* ---- BruteForceTracer: the engine's DEFAULT integrator --------------------
  * Replaces Vermilion::BruteForceTracer::Render (core/integrators/integrators.cpp:9-186; installed by

@@ -35,6 +35,7 @@ VMX_QUERY_COLLISION = 2
 VMX_QUERY_FETCH_PER_LANE = 0x100
 VMX_ALBEDO_FLOOR = 2.0 ** -10  # the demodulated filter's lower clamp of an albedo channel
 VMX_TEMPORAL_MOMENTS = 1  # vmx_temporal_create_ex: the handle keeps luminance moments (vmx_temporal_accumulate_variance_device)
+VMX_PROGRESSIVE_MOMENTS = 1  # vmx_progressive_begin_ex: the handle keeps the sum of squared sample luminances (adaptive sampling)
 VMX_VARIANCE_EPS = 1e-10  # the variance-guided filter's floor of sigma_luminance^2 * variance
 VMX_SIGMA_LUMINANCE_DEFAULT = 4.0
 VMX_ADAPTIVE_EPS = 1e-10  # the adaptive accumulation's floor of the window mean's squared standard error
@@ -243,6 +244,20 @@ class AdaptiveParams(C.Structure):
                 "sigma_depth": self.sigma_depth, "reserved": list(self.reserved)}
 
 
+class SamplingParams(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("floor", C.c_float),
+        ("min_samples", C.c_uint32),
+        ("radius", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+    def as_dict(self):
+        return {"threshold": self.threshold, "floor": self.floor, "min_samples": self.min_samples, "radius": self.radius,
+                "reserved": list(self.reserved)}
+
+
 class UpsampleParams(C.Structure):
     _fields_ = [
         ("normal_squarings", C.c_uint32),
@@ -298,6 +313,14 @@ SYMBOLS = {
     "vmx_progressive_preview_device": (C.c_int, [_P, _P, _P]),
     "vmx_progressive_preview": (C.c_int, [_P, _P, _P]),
     "vmx_progressive_end": (C.c_int, [_P]),
+    "vmx_progressive_begin_ex": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(_P)]),
+    "vmx_progressive_state_device": (C.c_int, [_P, _P, _P]),
+    "vmx_progressive_step_selected_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(Stats), C.POINTER(C.c_uint32)]),
+    "vmx_sampling_default_params": (C.c_int, [C.POINTER(SamplingParams)]),
+    "vmx_progressive_error_device": (C.c_int, [_P, C.POINTER(SamplingParams), _P, _P]),
+    "vmx_progressive_select_device": (C.c_int, [_P, C.POINTER(SamplingParams), _P, _P]),
+    "vmx_progressive_step_adaptive": (C.c_int, [_P, C.c_uint32, C.POINTER(SamplingParams), C.POINTER(Stats),
+                                                C.POINTER(C.c_uint32)]),
     "vmx_filter_default_params": (C.c_int, [C.POINTER(FilterParams)]),
     "vmx_filter_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "vmx_filter_destroy": (C.c_int, [_P]),

@@ -16,12 +16,33 @@ struct VMX_OPAQUE vmx_progressive {
     uint64_t generation = 0;        // the scene's when the handle began
     uint64_t samples = 0, passes = 0, steps = 0;
     bool failed = false;            // a step stopped half way: the schedule and the device state may disagree
+    // adaptive sampling (api_sampling.inc).  From the first selected step on the handle is ragged (job.ragged): `master` is
+    // the list of its active pixels in the tile order of render_init_pixels, compacted in order after every step; a step
+    // compacts it by its selection into the job's active list and runs the pass loop on that
+    DevBuf<unsigned int> master[2];
+    int cur_master = 0;
+    uint32_t n_master = 0;
+    DevBuf<unsigned long long> list_mask;   // one word of bits per 64 slots of the master list
+    DevBuf<unsigned int> list_u32;          // [popcounts | their exclusive scan | the compacted list's length]
+    DevBuf<unsigned char> list_tmp;         // scan scratch
+    size_t list_words = 0, list_tmp_bytes = 0;
+    DevBuf<unsigned char> select_map;       // vmx_progressive_step_adaptive's map, on first use
 };
 
+// a step of a ragged handle (api_sampling.inc); d_select NULL: every active pixel
+static int progressive_step_list(vmx_progressive *p, uint32_t samples, const unsigned char *d_select, vmx_stats *stats,
+                                 uint32_t *selected, std::chrono::steady_clock::time_point t0);
+
 int vmx_progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, void *stream, vmx_progressive **out) {
+    return vmx_progressive_begin_ex(sc, cam, opts, 0, stream, out);
+}
+
+int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                             vmx_progressive **out) {
     // checks that need no device, in this order so that each can be seen alone; the scene comes last
     if (!cam || !opts) return fail(VMX_ERR_INVALID, "NULL argument: cam or opts");
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
+    if (flags & ~VMX_PROGRESSIVE_MOMENTS) return fail(VMX_ERR_INVALID, "vmx_progressive_begin_ex: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)");
     {
         FrameDev fr;
         if (int rc = make_frame(*cam, *opts, fr)) return rc;
@@ -36,6 +57,7 @@ int vmx_progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *
     p->cam = *cam;
     p->generation = sc->generation;
     int rc = render_setup(sc, cam, opts, &p->pixels, nullptr, stream ? (hipStream_t)stream : sc->stream, p->job);
+    p->job.moments = (flags & VMX_PROGRESSIVE_MOMENTS) != 0;
     if (rc == VMX_OK && p->job.npix) {
         if (p->frame.ensure((size_t)p->job.npix * 5)) rc = fail(VMX_ERR_NOMEM, "hipMalloc failed for the frame buffer");
         p->job.d_out = p->frame.p;
@@ -60,6 +82,7 @@ int vmx_progressive_step(vmx_progressive *p, uint32_t samples, vmx_stats *stats)
     if (int rc = bind_device(sc)) return rc;
     if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
     if (p->failed) return fail(VMX_ERR_INVALID, "an earlier step of this handle failed: end it and begin again");
+    if (p->job.ragged) return progressive_step_list(p, samples, nullptr, stats, nullptr, t0);
     vmx_stats st;
     std::memset(&st, 0, sizeof(st));
     if (p->job.n_active > 0) {

@@ -623,6 +623,8 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
             S = (uint32_t)std::min<uint64_t>(S, ((uint64_t)n_pad_max * job.smax_alloc) / ((n_active + 63u) & ~63u));
             S = std::max(std::min(S, cap), 1u);
         }
+    } else if (job.ragged) {
+        S = std::min(smax, cap);  // (the run ends when its list is empty: render_run)
     } else {
         if (job.k_fixed >= fr.kmax) {
             job.n_active = 0;
@@ -741,7 +743,7 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
     if ((rc = timed_begin(ws, timed, s, -1, VMX_K_RESOLVE))) return rc;
     LAUNCH_TRY(launch_resolve(fr, act_cur, n_active, S, split || refill, ws.rad.p, split ? pa.rad_mask : nullptr, px, act_next,
-                              ws.next_count.p, job.d_out, ws.counters.p, s));
+                              ws.next_count.p, job.d_out, ws.counters.p, s, job.moments));
     if ((rc = timed_end(timed, s))) return rc;
     launches++;
     job.passes++;

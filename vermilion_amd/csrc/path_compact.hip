@@ -49,6 +49,22 @@ k_slot_scatter(const unsigned long long *__restrict__ mask, const unsigned int *
     }
 }
 
+// a pixel list compacted in order (a progressive handle's master list by a selection map, or by "still takes samples"):
+// slot i of `src` goes to its rank among the set bits
+__global__ void __launch_bounds__(256)
+k_list_scatter(const unsigned long long *__restrict__ mask, const unsigned int *__restrict__ offs, uint32_t nwords,
+               const unsigned int *__restrict__ src, unsigned int *__restrict__ dst, unsigned int *__restrict__ count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < nwords; w += waves) {
+        const unsigned long long bits = mask[w];
+        const uint32_t off = offs[w];
+        // (a set bit is a slot below the list's length: launch_list_words)
+        if ((bits >> lane) & 1ull) dst[off + (uint32_t)__popcll(bits & ((1ull << lane) - 1ull))] = src[w * 64u + lane];
+        if (w + 1 == nwords && lane == 0) *count = off + (uint32_t)__popcll(bits);
+    }
+}
+
 }  // namespace
 
 size_t live_compact_tmp_bytes(uint32_t nwords) {
@@ -76,6 +92,17 @@ int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, u
     if (e != hipSuccess) return (int)e;
     const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
     hipLaunchKernelGGL(k_slot_scatter, dim3(grid), dim3(256), 0, s, mask, offs, nwords, n_active, unclaimed, claimed, counts);
+    return (int)hipGetLastError();
+}
+
+int launch_list_compact(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, unsigned int *offs,
+                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (nwords == 0) return (int)hipMemsetAsync(count, 0, 4, s);
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, offs, (int)nwords, s);
+    if (e != hipSuccess) return (int)e;
+    const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
+    hipLaunchKernelGGL(k_list_scatter, dim3(grid), dim3(256), 0, s, mask, offs, nwords, src, dst, count);
     return (int)hipGetLastError();
 }
 

@@ -474,6 +474,10 @@ struct RenderJob {
     int cur_list = 0;
     uint32_t n_uniform = 0;  // samples every active pixel has taken while no early stop was possible
     uint32_t k_fixed = 0;    // fixed-spp mode: samples issued so far
+    // a progressive handle after its first selected step (api_sampling.inc): its pixels hold different counts, k_fixed means
+    // nothing any more, a pass takes min(smax, cap) samples and the kernels' k < kmax clipping ends each pixel on its own
+    bool ragged = false;
+    bool moments = false;    // k_resolve<true>: accum.w carries the sum of squared luminances (VMX_PROGRESSIVE_MOMENTS)
     uint64_t last_pass_pixels = 0, last_pass_breaks = 0;  // early-stop statistics of the previous pass
     uint64_t frame_passes = 0;                            // passes since set-up
     // the current run

@@ -16,7 +16,7 @@ struct QueueDev {  // first-generation kernels only (vmx_kernels_ab.inc): queue 
 };
 
 struct PixelStateDev {
-    void *accum;              // float4[npix_local]  (rgb sum, w unused)
+    void *accum;              // float4[npix_local]  (rgb sum; w: the sum of squared luminances on a moments handle, else 0)
     unsigned int *count;      // samples taken
     unsigned int *cursor;     // next linear sample index k
 };
@@ -258,7 +258,23 @@ int launch_radiance_init_ids(const float *o, const float *d, uint32_t n, uint64_
                              IdQueue qout, void *stream);
 int launch_resolve(const FrameDev &fr, const unsigned int *active, uint32_t n_active, uint32_t samples,
                    bool pixel_major, const void *rad, const unsigned long long *rad_mask, PixelStateDev px, unsigned int *next_active,
-                   unsigned int *next_count, float *out_rgbaz, DevCounters *counters, void *stream);
+                   unsigned int *next_count, float *out_rgbaz, DevCounters *counters, void *stream, bool moments = false);
+// adaptive sampling of a progressive handle (vmx_sampling.inc; the arithmetic is stated in include/vermilion_hip.h)
+// one word of bits and its popcount per 64 slots of `list` (nwords = ceil(n / 64)): slot i < n is set if its pixel lp =
+// list[i] has cursor[lp] < kmax and (select == NULL or select[lp] != 0); launch_list_compact then writes the set slots'
+// pixels to `dst` in order and their number to *count
+int launch_list_words(const unsigned int *list, uint32_t n, const unsigned char *select, const unsigned int *cursor, uint32_t kmax,
+                      unsigned long long *mask, unsigned int *cnt, void *stream);
+int launch_list_compact(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, unsigned int *offs,
+                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream);
+struct SamplingPass {
+    uint32_t width, height;  // the handle's local image
+    uint32_t kmax, min_samples, radius;
+    float threshold, floor;
+    PixelStateDev px;
+};
+int launch_sampling_error(const SamplingPass &a, float *error, float *variance, void *stream);
+int launch_sampling_select(const SamplingPass &a, unsigned char *select, unsigned int *count, void *stream);
 // BruteForceTracer::Render (integrators.cpp:9-186): one lane per pixel of `order` (tile-ordered local pixels)
 int launch_bruteforce(const SceneDev &sc, const FrameDev &fr, const unsigned int *order, uint32_t npix, uint32_t flags,
                       float *out, DevCounters *counters, void *longs /* 64 bytes per pixel */, unsigned int *long_count,

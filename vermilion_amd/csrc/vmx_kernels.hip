@@ -49,6 +49,7 @@
 
 
 namespace vmx {
+__device__ __forceinline__ float luminance(float r, float g, float b);  // (vmx_image.inc; k_resolve<true> folds its square)
 namespace {
 
 constexpr float kInf = __builtin_huge_valf();
@@ -3411,6 +3412,10 @@ __device__ __forceinline__ void resolved_pixel(const float4 &acc, uint32_t n, fl
 }
 
 // per-pixel accumulation in sample order + early stop + pixel write (pathtracer.cpp:282-324)
+// MOMENTS (a vmx_progressive handle begun with VMX_PROGRESSIVE_MOMENTS): accum.w carries the sum of the squared luminance of
+// the samples taken, folded right after the colour — a path the radiance mask marks as not stored adds an exact +0 there
+// too.  <false> is the kernel as it was.
+template <bool MOMENTS>
 __global__ void k_resolve(FrameDev fr, const unsigned int *__restrict__ active, uint32_t n_active,
                           uint32_t n_pad, uint32_t samples, uint32_t pixel_major, const float4 *__restrict__ rad,
                           const unsigned long long *__restrict__ rad_mask, PixelStateDev px,
@@ -3475,6 +3480,10 @@ __global__ void k_resolve(FrameDev fr, const unsigned int *__restrict__ active, 
                 acc.x = acc.x + s.x;  // :283
                 acc.y = acc.y + s.y;
                 acc.z = acc.z + s.z;
+                if (MOMENTS) {
+                    const float l = luminance(s.x, s.y, s.z);
+                    acc.w = acc.w + l * l;
+                }
                 ++taken;
                 bool early = false;
                 if (fr.early_stop && n > fr.nmin) {  // n > sqrt(spp), :292
@@ -4084,9 +4093,9 @@ int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, in
 
 int launch_resolve(const FrameDev &fr, const unsigned int *active, uint32_t n_active, uint32_t samples,
                    bool pixel_major, const void *rad, const unsigned long long *rad_mask, PixelStateDev px, unsigned int *next_active,
-                   unsigned int *next_count, float *out_rgbaz, DevCounters *counters, void *stream) {
+                   unsigned int *next_count, float *out_rgbaz, DevCounters *counters, void *stream, bool moments) {
     const uint32_t n_pad = (n_active + 63u) & ~63u;
-    hipLaunchKernelGGL(k_resolve, dim3((n_active + 255) / 256), dim3(256), 0, (hipStream_t)stream, fr, active,
+    hipLaunchKernelGGL(moments ? k_resolve<true> : k_resolve<false>, dim3((n_active + 255) / 256), dim3(256), 0, (hipStream_t)stream, fr, active,
                        n_active, n_pad, samples, pixel_major ? 1u : 0u, (const float4 *)rad, pixel_major ? rad_mask : nullptr, px, next_active,
                        next_count, out_rgbaz, counters);
     return launch_status();
@@ -4150,6 +4159,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 #include "vmx_adaptive.inc"
 // variance-guided denoising: the variance of a moments accumulator and the filter it steers
 #include "vmx_variance.inc"
+// adaptive sampling of a progressive handle: list compaction, the per-pixel error of the mean and the selection map
+#include "vmx_sampling.inc"
 // motion records for refitted geometry: where each pixel's surface point was before an update
 #include "vmx_motion.inc"
 

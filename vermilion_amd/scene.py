@@ -158,6 +158,21 @@ def make_adaptive_params(gamma=None, min_support=None, normal_squarings=None, si
     return p
 
 
+def make_sampling_params(threshold=None, floor=None, min_samples=None, radius=None):
+    """vmx_sampling_params: the library's defaults (vmx_sampling_default_params) with the given fields replaced"""
+    p = L.SamplingParams()
+    L.check(L.lib().vmx_sampling_default_params(C.byref(p)))
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if floor is not None:
+        p.floor = float(floor)
+    if min_samples is not None:
+        p.min_samples = int(min_samples)
+    if radius is not None:
+        p.radius = int(radius)
+    return p
+
+
 def make_upsample_params(normal_squarings=None, sigma_depth=None):
     """vmx_upsample_params: the library's defaults (vmx_upsample_default_params) with the given fields replaced"""
     p = L.UpsampleParams()
@@ -660,11 +675,12 @@ class Scene:
         self._check(self._lib.vmx_render(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
-    def progressive(self, cam, opts, stream=None):
+    def progressive(self, cam, opts, stream=None, moments=False):
         """vmx_progressive_begin: the frame `render(cam, opts)` returns, rendered in resumable steps with previews in
         between (a context-managed Progressive).  stream: a torch stream the passes and previews run on (default: the
-        scene's own stream)."""
-        return Progressive(self, cam, opts, stream)
+        scene's own stream).  moments (vmx_progressive_begin_ex, VMX_PROGRESSIVE_MOMENTS): the handle also keeps the
+        second moment of every pixel's luminance, which `error_device`, `select_device` and `step_adaptive` need."""
+        return Progressive(self, cam, opts, stream, moments)
 
     def render_bruteforce(self, cam, opts, flags=0):
         """BruteForceTracer::Render (core/integrators/integrators.cpp:9-186) into a host array
@@ -688,8 +704,9 @@ class Progressive:
     """One vmx_progressive handle: `step` issues samples, `preview` shows the frame so far, and the frame a completed
     handle previews is `Scene.render`'s, bit for bit, whatever the steps were."""
 
-    def __init__(self, scene, cam, opts, stream=None):
+    def __init__(self, scene, cam, opts, stream=None, moments=False):
         self._scene = scene  # (keeps the scene alive: it cannot be destroyed before its handles)
+        self.moments = bool(moments)
         self._lib = scene._lib
         self._h = None
         self.device = scene.device
@@ -697,9 +714,12 @@ class Progressive:
         rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
         self.shape = (rows, int(cam.image_res[0]))
         h = C.c_void_p()
-        scene._check(self._lib.vmx_progressive_begin(scene._h, C.byref(cam), C.byref(opts),
-                                                     C.c_void_p(stream.cuda_stream if stream is not None else 0),
-                                                     C.byref(h)))
+        sptr = C.c_void_p(stream.cuda_stream if stream is not None else 0)
+        if moments:
+            scene._check(self._lib.vmx_progressive_begin_ex(scene._h, C.byref(cam), C.byref(opts), L.VMX_PROGRESSIVE_MOMENTS,
+                                                            sptr, C.byref(h)))
+        else:
+            scene._check(self._lib.vmx_progressive_begin(scene._h, C.byref(cam), C.byref(opts), sptr, C.byref(h)))
         self._h = h
 
     def close(self):
@@ -724,6 +744,74 @@ class Progressive:
         st = L.Stats()
         self._scene._check(self._lib.vmx_progressive_step(self._h, int(samples), C.byref(st)))
         return st.as_dict()
+
+    def _plane(self, x, name, dtype, last=None):
+        """a torch tensor of the handle's local image ([rows, W] or [rows, W, last]) on its device, or a ValueError"""
+        import torch
+        return _frame_tensor(x, name, dtype, self.shape + (() if last is None else (last,)), torch.device("cuda", self.device))
+
+    def state_device(self, sums=None, counts=None):
+        """vmx_progressive_state_device: the raw per-pixel state into torch tensors on the scene's device — sums float32
+        [local_rows, W, 4] (r, g, b sums; w = the sum of squared luminances on a moments handle, else 0) and / or counts
+        int32 [local_rows, W].  Enqueued on the handle's stream, nothing synchronised; returns (sums, counts)."""
+        import torch
+        if sums is None and counts is None:
+            raise ValueError("no output: sums and counts are both None")
+        if sums is not None:
+            self._plane(sums, "sums", torch.float32, 4)
+        if counts is not None:
+            self._plane(counts, "counts", torch.int32)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        self._scene._check(self._lib.vmx_progressive_state_device(self._h, ptr(sums), ptr(counts)))
+        return sums, counts
+
+    def step_selected(self, samples, select):
+        """vmx_progressive_step_selected_device: a step in which only the pixels with select != 0 take samples (select: a
+        torch uint8 or bool tensor [local_rows, W] on the scene's device; 0 samples: the selected pixels run to kmax).
+        Blocks; returns (this step's vmx_stats as a dict, the number of pixels that took samples)."""
+        import torch
+        self._plane(select, "select", torch.bool if select is not None and _is_tensor(select) and select.dtype == torch.bool else torch.uint8)
+        st, n = L.Stats(), C.c_uint32(0)
+        self._scene._check(self._lib.vmx_progressive_step_selected_device(self._h, int(samples), C.c_void_p(select.data_ptr()),
+                                                                          C.byref(st), C.byref(n)))
+        return st.as_dict(), int(n.value)
+
+    def error_device(self, error=None, variance=None, params=None):
+        """vmx_progressive_error_device (a moments handle): the relative standard error of every pixel's mean luminance
+        and / or the variance of that mean — what Filter.apply(variance=...) reads — into float32 tensors [local_rows, W].
+        params: make_sampling_params(...), default the library's (only `floor` matters here).  Returns (error, variance)."""
+        import torch
+        if error is None and variance is None:
+            raise ValueError("no output: error and variance are both None")
+        if error is not None:
+            self._plane(error, "error", torch.float32)
+        if variance is not None:
+            self._plane(variance, "variance", torch.float32)
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        prm = None if params is None else C.byref(params)
+        self._scene._check(self._lib.vmx_progressive_error_device(self._h, prm, ptr(error), ptr(variance)))
+        return error, variance
+
+    def select_device(self, select, count=None, params=None):
+        """vmx_progressive_select_device (a moments handle): select[p] = 1 where pixel p is unfinished and has fewer than
+        min_samples samples or an error above the threshold within `radius` pixels, else 0 (uint8 [local_rows, W]); count:
+        an int32 tensor of one element that receives the number of selected pixels.  Returns (select, count)."""
+        import torch
+        self._plane(select, "select", torch.uint8)
+        if count is not None:
+            _frame_tensor(count, "count", torch.int32, (1,), torch.device("cuda", self.device))
+        prm = None if params is None else C.byref(params)
+        self._scene._check(self._lib.vmx_progressive_select_device(self._h, prm, C.c_void_p(select.data_ptr()),
+                                                                   None if count is None else C.c_void_p(count.data_ptr())))
+        return select, count
+
+    def step_adaptive(self, samples, params=None):
+        """vmx_progressive_step_adaptive (a moments handle): `select_device` into a map of the handle's, then
+        `step_selected` with it.  Blocks; returns (this step's vmx_stats as a dict, the number of pixels that took samples)."""
+        st, n = L.Stats(), C.c_uint32(0)
+        prm = None if params is None else C.byref(params)
+        self._scene._check(self._lib.vmx_progressive_step_adaptive(self._h, int(samples), prm, C.byref(st), C.byref(n)))
+        return st.as_dict(), int(n.value)
 
     def info(self):
         i = L.ProgressiveInfo()
