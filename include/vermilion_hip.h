@@ -436,6 +436,13 @@ int vmx_guide_fused_rays(const vmx_scene *scene, uint64_t *settled, uint64_t *fa
  * nothing.  Afterwards vmx_guide_rays reports this call's counts and vmx_guide_list_entries n. */
 int vmx_guide_trace(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
                     uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t);
+/* vmx_guide_trace through the kernel's counting form: additionally inner_visits[i] and tri_tests[i], the inner records
+ * and the triangle tests of ray i's walk over the guide (0 and 0 for a ray that never walked it), so that a test can hold
+ * the device's walk against the host program's visit by visit: a device that never skips a box behind the ray's origin
+ * passes every comparison of answers.  flags bit 0 is VMX_ERR_INVALID here (hit records only); the rest as above. */
+int vmx_guide_trace_visits(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                           uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t,
+                           uint32_t *inner_visits, uint32_t *tri_tests);
 /*
  * Radiance (pathtracer.cpp:21-198) for n explicit camera rays; ray i draws
  * from the stream keyed (opts->seed, i, 0) with the two pixel-jitter draws

@@ -302,6 +302,7 @@ SYMBOLS = {
     "vmx_guide_list_entries": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "vmx_guide_fused_rays": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vmx_guide_trace": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "vmx_guide_trace_visits": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
     "vmx_radiance": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_trig": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_int]),
     "vmx_local_rows": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -982,11 +982,16 @@ int vmx_guide_list_entries(const vmx_scene *csc, uint64_t *entries) {
 
 // One launch of the GUIDE form over n explicit rays, built as run_ids builds a guided bounce generation, and (flags bit 1)
 // run_ids' second launch over the fallback list.  Where each ray ended is read back and checked per ray.
-int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
-                    uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t) {
+// inner_visits / tri_tests (both or neither; hit records only): the launch is the kernel's counting form, and every ray's
+// guide walk leaves its inner records and triangle tests there (0, 0 for a ray that never walked).
+static int guide_trace_impl(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                            uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t,
+                            uint32_t *inner_visits, uint32_t *tri_tests) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
     if (!sc || !origin || !dir || !opts || !settled || !slot || !t) return fail(VMX_ERR_INVALID, "NULL argument");
     if (flags & ~3u) return fail(VMX_ERR_INVALID, "vmx_guide_trace: unknown flag");
+    const bool visits = inner_visits != nullptr;
+    if (visits && (flags & 1u)) return fail(VMX_ERR_INVALID, "vmx_guide_trace_visits: visits are counted with hit records only");
     if (opts->collect_counters) return fail(VMX_ERR_INVALID, "vmx_guide_trace: the counting build never walks the guide");
     const bool records = (flags & 1u) != 0, complete = (flags & 2u) != 0;
     std::lock_guard<std::mutex> lock(sc->mu);
@@ -1020,7 +1025,9 @@ int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir,
         (records && (ws.out_rec.ensure(out_capacity * 16) || ws.out_count.ensure(32))))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed for the guide tree's lists");
     DevBuf<float> d_o, d_d;
-    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3)) return fail(VMX_ERR_NOMEM, "hipMalloc failed");
+    DevBuf<unsigned int> d_visits;
+    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || (visits && d_visits.ensure((size_t)n * 2)))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed");
     WorkDev wk;
     std::memset(&wk, 0, sizeof(wk));
     wk.heads = ws.heads.p;
@@ -1089,7 +1096,14 @@ int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir,
         if (records) HIP_TRY(hipMemsetAsync(ws.out_count.p, 0, 4, s));
         HIP_TRY(hipMemsetAsync(ws.guide_fb_count.p, 0, 4, s));
         HIP_TRY(hipMemsetAsync(ws.guide_heads.p, 0, 4, s));
-        LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, nopx, pa, ws.counters.p, false, true, cfg, s, &gd));
+        if (visits) HIP_TRY(hipMemsetAsync(d_visits.p, 0, (size_t)n * 8, s));
+        LAUNCH_TRY(launch_trace_q(sc->dev, fr, wk, nopx, pa, ws.counters.p, false, true, cfg, s, &gd, visits ? d_visits.p : nullptr));
+        if (visits) {
+            std::vector<unsigned int> hv((size_t)n * 2);
+            HIP_TRY(hipMemcpyAsync(hv.data(), d_visits.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            for (uint32_t i = 0; i < n; ++i) inner_visits[i] = hv[(size_t)i * 2], tri_tests[i] = hv[(size_t)i * 2 + 1];
+        }
         std::memset(settled, 0, n);
         for (uint32_t i = 0; i < n; ++i) slot[i] = 0xFFFFFFFFu, t[i] = 0.f;
         int r = collect(true);
@@ -1142,6 +1156,18 @@ int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir,
     rc = body();
     if (rc) (void)hipStreamSynchronize(s);  // (what was enqueued may still use d_o / d_d, which are freed here)
     return rc;
+}
+
+int vmx_guide_trace(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                    uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t) {
+    return guide_trace_impl(csc, origin, dir, n, opts, flags, grid_blocks, settled, slot, t, nullptr, nullptr);
+}
+
+int vmx_guide_trace_visits(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                           uint32_t flags, uint32_t grid_blocks, uint8_t *settled, uint32_t *slot, float *t,
+                           uint32_t *inner_visits, uint32_t *tri_tests) {
+    if (!inner_visits || !tri_tests) return fail(VMX_ERR_INVALID, "NULL argument");
+    return guide_trace_impl(csc, origin, dir, n, opts, flags, grid_blocks, settled, slot, t, inner_visits, tri_tests);
 }
 
 int vmx_fused_camera_paths(const vmx_scene *csc, uint64_t *paths) {

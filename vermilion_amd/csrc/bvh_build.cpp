@@ -215,9 +215,33 @@ bool flatten_bvh(const float *pos, const float *nrm, const float *uv, uint32_t n
     return flatten(pos, nrm, uv, ntris, out, err);
 }
 
+// (B) of guide_walk.h: a child box may be skipped when it ends behind the ray's origin only if no triangle of its
+// subtree is worse conditioned than shape_max.  Prefix counts of the flagged triangles over the guide's slot order; a
+// flat node's start / nprims cover its subtree, and the inner records follow the flat nodes' order (flatten).
+uint32_t mark_guide_children(HostBvh &guide, double shape_max, uint32_t *unmarked) {
+    const uint32_t ntris = (uint32_t)guide.tris.size();
+    std::vector<uint32_t> flagged((size_t)ntris + 1, 0);
+    for (uint32_t s = 0; s < ntris; ++s)
+        flagged[s + 1] = flagged[s] + (gw_shape(guide.tris[s].e1, guide.tris[s].e2) <= shape_max ? 0u : 1u);
+    uint32_t k = 0, none = 0;
+    for (uint32_t i = 0; i < (uint32_t)guide.start.size() && k < (uint32_t)guide.inner.size(); ++i) {
+        if (guide.right_offset[i] == 0) continue;
+        InnerRecord &r = guide.inner[k++];
+        const uint32_t c[2] = {i + 1, i + guide.right_offset[i]};
+        uint32_t mark[2];
+        for (int j = 0; j < 2; ++j) {
+            mark[j] = flagged[guide.start[c[j]] + guide.nprims[c[j]]] == flagged[guide.start[c[j]]] ? 1u : 0u;
+            none += 1u - mark[j];
+        }
+        r.pad0 = mark[0], r.pad1 = mark[1];
+    }
+    if (unmarked) *unmarked = none;
+    return flagged[ntris];
+}
+
 // The guide of a reference-tree scene (guide_walk.h): the quality tree's device records with every child box padded
-// (gw_pad) and the triangle's leaf slot in the REFERENCE tree in TriRecord::pad[0].  The attribute table is the
-// reference tree's; the guide keeps none.
+// (gw_pad) and marked (mark_guide_children), and the triangle's leaf slot in the REFERENCE tree in TriRecord::pad[0].
+// The attribute table is the reference tree's; the guide keeps none.
 float make_guide_records(HostBvh &guide, const HostBvh &ref, const float *pos, uint32_t ntris) {
     float scene_max = 0.f;
     for (size_t i = 0; i < (size_t)ntris * 9; ++i) scene_max = fmax2(scene_max, std::fabs(pos[i]));
@@ -229,6 +253,7 @@ float make_guide_records(HostBvh &guide, const HostBvh &ref, const float *pos, u
             r.rmin[a] -= pr, r.rmax[a] += pr;
         }
     }
+    mark_guide_children(guide, kGwShapeMax);
     std::vector<uint32_t> ref_slot(ntris, 0);
     for (uint32_t s = 0; s < ntris; ++s) ref_slot[ref.prim_order[s]] = s;
     for (uint32_t s = 0; s < ntris; ++s) guide.tris[s].pad[0] = ref_slot[guide.prim_order[s]];

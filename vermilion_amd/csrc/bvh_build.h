@@ -36,6 +36,11 @@ bool build_bvh_sah(const float *pos, const float *nrm, const float *uv, uint32_t
 // (guide_walk.h): padded child boxes, the reference leaf slot of each triangle in TriRecord::pad[0], no attributes.
 // Returns M, the bound on |origin coordinate| that the pad and the per-ray rule share.
 float make_guide_records(HostBvh &guide, const HostBvh &ref, const float *pos, uint32_t ntris);
+// ... and its skip marks (guide_walk.h (B)), which make_guide_records sets with kGwShapeMax: InnerRecord::pad0 / pad1 = 1
+// for a child whose subtree holds no triangle with gw_shape > shape_max, else 0.  Returns the triangles beyond the limit;
+// *unmarked, if given, receives the child boxes left without a mark.  (shape_max = infinity marks every child, a
+// negative one none: the test program's two extremes.)
+uint32_t mark_guide_children(HostBvh &guide, double shape_max, uint32_t *unmarked = nullptr);
 
 // linear BVH built ENTIRELY on the GPU (lbvh_build.hip): Morton sort + Karras hierarchy + bottom-up fit +
 // device-record emission.  The product buffers (`geom` = inner records then triangle records, `attrs`) are

@@ -22,7 +22,7 @@
 //
 // The guide walk (gw_walk here; the GUIDE step of k_trace_w<1>) is the step of k_trace_w<1> over the guide's records —
 // nearer child first, one triangle per step, tri_test untouched, so a triangle's t has the bits the reference computes —
-// with two changes:
+// with three changes (the third one is (B) below: a marked child box that ends behind the origin is not entered):
 //   * a node is pruned, in choose_child and in the pop, when near > cut, cut = best (1 + kGwKappa), kept up to date
 //     with best (the reference prunes on near > best, bvh.cpp:69);
 //   * beside (best, slot) the ray keeps `second`, the smallest accepted distance of any OTHER triangle it tested: on a
@@ -48,10 +48,29 @@
 //       whose det cancels can miss it, and the adversarial cases of tests/test_guide_walk.py (sliver fans, coplanar
 //       pairs, planes a few floats apart, grazing rays) are there to hold it.  A wider kappa asks less of it; the widest
 //       one that costs less than 3 % more visits was taken (profiles/guide_tree.txt).
+//   (B) The second premise, for the cull below: a triangle U that tri_test accepts (dist > 0) is crossed by the exact
+//       line inside the box of its vertices at a parameter tau > -(15/16) pad, pad the smallest pad of any guide box that
+//       holds U.  Then by (S) (a sixteenth of the pad, in coordinates) U's padded leaf box and every padded ancestor have
+//       float far >= 0.  Like (P) it is a statement about tri_test's accuracy, and it is FALSE for ill-conditioned
+//       records: where the origin lies within rounding of the plane of a sliver, the numerator e2 . q of dist has no
+//       reliable sign, and a triangle hundreds of pads behind the origin is accepted with a positive float dist (3.5, 92,
+//       234 were seen).  The failure rate falls with the conditioning of the record's edge pair,
+//         gw_shape(e1, e2) = |e1| |e2| / |e1 x e2|     (1 / sin of the angle between the edges; computed in double),
+//       from 372 wrong rays in 200,000 at shape ~40,000 to 4 at ~400 and none at ~107 and below (the sweep of
+//       tests/test_guide_cull.py, profiles/guide_cull.txt; an earlier host experiment saw 1 at ~70, none at ~18), so (B) is
+//       asked only of triangles with gw_shape <= kGwShapeMax: make_guide_records marks a child box of a guide record
+//       (InnerRecord::pad0 for the left child, pad1 for the right; 1 = may be skipped) only if no triangle of the child's
+//       subtree is worse.  A zero word means "never skip": the reference tree's records, whose spare words are zero, are
+//       walked as the reference walks them, boxes behind the origin included (bbox.cpp:70-83 has no sign test).
+//       The cull: a marked child counts as hit only if near <= far AND far >= 0.  `near` keeps its meaning for the
+//       order and the prune; only the hit decision changes.  A bounce ray's own surface, 0.001 behind its origin, is
+//       never culled: its padded box contains the origin.
 //   (1) Completeness of the guide walk.  Let t be the final best.  A triangle U accepted at t_U <= t (1 + 2^-16) was
 //       TESTED by the walk.  Its leaf and every ancestor contain U's vertex box, so by (P) and (S) none of them is a slab
 //       miss and each has near <= tau <= t_U (1 + kappa / 2) <= t (1 + 2^-16)(1 + kappa / 2) < t (1 + kappa) <= cut at any
-//       time (best only falls towards t; kappa >= 2^-10), so none is pruned either.  Hence second, as the walk leaves it,
+//       time (best only falls towards t; kappa >= 2^-10), so none is pruned either.  Nor is any of them skipped by the
+//       cull: a box on the way to U that carries a mark holds only triangles of shape <= kGwShapeMax, U among them, so
+//       (B) gives it far >= 0; a box without a mark is never skipped.  Hence second, as the walk leaves it,
 //       is the smallest accepted distance of every triangle other than the winner, up to those beyond t (1 + 2^-16).
 //   (2) The rule asks second > best (1 + 2^-16).  With (1): every triangle other than the winner m that the reference
 //       can accept for this ray is accepted beyond t (1 + 2^-16).  Equal distances (a duplicated triangle, a shared
@@ -78,7 +97,8 @@
 //       tree, so the hit record and everything downstream keep reference slots.
 //   (5) No hit.  best stays 999999999 and cut = 999999999 (1 + kappa).  By (P) and (S) a triangle accepted at t_U in a
 //       pruned node has t_U (1 + kappa / 2) > cut, t_U > 999999999, and fails the reference's `dist < 999999999`
-//       (bvh.cpp:90) as well; one behind a slab miss is not accepted at all.  The reference returns no hit.
+//       (bvh.cpp:90) as well; one behind a slab miss is not accepted at all; one in a skipped box (marked, far < 0) is
+//       not accepted by (B).  The reference returns no hit.
 //   (6) Guards: origin, direction and reciprocals all finite (so no direction component is zero, no slab is NaN and
 //       the wave-level NaN-exact box form never meets the guide: such rays are appended to the fallback list unwalked),
 //       |o_k| <= M, and every comparison of the rule is written so that a NaN fails it.
@@ -105,6 +125,25 @@ constexpr float kGwFlatRel = 7.62939453125e-06f;  // 2^-17: (3b)
 constexpr float kGwPadRel = 3.814697265625e-06f;  // 2^-18: the pad of a guide box face
 constexpr float kGwLimit = 999999999.f;           // bvh.cpp:48
 constexpr float kGwOriginReach = 4.0f;            // M over the largest |coordinate| of the vertices
+#ifndef VMX_GW_SHAPE_MAX
+#define VMX_GW_SHAPE_MAX 8.0  // (B): the worst gw_shape a skippable box may hold (the sweep of tests/test_guide_cull.py)
+#endif
+constexpr double kGwShapeMax = VMX_GW_SHAPE_MAX;
+#ifndef VMX_GW_CULL
+#define VMX_GW_CULL 1  // 0: every walk tests the boxes behind the origin, whatever the marks say (the A/B build)
+#endif
+
+// (B): the conditioning of a record's edge pair, |e1| |e2| / |e1 x e2|, in double from the record's floats; a zero cross
+// product (or a NaN) counts as infinite
+VMX_GW_FN double gw_shape(const float *e1, const float *e2) {
+    const double ax = e1[0], ay = e1[1], az = e1[2], bx = e2[0], by = e2[1], bz = e2[2];
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double cross2 = cx * cx + cy * cy + cz * cz, dots = (ax * ax + ay * ay + az * az) * (bx * bx + by * by + bz * bz);
+    if (!(cross2 > 0.0)) return (double)INFINITY;
+    return sqrt(dots / cross2);
+}
+// the bound a child's `far` has to reach to count as hit, from the record's spare word for that child (0: never skipped)
+VMX_GW_FN float gw_far_floor(uint32_t mark) { return (VMX_GW_CULL && mark != 0u) ? 0.0f : -INFINITY; }
 
 VMX_GW_FN bool gw_finite(float x) { return fabsf(x) <= 3.0e38f; }  // false on NaN
 
@@ -225,7 +264,7 @@ VMX_GW_FN bool gw_walk(const InnerRecord *inner, const TriRecord *tris, uint32_t
                 const float bx = (hi[0] - o[0]) * inv[0], by = (hi[1] - o[1]) * inv[1], bz = (hi[2] - o[2]) * inv[2];
                 const float n = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
                 const float f = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-                tn[c] = n, h[c] = n <= f;
+                tn[c] = n, h[c] = n <= f && f >= gw_far_floor(c ? q.pad1 : q.pad0);  // (B): a marked box behind the origin
             }
             const bool go_right = h[1] && (!h[0] || tn[1] < tn[0]);
             if (h[0] && h[1]) {

@@ -242,8 +242,11 @@ int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, u
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
                            unsigned long long *mask, unsigned int *cnt, void *stream);
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
-                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide = nullptr);
-// (guide: the GUIDE form of the bounce kernel, which launch_trace_q launches when it is handed a guide)
+                   DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide = nullptr,
+                   unsigned int *visits = nullptr);
+// (guide: the GUIDE form of the bounce kernel, which launch_trace_q launches when it is handed a guide; visits, with a
+// guide and hit records only: its counting form k_trace_w_visits, which leaves two words per path id there — the inner
+// records and the triangle tests of the ray's guide walk)
 int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, bool from_queue, bool sorted, bool live, int *blocks,
                                 bool guide = false);
 // ... and the wide shading kernel: RayCast tail + Radiance step + id compaction

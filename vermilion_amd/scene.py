@@ -667,6 +667,22 @@ class Scene:
                                               settled.ctypes.data, slot.ctypes.data, t.ctypes.data))
         return settled, slot, t
 
+    def guide_trace_visits(self, origin, direction, opts=None, complete=False, grid_blocks=0):
+        """vmx_guide_trace_visits (debug entry): guide_trace through the kernel's counting form.  Returns (settled, slot, t,
+        inner_visits uint32 [n], tri_tests uint32 [n]): the inner records and triangle tests of every ray's guide walk."""
+        o, d = _f32(origin, 3), _f32(direction, 3)
+        n = o.shape[0]
+        if opts is None:
+            opts = make_opts()
+        settled = np.zeros(n, np.uint8)
+        slot = np.full(n, 0xFFFFFFFF, np.uint32)
+        t = np.zeros(n, np.float32)
+        nv, nt = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._check(self._lib.vmx_guide_trace_visits(self._h, o.ctypes.data, d.ctypes.data, n, C.byref(opts), 2 if complete else 0,
+                                                     int(grid_blocks), settled.ctypes.data, slot.ctypes.data, t.ctypes.data,
+                                                     nv.ctypes.data, nt.ctypes.data))
+        return settled, slot, t, nv, nt
+
     def render(self, cam, opts):
         """PathTracer::Render into a host array [local_rows, W, 5] (RGBAZ)."""
         rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
