@@ -738,16 +738,18 @@ def test_random_soups_production_kernels_bit_exact(kind):
         rids, rtt = p.cpu.trace(oo, dd)
         assert np.array_equal(ids, rids) and np.array_equal(bits(tt), bits(rtt)), (kind, n)
         p.close()
-        # the same soup through the quality tree the GPU builds (PLOC): the reference's traversal over the exported
-        # tree must agree bit for bit, frames included (duplicates and degenerate boxes stress the clustering)
-        with va.Scene(pos, nrm, uv, leaf_size=leaf, builder=va._lib.VMX_BVH_PLOC) as g:
-            tree = g.bvh()
-            assert sorted(tree["prim_order"].tolist()) == list(range(n))
-            osc = O.OracleScene(pos, nrm, uv, leaf_size=leaf, tree=tree)
-            tri, t = g.trace(o, d)
-            otri, ot = osc.trace(o, d)
-            assert np.array_equal(tri, otri) and np.array_equal(bits(t), bits(ot)), (kind, n, "ploc")
-            img, _ = g.render(cam, va.make_opts(seed=5, early_stop=False, pipeline=4))
-            oimg, _ = osc.render(cam, va.make_opts(seed=5, early_stop=False))
-            assert np.array_equal(bits(img), bits(oimg)), (kind, n, "ploc frame")
-            osc.close()
+        # the same soup through the trees the GPU builds (the PLOC quality tree and the linear BVH): the reference's
+        # traversal over the exported tree must agree bit for bit, frames included (duplicates and degenerate boxes stress
+        # the clustering, equal Morton codes the radix tree)
+        for tag, bld in (("ploc", va._lib.VMX_BVH_PLOC), ("lbvh", va._lib.VMX_BVH_LBVH)):
+            with va.Scene(pos, nrm, uv, leaf_size=leaf, builder=bld) as g:
+                tree = g.bvh()
+                assert sorted(tree["prim_order"].tolist()) == list(range(n))
+                osc = O.OracleScene(pos, nrm, uv, leaf_size=leaf, tree=tree)
+                tri, t = g.trace(o, d)
+                otri, ot = osc.trace(o, d)
+                assert np.array_equal(tri, otri) and np.array_equal(bits(t), bits(ot)), (kind, n, tag)
+                img, _ = g.render(cam, va.make_opts(seed=5, early_stop=False, pipeline=4))
+                oimg, _ = osc.render(cam, va.make_opts(seed=5, early_stop=False))
+                assert np.array_equal(bits(img), bits(oimg)), (kind, n, tag + " frame")
+                osc.close()

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import oracle_lib as O
+from shared_inputs import numpy_boxes
 import vermilion_amd as va
 from vermilion_amd import _lib as L
 from vermilion_amd import scenes
@@ -41,27 +42,6 @@ def scene_rays(pos, n=20000, seed=5):
     lo, hi = v.min(axis=0), v.max(axis=0)
     pad = 0.1 * (hi - lo)
     return rand_rays(n, seed, lo - pad, hi + pad)
-
-
-def numpy_boxes(tree, pos):
-    """every node's tight box over its triangles' vertices, for the given topology"""
-    p = np.asarray(pos, np.float32).reshape(-1, 3, 3)
-    order = tree["prim_order"]
-    slo, shi = p.min(axis=1)[order], p.max(axis=1)[order]
-    ro = tree["right_offset"]
-    n = len(tree["start"])
-    box = np.zeros((n, 6), np.float32)
-    leaf = ro == 0
-    li = np.nonzero(leaf)[0]
-    li = li[np.argsort(tree["start"][li], kind="stable")]  # leaves partition the slots
-    st = tree["start"][li].astype(np.int64)
-    box[li, :3] = np.minimum.reduceat(slo, st, axis=0)
-    box[li, 3:] = np.maximum.reduceat(shi, st, axis=0)
-    for i in np.nonzero(~leaf)[0][::-1]:
-        l, r = i + 1, i + ro[i]
-        box[i, :3] = np.minimum(box[l, :3], box[r, :3])
-        box[i, 3:] = np.maximum(box[l, 3:], box[r, 3:])
-    return box
 
 
 def deform(pos, amp=0.02, phase=0.0):

@@ -266,8 +266,8 @@ __global__ void k_lbvh_keys(const float *__restrict__ pos, uint32_t n, const int
 // A quality tree built bottom-up on the GPU: the clusters (at first the triangles in Morton order) each look
 // for the neighbour within `radius` positions whose union box has the smallest surface area; pairs that chose
 // each other merge into a new node, the cluster array is compacted, and the rounds repeat until one cluster
-// is left.  Everything that orders the result is a scan or a strict total order on pairs (area, lower
-// position, higher position), so the tree is the same on every run.  Node indices are handed out from the top
+// is left.  Everything that orders the result is a scan or a strict total order on pairs (area, even-odd
+// neighbours first, lower position, higher position), so the tree is the same on every run.  Node indices are handed out from the top
 // (the last merge gets index 0): the emission kernels take inner record 0 as the root, as for the Karras tree.
 __device__ __forceinline__ float ploc_half_area(const float *a, const float *b) {
     const float dx = fmaxf(a[3], b[3]) - fminf(a[0], b[0]), dy = fmaxf(a[4], b[4]) - fminf(a[1], b[1]),
@@ -298,12 +298,17 @@ __global__ void k_ploc_nearest(int nc, int radius, const float *__restrict__ c_b
     const int lo = max(i - radius, 0), hi = min(i + radius, nc - 1);
     for (int j = lo; j <= hi; ++j) {
         if (j == i) continue;
-        const float a = ploc_half_area(mine, c_box + (size_t)j * 6);
-        // strict total order on pairs: (area, lower position, higher position)
+        const float area = ploc_half_area(mine, c_box + (size_t)j * 6);
+        // extents that overflow give inf * 0: a NaN is never smaller or equal, and would stay `best` for good
+        const float a = area == area ? area : INFINITY;
+        // strict total order on pairs: (area, not positions 2k and 2k + 1, lower position, higher position).  Were equal
+        // areas settled by position alone, every cluster of a run of equal boxes would choose its leftmost candidate,
+        // one pair would merge per round and the tree would be a chain; pairs (2k, 2k + 1) halve such a run.
         bool better = bj < 0 || a < best;
         if (!better && a == best) {
             const int m0 = min(i, j), m1 = max(i, j), b0 = min(i, bj), b1 = max(i, bj);
-            better = m0 < b0 || (m0 == b0 && m1 < b1);
+            const bool mp = (m0 ^ 1) == m1, bp = (b0 ^ 1) == b1;  // m0 < m1: m0 is even
+            better = mp != bp ? mp : (m0 < b0 || (m0 == b0 && m1 < b1));
         }
         if (better) best = a, bj = j;
     }
