@@ -15,7 +15,7 @@
 //
 //   g++ -std=c++17 -I include examples/render_flythrough.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_flythrough     (done by __graft_entry__.build())
-//   ./examples/render_flythrough [--moving] [--textured] [--variance] [--adaptive] [--upsample N/D] fly 256 256 [frames [spp [seed]]]
+//   ./examples/render_flythrough [--moving] [--light] [--textured] [--variance] [--adaptive] [--upsample N/D] fly 256 256 [frames [spp [seed]]]
 //
 // Writes fly_raw.ppm (the last frame as rendered), fly_acc.ppm (accumulated) and fly_out.ppm (accumulated and filtered),
 // and prints the mean history length of each frame.
@@ -28,6 +28,14 @@
 //   vmx_temporal_accumulate_motion_device   the history looked up where the surface was: the block keeps its own
 //   vmx_filter_set_guide_device + vmx_filter_apply_device
 // A second accumulator takes the same frames without the motion records; the mean history length of both is printed.
+//
+// --light: from frame 8 on (so: with more than the default 8 frames) the lights change every frame — the small emitter
+// moves by (3, 0, 2) a frame and the big one is dimmed to a quarter — and each such frame adds
+//   vmx_scene_set_spheres             the new sphere table, in place: no rebuild, no upload of the scene
+//   vmx_motion_spheres_device         after the G-buffer: where the pixels on the moved emitter were a frame before; it
+//                                     writes over vmx_motion_device's records in place under --moving, else stands alone
+// The records go wherever --moving's go, so it composes with --moving, --variance and --adaptive (whose history cut is
+// what answers the dimmed light).
 //
 // --textured: a procedural checker is bound (vmx_scene_bind_texture), and the filter step becomes
 //   vmx_albedo_camera_device             the frame's albedo plane: 4 samples of what the integrator multiplies by
@@ -116,10 +124,11 @@ bool write_ppm(const std::string &name, const std::vector<unsigned char> &rgba, 
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool moving = false, textured = false, variance = false, adaptive = false;
+    bool moving = false, textured = false, variance = false, adaptive = false, light = false;
     uint32_t up_n = 0, up_d = 0;  // --upsample N/D
     for (; argc > 1 && std::strncmp(argv[1], "--", 2) == 0; --argc, ++argv) {
         if (std::strcmp(argv[1], "--moving") == 0) moving = true;
+        else if (std::strcmp(argv[1], "--light") == 0) light = true;
         else if (std::strcmp(argv[1], "--textured") == 0) textured = true;
         else if (std::strcmp(argv[1], "--variance") == 0) variance = true;
         else if (std::strcmp(argv[1], "--adaptive") == 0) adaptive = true;
@@ -216,9 +225,17 @@ int main(int argc, char **argv) {
     if (textured && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_albedo, npix * 16) == 0;
     if (variance && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_var, npix * 4) == 0;
     if (adaptive && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_change, npix * 4) == 0;
+    if ((moving || light) && hip_ok && rc == VMX_OK) hip_ok = hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0;
+    // --light: the sphere table of this frame and of the one before
+    std::vector<vmx_sphere> lights[2];
+    if (light) {
+        uint32_t count = 0;
+        const vmx_sphere *def = vmx_default_spheres(&count);
+        lights[0].assign(def, def + count), lights[1] = lights[0];
+    }
     if (moving && hip_ok && rc == VMX_OK) {
         hip_ok = hip.malloc_(&d_pos[0], pos.size() * 4) == 0 && hip.malloc_(&d_pos[1], pos.size() * 4) == 0 &&
-                 hip.malloc_(&d_motion, npix * sizeof(vmx_motion)) == 0 && hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
+                 hip.malloc_(&d_acc_plain, npix * 20) == 0 &&
                  hip.malloc_(&d_hist_plain, npix * 4) == 0 && hip.memcpy_(d_pos[0], pos.data(), pos.size() * 4, 1) == 0;
         if (hip_ok) rc = vmx_temporal_create(0, W, H, &plain);
     }
@@ -254,21 +271,35 @@ int main(int argc, char **argv) {
                 break;
             if ((rc = vmx_scene_update_device(scene, d_pos[i & 1], nullptr, nullptr, ntris, VMX_UPDATE_REFIT, stream)) != VMX_OK) break;
         }
+        const bool relit = light && i >= 8;
+        if (relit) {
+            // sphere 0 is the small emitter, sphere 1 the big one (vmx_default_spheres)
+            std::vector<vmx_sphere> &now = lights[i & 1];
+            now = lights[0], now[0] = vmx_default_spheres(nullptr)[0], now[1] = vmx_default_spheres(nullptr)[1];
+            now[0].centre[0] += 3.f * (float)(i - 7), now[0].centre[2] += 2.f * (float)(i - 7);
+            for (float &c : now[1].colour) c *= 0.25f;
+            if ((rc = vmx_scene_set_spheres(scene, now.data(), (uint32_t)now.size())) != VMX_OK) break;
+        }
         if ((rc = vmx_raycast_camera_device(scene, &cam, &opts, 0, d_rec, 0, stream)) != VMX_OK) break;
         if (update && (rc = vmx_motion_device(d_rec, (uint32_t)npix, d_pos[i & 1], d_pos[(i & 1) ^ 1], nullptr, ntris, d_motion, 0,
                                               stream)) != VMX_OK)
             break;
+        if (relit && (rc = vmx_motion_spheres_device(d_rec, (uint32_t)npix, cam.position, lights[i & 1].data(),
+                                                     lights[(i & 1) ^ 1].data(), (uint32_t)lights[0].size(),
+                                                     update ? d_motion : nullptr, d_motion, stream)) != VMX_OK)
+            break;
+        const void *motion = update || relit ? d_motion : nullptr;
         if ((rc = vmx_render_device(scene, &cam, &opts, d_frame, stream, &st)) != VMX_OK) break;
         if (adaptive) {  // (d_var is NULL without --variance, as a handle without moments wants it)
-            if ((rc = vmx_temporal_accumulate_adaptive_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+            if ((rc = vmx_temporal_accumulate_adaptive_device(temporal, &cam, d_rec, motion, d_frame, d_acc,
                                                               nullptr, d_hist, d_var, d_change, nullptr, nullptr, nullptr,
                                                               stream)) != VMX_OK)
                 break;
         } else if (variance) {
-            if ((rc = vmx_temporal_accumulate_variance_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+            if ((rc = vmx_temporal_accumulate_variance_device(temporal, &cam, d_rec, motion, d_frame, d_acc,
                                                               nullptr, d_hist, d_var, nullptr, nullptr, stream)) != VMX_OK)
                 break;
-        } else if ((rc = vmx_temporal_accumulate_motion_device(temporal, &cam, d_rec, update ? d_motion : nullptr, d_frame, d_acc,
+        } else if ((rc = vmx_temporal_accumulate_motion_device(temporal, &cam, d_rec, motion, d_frame, d_acc,
                                                                nullptr, d_hist, nullptr, stream)) != VMX_OK)
             break;
         if (moving && (rc = vmx_temporal_accumulate_device(plain, &cam, d_rec, d_frame, d_acc_plain, nullptr, d_hist_plain, nullptr,

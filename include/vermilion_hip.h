@@ -307,6 +307,28 @@ int vmx_scene_update(vmx_scene *scene, const float *pos, const float *nrm, const
 int vmx_scene_update_device(vmx_scene *scene, const void *d_pos, const void *d_nrm, const void *d_uv, uint32_t ntris,
                             uint32_t flags, void *stream);
 
+/* ---- changing lights: the sphere table of a live scene ---------------------
+ * All light comes from the analytic sphere table.  vmx_scene_set_spheres replaces it in place: dim, recolour or move a
+ * light, move a wall, or change the count, without building or uploading the scene again.  (spheres, nspheres) mean
+ * exactly what they mean to vmx_scene_create_ex: NULL, 0 selects vmx_default_spheres(); a non-NULL pointer with
+ * nspheres == 0 means no spheres at all; NULL with nspheres > 0, or more than 16 spheres, is VMX_ERR_INVALID; normal_sign
+ * is read as -1 if negative and +1 otherwise, and rad*rad is the float product.  The count may change between calls.
+ * After the call the scene renders, casts and answers exactly as a scene created with that table does, bit for bit:
+ * nothing derived from the old table outlives it (the emitter prefix, the per-run claim tables and pixel-sphere bounds,
+ * the rays' "light in reach" notes).
+ *
+ * Checks that need no device come first, in this order: the (spheres, nspheres) pair, then the NULL handle.
+ * HOST array; returns once the table is written.  Ordering is vmx_scene_update's: the write waits for the scene's last
+ * query and last update, whatever stream they ran on (a render or parity hook has returned before, and a progressive step
+ * likewise); every later render (path tracer and BruteForceTracer), vmx_raycast*, vmx_query*, vmx_albedo_camera_device,
+ * vmx_radiance and parity hook waits for it.  Like a geometry update it ends the progressive handles begun before it:
+ * their next step is VMX_ERR_INVALID ("scene updated since vmx_progressive_begin"); handles begun afterwards see the new
+ * table.  A failed call leaves the scene exactly as it was.  vmx_scene_describe reports the new count.
+ * Temporal accumulation: a dimmed or recoloured light is what vmx_temporal_accumulate_adaptive_device is for; a sphere
+ * that MOVED is followed by vmx_motion_spheres_device (below, "motion records").
+ */
+int vmx_scene_set_spheres(vmx_scene *scene, const vmx_sphere *spheres, uint32_t nspheres);
+
 /* ---- parity hooks (explicit ray batches, host buffers) ----------------- */
 /* BVH::getIntersection (bvh.cpp:47-145): tri_id[n] (-1 = miss), t[n] */
 int vmx_trace(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n,
@@ -663,7 +685,7 @@ int vmx_progressive_preview_demodulated(vmx_progressive *p, float *rgbaz, unsign
  * Limits: without motion records (below) the world is taken as static between the two frames — after
  * vmx_scene_update a moved surface fails the plane test and restarts at n' = 1, and a face that slid within its own
  * plane keeps history of other surface points; vmx_motion_device and vmx_temporal_accumulate_motion_device follow
- * refitted triangles.  The analytic spheres have no motion records.  A NaN colour passes into the history and stays
+ * refitted triangles, vmx_motion_spheres_device an analytic sphere that vmx_scene_set_spheres moved.  A NaN colour passes into the history and stays
  * until that pixel is invalidated or the handle is reset.
  * The kernel holds to this restatement bit for bit (tests/temporal_spec.py).
  */
@@ -735,6 +757,45 @@ typedef struct vmx_motion {       /* 32 bytes, two float4 */
  * VMX_ERR_INVALID; n == 0 is VMX_OK and launches nothing.  Enqueued on `stream`, no synchronisation. */
 int vmx_motion_device(const void *d_rayhit, uint32_t n, const void *d_pos_now, const void *d_pos_prev,
                       const void *d_nrm_prev /* or NULL */, uint32_t ntris, void *d_out, int device, void *stream);
+/* Motion records for pixels that lie on an analytic sphere which vmx_scene_set_spheres moved or resized.  A pure function
+ * of a G-buffer whose rays share one origin (vmx_raycast_camera_device's: origin = the camera's position) and of the
+ * sphere table now and before, as HOST arrays of the same count (no scene handle; a sphere that appears or disappears
+ * between the two tables is outside the rule).  Same arithmetic rules as above; sphereIntersect's discriminant and roots
+ * are double, as in the reference (meshEngine.cpp:182-194).  O = origin; per table entry i: c, r, nc = centre, radius,
+ * normal_centre; sg = normal_sign < 0 ? -1.f : 1.f (as scene creation reads it); _now / _prev name the table.
+ *   moved_i = centre, radius or normal_centre differ bitwise between now and prev, or sg differs
+ * For record r, P = r.location:
+ *   sphere = (r.flags & 1) && !(r.tri_id >= 0 && r.distance == r.tri_t)     (the complement of `on` above without its
+ *            ntris bound: a hit that does not lie on its triangle lies on a sphere)
+ *   Which sphere — the record does not say — is decided as MeshEngine::RayCast decides it, on the table now:
+ *     d = P - O;  s = 1.f / sqrtf(dot(d, d));  d = d * s;  if any component of d is not finite, no sphere is accepted
+ *     nearest = +inf;  for i in table order:  op = c_i - O;  B = dot(op, d);  C = dot(op, op);  R2 = r_i * r_i;
+ *       det = ((double)B*(double)B - (double)C) + (double)R2;  th = 0 if det < 0, else with q = sqrt(det):
+ *       t = (double)B - q;  th = (float)t if t > 1e-4, else t = (double)B + q;  th = (float)t if t > 1e-4, else 0
+ *       th > 0 && th < nearest:  nearest = th, sphere i is accepted        (the last one accepted is the one)
+ *     (never by a residual | |P - c| - r |: any point of the reference's room lies within 3e-6 relative of a radius-5e7
+ *     wall, and the floor would be taken for the small light)
+ *   With the accepted sphere's entries:
+ *     k = r_prev / r_now;  Xh. = c_prev. + (P. - c_now.) * k   per component
+ *     m = Xh - nc_prev;  s = 1.f / sqrtf(dot(m, m));  nh. = (m. * s) * sg_prev;  nh = r.normal if any component is not
+ *     finite (nc_prev == Xh)
+ *   sphere && a sphere was accepted && moved && every component of Xh finite (r_now == 0 is not):  the output is
+ *   (Xh, VMX_MOTION_MOVED, nh, 0);  otherwise the record leaves as d_motion_in's record for that pixel, bit for bit, or
+ *   without d_motion_in as (r.location, 0, r.normal, 0) — what vmx_motion_device writes for an unmoved pixel.  The call
+ *   therefore composes after vmx_motion_device (its d_out as d_motion_in here, in place if wanted) or stands alone.
+ * A record on a sphere that did not move is never rewritten.  That matters on the reference's radius-5e7 walls, where
+ * P - c has an ulp of 4: the rule applies to a wall that moves, but to that precision only.
+ * The kernel holds to this restatement bit for bit (tests/sphere_motion_spec.py).
+ * d_rayhit: n records, d_out: n vmx_motion records, d_motion_in: n vmx_motion records or NULL; all 16-byte aligned DEVICE
+ * memory of one device (the one d_rayhit lies on), checked as vmx_motion_device checks its pointers.  d_out may be
+ * d_motion_in exactly (in place); any other overlap of d_out with an input is VMX_ERR_INVALID.  nspheres > 16, a NULL
+ * pointer other than d_motion_in (the tables may be NULL when nspheres == 0) or n > 2^31 - 1 is VMX_ERR_INVALID, checked
+ * in this order: d_rayhit, origin, spheres_now, spheres_prev, d_out, nspheres, alignment, n, overlap.  n == 0 is VMX_OK
+ * and launches nothing.  The tables are passed to the kernel by value: they may change as soon as the call returns.
+ * Enqueued on `stream`, no synchronisation. */
+int vmx_motion_spheres_device(const void *d_rayhit, uint32_t n, const float origin[3], const vmx_sphere *spheres_now,
+                              const vmx_sphere *spheres_prev, uint32_t nspheres, const void *d_motion_in /* or NULL */,
+                              void *d_out, void *stream);
 /* vmx_temporal_accumulate_device with motion records: d_motion = W*H vmx_motion records in pixel order, 16-byte aligned,
  * read only (it may overlap no buffer the call writes), or NULL — then the call IS vmx_temporal_accumulate_device.
  * Per pixel Xh, nh = prev_location, prev_normal of its record (X, n_p wherever the flag is clear), and the
@@ -785,7 +846,7 @@ int vmx_temporal_accumulate_motion_device(vmx_temporal *t, const vmx_camera *cam
  * tests/variance_spec.py restates it; the kernels hold to it bit for bit.
  * A progressive preview gets its variance plane from the handle itself: vmx_progressive_error_device on a
  * VMX_PROGRESSIVE_MOMENTS handle (the adaptive sampling section below) writes d_variance in this layout.
- * Out of scope: the analytic spheres' motion, and a variance output of the filter. */
+ * Out of scope: a variance output of the filter.  (d_motion may carry vmx_motion_spheres_device's records.) */
 #define VMX_TEMPORAL_MOMENTS 1u
 typedef struct vmx_variance_params {
     float min_history;         /* finite, >= 1; default 4.f                       */
@@ -988,6 +1049,11 @@ int vmx_multi_bind_texture(vmx_multi *m, const float *data, uint32_t width, uint
 /* vmx_scene_update on every replica (HOST arrays).  Host builders with VMX_UPDATE_REBUILD: one host build, uploaded to
  * each device; device builders build on each device.  The frame is bit-identical to one scene updated the same way. */
 int vmx_multi_update(vmx_multi *m, const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t flags);
+/* vmx_scene_set_spheres on every replica, and on the host copy of the table that later vmx_multi_* calls read.  A table
+ * that is refused is refused before any replica changed.  If a device fails part-way (VMX_ERR_HIP), the replicas already
+ * changed are given the old table back, so every replica renders the old table again; their generation has moved on,
+ * so progressive handles of those replicas end as after any update. */
+int vmx_multi_set_spheres(vmx_multi *m, const vmx_sphere *spheres, uint32_t nspheres);
 /* whole frame (W*H*5 floats) into a caller-owned HOST buffer / into DEVICE memory on devices[0];
  * stats: rays and samples summed over the devices, times = the slowest device's */
 int vmx_multi_render(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats);

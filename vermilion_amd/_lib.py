@@ -286,6 +286,7 @@ SYMBOLS = {
     "vmx_scene_bvh": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "vmx_scene_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
     "vmx_scene_update_device": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    "vmx_scene_set_spheres": (C.c_int, [_P, _P, C.c_uint32]),
     "vmx_trace": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P]),
     "vmx_raycast": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "vmx_query_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
@@ -343,6 +344,7 @@ SYMBOLS = {
     "vmx_temporal_accumulate_motion_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P,
                                                         C.POINTER(TemporalParams), _P]),
     "vmx_motion_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_int, _P]),
+    "vmx_motion_spheres_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "vmx_variance_default_params": (C.c_int, [C.POINTER(VarianceParams)]),
     "vmx_temporal_create_ex": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "vmx_temporal_accumulate_variance_device": (C.c_int, [_P, C.POINTER(CameraDesc), _P, _P, _P, _P, _P, _P, _P,
@@ -368,6 +370,7 @@ SYMBOLS = {
     "vmx_multi_timings": (C.c_int, [_P, C.POINTER(MultiTimes), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vmx_multi_bind_texture": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vmx_multi_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
+    "vmx_multi_set_spheres": (C.c_int, [_P, _P, C.c_uint32]),
     "vmx_multi_render": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P,

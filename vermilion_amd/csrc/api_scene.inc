@@ -166,6 +166,42 @@ static void bind_records(vmx_scene *sc) {
     while (sc->block > 64 && (sc->block / 64) * sc->dev.stack_entries * 512 > 65536) sc->block /= 2;
 }
 
+// the (spheres, nspheres) pair of vmx_scene_create_ex, vmx_multi_create and vmx_*_set_spheres: checked the same way
+static int sphere_table_args(const vmx_sphere *spheres, uint32_t nspheres) {
+    if (spheres == nullptr && nspheres != 0)
+        return fail(VMX_ERR_INVALID, "spheres is NULL but nspheres > 0 (NULL,0 selects the reference table)");
+    if (nspheres > kMaxSpheres) return fail(VMX_ERR_INVALID, "more than 16 spheres");
+    return VMX_OK;
+}
+
+// ... and what it selects: the caller's table, or the reference's for NULL
+static std::vector<vmx_sphere> sphere_table(const vmx_sphere *spheres, uint32_t nspheres) {
+    if (spheres) return std::vector<vmx_sphere>(spheres, spheres + nspheres);
+    return std::vector<vmx_sphere>(kReferenceSpheres, kReferenceSpheres + 8);
+}
+
+// the normal_sign the kernels multiply by
+static float sphere_sign(const vmx_sphere &s) { return s.normal_sign < 0.f ? -1.f : 1.f; }
+
+// The device's form of a table — sd[kMaxSpheres], entries past the table zeroed — and what is derived from it
+// (SceneDev::emit_prefix): the one place, for scene creation and for vmx_scene_set_spheres
+static void derive_spheres(const std::vector<vmx_sphere> &table, SphereDev *sd, uint32_t &emit_prefix) {
+    std::memset(sd, 0, kMaxSpheres * sizeof(SphereDev));
+    emit_prefix = 0;
+    for (size_t i = 0; i < table.size(); ++i) {
+        const vmx_sphere &s = table[i];
+        SphereDev &d = sd[i];
+        d.cx = s.centre[0], d.cy = s.centre[1], d.cz = s.centre[2];
+        d.rad = s.radius;
+        d.rad2 = s.radius * s.radius;  // float product (meshEngine.cpp:188)
+        d.colr = s.colour[0], d.colg = s.colour[1], d.colb = s.colour[2];
+        d.ncx = s.normal_centre[0], d.ncy = s.normal_centre[1], d.ncz = s.normal_centre[2];
+        d.nsign = sphere_sign(s);
+        d.flags = s.flags;
+        if (d.flags & 1u) emit_prefix = (uint32_t)i + 1;
+    }
+}
+
 // device half of scene creation: uploads sc->bvh / sc->spheres to sc->device (used for the first scene
 // and for the replicas of a multi-device scene, which share one host-side build)
 static int scene_upload(vmx_scene *sc) {
@@ -176,26 +212,13 @@ static int scene_upload(vmx_scene *sc) {
     sc->num_cus = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&sc->stream.s, hipStreamNonBlocking));
 
-    std::vector<SphereDev> sd(sc->spheres.size());
-    for (size_t i = 0; i < sd.size(); ++i) {
-        const vmx_sphere &s = sc->spheres[i];
-        SphereDev &d = sd[i];
-        std::memset(&d, 0, sizeof(d));
-        d.cx = s.centre[0], d.cy = s.centre[1], d.cz = s.centre[2];
-        d.rad = s.radius;
-        d.rad2 = s.radius * s.radius;  // float product (meshEngine.cpp:188)
-        d.colr = s.colour[0], d.colg = s.colour[1], d.colb = s.colour[2];
-        d.ncx = s.normal_centre[0], d.ncy = s.normal_centre[1], d.ncz = s.normal_centre[2];
-        d.nsign = s.normal_sign < 0.f ? -1.f : 1.f;
-        d.flags = s.flags;
-    }
-    if (sc->d_spheres.ensure(std::max<size_t>(sd.size(), 1))) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
-    if (sd.size()) HIP_TRY(hipMemcpy(sc->d_spheres.p, sd.data(), sd.size() * sizeof(SphereDev), hipMemcpyHostToDevice));
+    // room for the largest table from the start: vmx_scene_set_spheres rewrites it in place, whatever its count
+    SphereDev sd[kMaxSpheres];
+    derive_spheres(sc->spheres, sd, sc->dev.emit_prefix);
+    if (sc->d_spheres.ensure(kMaxSpheres)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the scene");
+    HIP_TRY(hipMemcpy(sc->d_spheres.p, sd, sizeof(sd), hipMemcpyHostToDevice));
     sc->dev.spheres = sc->d_spheres.p;
-    sc->dev.nspheres = (uint32_t)sd.size();
-    sc->dev.emit_prefix = 0;
-    for (size_t i = 0; i < sd.size(); ++i)
-        if (sd[i].flags & 1u) sc->dev.emit_prefix = (uint32_t)i + 1;
+    sc->dev.nspheres = (uint32_t)sc->spheres.size();
     sc->dev.ntris = sc->ntris;
     if (!sc->device_built)
         if (int rc = upload_records(sc->bvh, sc->guide.host.get(), sc->d_geom, sc->d_attrs)) return rc;
@@ -231,9 +254,7 @@ int vmx_scene_create_ex(const float *pos, const float *nrm, const float *uv, uin
     if (builder > VMX_BVH_PLOC) return fail(VMX_ERR_INVALID, "unknown BVH builder");
     *out = nullptr;
     if (!pos || !nrm || ntris == 0) return fail(VMX_ERR_INVALID, "scene needs positions, normals, ntris > 0");
-    if (spheres == nullptr && nspheres != 0)
-        return fail(VMX_ERR_INVALID, "spheres is NULL but nspheres > 0 (NULL,0 selects the reference table)");
-    if (nspheres > kMaxSpheres) return fail(VMX_ERR_INVALID, "more than 16 spheres");
+    if (int rc = sphere_table_args(spheres, nspheres)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(VMX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
@@ -262,10 +283,7 @@ int vmx_scene_create_ex(const float *pos, const float *nrm, const float *uv, uin
         delete sc;
         return build_error(err);
     }
-    if (spheres)
-        sc->spheres.assign(spheres, spheres + nspheres);
-    else
-        sc->spheres.assign(kReferenceSpheres, kReferenceSpheres + 8);
+    sc->spheres = sphere_table(spheres, nspheres);
     vertex_bounds(sc, pos);
     const int rc = scene_upload(sc);
     if (rc) {

@@ -211,9 +211,76 @@ int host_update(vmx_scene *sc, const float *pos, const float *nrm, const float *
     return VMX_OK;
 }
 
+// ---- the sphere table of a live scene (vmx_scene_set_spheres, vmx_multi_set_spheres) ------------------------------------
+// argument checks that need no device, in this order so that each can be seen alone (the handle is checked last)
+int set_spheres_args(const void *handle, const vmx_sphere *spheres, uint32_t nspheres, const char *null_handle) {
+    if (int rc = sphere_table_args(spheres, nspheres)) return rc;
+    if (!handle) return fail(VMX_ERR_INVALID, null_handle);
+    return VMX_OK;
+}
+
+// Rewrites the table in place, under the scene's lock, and returns once it is written.  d_spheres holds kMaxSpheres
+// entries from creation on, so no count needs another allocation.  The write waits for the scene's last query and last
+// update (update_wait); renders, parity hooks and progressive steps block until their kernels are done and hold the lock
+// meanwhile, so none of them is still reading.  Every later call waits on upd.done, as after a geometry update.  What
+// the kernels get by value with each launch — nspheres, emit_prefix — and the host copy change only once the device
+// has the table: a failed call leaves the scene as it was.  Everything else derived from the table (claim tables, pixel
+// bounds, the rays' "light in reach" notes) is made per run from the table a launch sees.
+int set_spheres(vmx_scene *sc, const std::vector<vmx_sphere> &table) {
+    if (int rc = bind_device(sc)) return rc;
+    hipStream_t s = sc->stream;
+    SphereDev sd[kMaxSpheres];
+    uint32_t emit_prefix = 0;
+    derive_spheres(table, sd, emit_prefix);
+    if (int rc = update_wait(sc, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(sc->d_spheres.p, sd, sizeof(sd), hipMemcpyHostToDevice, s));
+    const int rc = sc->upd.done.record(s);
+    const hipError_t es = hipStreamSynchronize(s);  // (`sd` is a host temporary)
+    if (rc) return rc;
+    if (es != hipSuccess) return fail(VMX_ERR_HIP, std::string("vmx_scene_set_spheres: ") + hipGetErrorString(es));
+    sc->spheres = table;
+    sc->dev.nspheres = (uint32_t)table.size();
+    sc->dev.emit_prefix = emit_prefix;
+    sc->generation++;
+    return VMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vmx_scene_set_spheres(vmx_scene *sc, const vmx_sphere *spheres, uint32_t nspheres) {
+    if (int rc = set_spheres_args(sc, spheres, nspheres, "NULL scene")) return rc;
+    const std::vector<vmx_sphere> table = sphere_table(spheres, nspheres);
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return set_spheres(sc, table);
+}
+
+int vmx_multi_set_spheres(vmx_multi *m, const vmx_sphere *spheres, uint32_t nspheres) {
+    if (int rc = set_spheres_args(m, spheres, nspheres, "NULL vmx_multi")) return rc;
+    const std::vector<vmx_sphere> table = sphere_table(spheres, nspheres);
+    std::lock_guard<std::mutex> mlock(m->mu);
+    // replica by replica, each with its own host copy (replica[0]'s is the one later vmx_multi_* calls read).  Nothing
+    // about a table can fail on one device and not on another, but a device can: the replicas already changed then get
+    // the old table back, so that all of them still hold one table
+    const std::vector<vmx_sphere> old = m->replica[0]->spheres;
+    for (size_t r = 0; r < m->replica.size(); ++r) {
+        vmx_scene *sc = m->replica[r];
+        int rc;
+        {
+            std::lock_guard<std::mutex> lock(sc->mu);
+            rc = set_spheres(sc, table);
+        }
+        if (rc == VMX_OK) continue;
+        const std::string keep = r ? "device " + std::to_string(sc->device) + ": " + g_err : g_err;
+        for (size_t q = 0; q < r; ++q) {
+            std::lock_guard<std::mutex> lock(m->replica[q]->mu);
+            (void)set_spheres(m->replica[q], old);
+        }
+        return fail(rc, keep);
+    }
+    return VMX_OK;
+}
 
 int vmx_scene_update(vmx_scene *sc, const float *pos, const float *nrm, const float *uv, uint32_t ntris, uint32_t flags) {
     if (int rc = update_args(sc, pos, nrm, uv, ntris, flags)) return rc;

@@ -388,6 +388,18 @@ int launch_variance(const VariancePass &pass, void *stream);
 constexpr uint32_t kMotionMoved = 1u;  // VMX_MOTION_MOVED
 int launch_motion(const void *rayhit, uint32_t n, const float *pos_now, const float *pos_prev, const float *nrm_prev,
                   uint32_t ntris, void *out, void *stream);
+// motion records for pixels on a moved analytic sphere (vmx_motion_spheres.inc; stated in include/vermilion_hip.h): the
+// two tables of one call, passed to the kernel by value
+struct SphereMotionDev {
+    float now[kMaxSpheres][4];    // centre, radius of the table now
+    float prev[kMaxSpheres][4];   // centre, radius before
+    float nprev[kMaxSpheres][4];  // normal_centre before, normal_sign before as scene creation normalises it (-1.f / 1.f)
+    uint32_t nspheres;
+    uint32_t moved;               // bit i: sphere i differs between the two tables
+    float ox, oy, oz;             // the G-buffer's common ray origin
+};
+int launch_motion_spheres(const void *rayhit, uint32_t n, const SphereMotionDev &tb, const void *motion_in, void *out,
+                          void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

@@ -3766,6 +3766,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 #include "vmx_sampling.inc"
 // motion records for refitted geometry: where each pixel's surface point was before an update
 #include "vmx_motion.inc"
+// ... and for pixels on an analytic sphere that vmx_scene_set_spheres moved
+#include "vmx_motion_spheres.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

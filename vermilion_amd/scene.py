@@ -263,6 +263,67 @@ def motion_vectors(raw, pos_now, pos_prev, nrm_prev=None, out=None, stream=None)
     return out
 
 
+def _sphere_table(spheres, name):
+    """(address, count) of a sphere table as Scene(...) takes it: None (NULL, 0: the reference's table) or a ctypes array of
+    vmx_sphere (spheres_array / default_spheres; an empty one means no spheres at all)"""
+    if spheres is None:
+        return None, 0
+    if not (isinstance(spheres, C.Array) and spheres._type_ is L.Sphere):
+        raise ValueError(f"{name} must be None or a ctypes array of vmx_sphere (spheres_array, default_spheres)")
+    return C.addressof(spheres), len(spheres)
+
+
+def sphere_motion_vectors(raw, origin, spheres_now, spheres_prev, motion=None, out=None, stream=None):
+    """vmx_motion_spheres_device: the motion records of a G-buffer's pixels that lie on a sphere which Scene.set_spheres
+    moved, for Temporal.accumulate(motion=...).  `raw` is the ["raw"] tensor of Scene.raycast_camera on the scene as it is
+    now (float32 [..., 16]); `origin` its rays' common origin, the camera's position (three floats); `spheres_now` and
+    `spheres_prev` the table now and before, ctypes arrays of vmx_sphere of one length (None: the reference's table).
+    `motion`: the records of motion_vectors for the same G-buffer, float32 [..., 8], or None; every pixel that is not on a
+    moved sphere leaves as it is there.  Returns `out`, float32 [..., 8], made if not given; out may be `motion` itself.
+    Tensors are contiguous float32 on raw's device: anything else is a ValueError, never a copy through the host.
+    Enqueued on `stream` (default torch.cuda.current_stream()), nothing synchronised."""
+    import torch
+    if not _is_tensor(raw):
+        raise ValueError("raw must be a torch tensor")
+    if raw.dtype != torch.float32:
+        raise ValueError(f"raw must be {torch.float32} (got {raw.dtype})")
+    if len(raw.shape) < 1 or raw.shape[-1] != 16:
+        raise ValueError(f"raw must be [..., 16] (got {list(raw.shape)})")
+    if not raw.is_contiguous():
+        raise ValueError("raw must be contiguous")
+    dev = raw.device
+    if dev.type != "cuda":
+        raise ValueError(f"raw must be on cuda (got {dev})")
+    o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1)
+    if o.shape != (3,):
+        raise ValueError(f"origin must be three floats (got {list(np.shape(origin))})")
+    if spheres_now is None:
+        spheres_now = default_spheres()
+    if spheres_prev is None:
+        spheres_prev = default_spheres()
+    now, n_now = _sphere_table(spheres_now, "spheres_now")
+    prev, n_prev = _sphere_table(spheres_prev, "spheres_prev")
+    if n_now != n_prev:
+        raise ValueError(f"spheres_now and spheres_prev must have one length (got {n_now} and {n_prev})")
+    lead = tuple(raw.shape[:-1])
+    n = 1
+    for d in lead:
+        n *= int(d)
+    if motion is not None:
+        _frame_tensor(motion, "motion", torch.float32, lead + (8,), dev)
+    if out is None:
+        out = torch.empty(lead + (8,), dtype=torch.float32, device=dev)
+    else:
+        _frame_tensor(out, "out", torch.float32, lead + (8,), dev)
+    if n == 0:
+        return out
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    with _SideStream(dev, stream) as run:
+        L.check(L.lib().vmx_motion_spheres_device(ptr(raw), n, o.ctypes.data, now, prev, n_now, ptr(motion), ptr(out),
+                                                  C.c_void_p(run.cuda_stream)))
+    return out
+
+
 def spheres_array(spheres):
     """list of dicts/tuples -> ctypes array of vmx_sphere"""
     arr = (L.Sphere * len(spheres))()
@@ -523,6 +584,15 @@ class Scene:
             if side is not None:
                 s.wait_stream(side)
         return (tri, t, hit) if want_ids else hit
+
+    # -- changing lights ----------------------------------------------------------
+    def set_spheres(self, spheres=None):
+        """vmx_scene_set_spheres: replaces the sphere table of the live scene — what Scene(...) takes for it: None (the
+        reference's table) or a ctypes array of vmx_sphere (spheres_array / default_spheres; an empty one: no spheres).
+        Returns once the table is written; progressive renders begun before it refuse further steps."""
+        sp, nsp = _sphere_table(spheres, "spheres")
+        self._check(self._lib.vmx_scene_set_spheres(self._h, sp, nsp))
+        self._spheres = spheres
 
     # -- moving geometry --------------------------------------------------------
     def update(self, pos=None, nrm=None, uv=None, rebuild=False, stream=None):
@@ -969,6 +1039,12 @@ class MultiScene:
         data = np.ascontiguousarray(data, dtype=np.float32)
         c = 1 if data.ndim == 2 else data.shape[2]
         L.check(L.lib().vmx_multi_bind_texture(self._h, data.ctypes.data, data.shape[1], data.shape[0], c))
+
+    def set_spheres(self, spheres=None):
+        """vmx_multi_set_spheres: Scene.set_spheres on every replica"""
+        sp, nsp = _sphere_table(spheres, "spheres")
+        L.check(L.lib().vmx_multi_set_spheres(self._h, sp, nsp))
+        self._spheres = spheres
 
     def update(self, pos=None, nrm=None, uv=None, rebuild=False):
         """vmx_multi_update: Scene.update's host entry on every replica (numpy arrays; None keeps that attribute)"""
