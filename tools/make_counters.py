@@ -22,7 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLASSES = [
     # (shade_camera: one timed interval, two launches — the dense form over the unclaimed slots and its CLAIMED
     # instantiation over the claimed ones; a class with several patterns adds their launches' counters and durations up)
-    ("raygen", "k_raygen<0>"), ("trace_camera", "k_trace_w<0, false, false, false>"),
+    # (raygen: the form that settles the listed pixels' rays, k_raygen<0, true> — profiles/raygen_lists.txt)
+    ("raygen", "k_raygen<0, true>"), ("trace_camera", "k_trace_w<0, false, false, false>"),
     ("shade_camera", ("k_shade<0, false, false, 0, true, false>", "k_shade<0, false, false, 0, true, true>")),
     # (one-phase bounce generations go through dense ray records, all kept: the SORT instantiation with WorkDev::keep_all)
     # (with the scene's guide tree, guide_walk.h, the timed interval is two launches as well: the GUIDE instantiation and

@@ -562,6 +562,9 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
         if (ws.unclaimed.ensure((size_t)n_pad_max + 64) || ws.claimed_slots.ensure((size_t)n_pad_max + 64) || ws.unclaimed_mask.ensure(words + 8) || ws.unclaimed_u32.ensure(2 * words + 16) ||
             ws.unclaimed_tmp.ensure(tmp + 256))
             return fail(VMX_ERR_NOMEM, "hipMalloc failed for the list of unclaimed pixels");
+        // (with list claims: the third list, of the unclaimed slots without a list — render_pass)
+        if (job.claim_lists && (ws.walk_slots.ensure((size_t)n_pad_max + 64) || ws.walk_mask.ensure(words + 8) || ws.walk_u32.ensure(2 * words + 16)))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the list of walk slots");
         ws.unclaimed_words = words, ws.unclaimed_tmp_bytes = tmp;
     }
     return VMX_OK;
@@ -656,6 +659,10 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         wk.claim_lists = elide ? nullptr : job.claim_lists, wk.list_ctr = ws.counters.p;
         // fused claimed pixels: where launch_shade picks the dense form of k_shade<0> (pixel-major ids, whole chunks of 64)
         const bool fuse = job.fuse_on && job.claims && (S & 63u) == 0;
+        // ... and, where the run has list claims, settles the listed pixels' rays in k_raygen (below)
+        const bool rays_settle_lists = fuse && !elide && wk.claim_lists != nullptr;
+        unsigned int *walk_len = nullptr;
+        IdQueue stragglers{};
         LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)n_pad * S, job.tb);
         rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)n_pad * S, wk);
         if (rc) return rc;
@@ -679,7 +686,8 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
             if (fuse) {
                 // the pass's unclaimed slots and its claimed ones, each in order (an unordered list costs the traversal kernel
                 // its bands' locality, see above), their numbers on the device only: k_raygen and k_trace_w<0> work on the
-                // first list; k_shade<0> runs over it as it is and, in its CLAIMED form, over the second, where it makes, tests
+                // first list (k_trace_w<0> on the part of it without a list where k_raygen settles the listed pixels' rays,
+                // below); k_shade<0> runs over it as it is and, in its CLAIMED form, over the second, where it makes, tests
                 // and shades the rays itself.  Per pass: `active` shrinks between passes
                 const uint32_t nwords = n_pad / 64;
                 unsigned int *cnt = ws.unclaimed_u32.p, *offs = cnt + ws.unclaimed_words, *len = offs + ws.unclaimed_words;
@@ -689,7 +697,26 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
                 wk.unclaimed = ws.unclaimed.p, wk.unclaimed_count = len;
                 launches += 3;  // (the scan counted as one launch, whatever hipcub makes of it)
             }
-            LAUNCH_TRY(launch_raygen(sc->dev, fr, wk, px, pa, s));
+            WorkDev wr = wk;
+            if (rays_settle_lists) {
+                // a run with list claims: k_raygen settles a listed pixel's rays where it forms them (its <0, true> form:
+                // the pixel's list and its members are wave-uniform there) and leaves the path ids of those the rule does not
+                // settle in the straggler list.  What walks the tree is the third ordered list, the unclaimed slots without
+                // a list, and the stragglers; the traversal kernel gets both below and no lists.  The straggler list lies in
+                // the id list of two-phase shading, which holds every path of a pass and which a fused run never uses
+                const uint32_t nwords = n_pad / 64;
+                unsigned int *cnt = ws.walk_u32.p, *offs = cnt + ws.unclaimed_words;
+                walk_len = offs + ws.unclaimed_words;
+                LAUNCH_TRY(launch_walk_words(act_cur, n_active, n_pad, job.claims, job.claim_lists, ws.walk_mask.p, cnt, s));
+                HIP_TRY((hipError_t)launch_live_compact(ws.walk_mask.p, cnt, nwords, offs, ws.walk_slots.p, walk_len, ws.unclaimed_tmp.p,
+                                                        ws.unclaimed_tmp_bytes, s));
+                HIP_TRY(hipMemsetAsync(qi[2].counts, 0, 4, s));
+                wr.qids.ids = qi[2].ids, wr.qids.counts = qi[2].counts;
+                wr.qids.sub_capacity = (uint32_t)std::min<uint64_t>((uint64_t)qi[2].sub_capacity * kSubQueues, 0xFFFFFFFFull);
+                launches += 2;
+            }
+            LAUNCH_TRY(launch_raygen(sc->dev, fr, wr, px, pa, s));
+            if (rays_settle_lists) stragglers = wr.qids;
         }
         if (tn.sorted) {
             wk.out_rec = ws.out_rec.p, wk.out_count = ws.out_count.p, wk.out_ctr = ws.counters.p, wk.out_capacity = (uint32_t)ws.out_capacity;
@@ -701,6 +728,10 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
         {
             WorkDev wt = wk;
             if (fuse) wt.claims = nullptr;  // no listed slot has a claim: the refill-time claim branch has nothing to look up
+            if (rays_settle_lists) {  // the walk slots in 8 bands, then the stragglers as a ninth source; the rule has run
+                wt.unclaimed = ws.walk_slots.p, wt.unclaimed_count = walk_len, wt.claim_lists = nullptr;
+                wt.qids = stragglers, wt.nsrc = 9;
+            }
             LAUNCH_TRY(launch_trace_q(sc->dev, fr, wt, px, pa, ws.counters.p, count, false, cfg, s));
         }
         if ((rc = timed_end(timed, s))) return rc;

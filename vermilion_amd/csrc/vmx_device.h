@@ -88,7 +88,7 @@ struct DevCounters {
     StageCounters stage[2];
     unsigned long long samples, discarded, pixels_done, overflow;
     unsigned long long fused;  // camera paths whose ray k_shade<0, .., DENSE> formed and tested itself (claimed pixels)
-    unsigned long long listed;  // camera rays that k_trace_w<0> settled by their pixel's list claim (pc_list_settle)
+    unsigned long long listed;  // camera rays settled by their pixel's list claim (pc_list_settle: k_raygen<0, true> in a fused pass, else k_trace_w<0>)
 };
 
 // Division of a 32-bit index by a launch constant (samples per pixel of a pass, image width, rows per stripe) as a

@@ -148,6 +148,10 @@ struct Workspace {
     DevBuf<unsigned long long> unclaimed_mask;
     DevBuf<unsigned char> unclaimed_tmp;
     size_t unclaimed_words = 0, unclaimed_tmp_bytes = 0;
+    // ... and, in a run with list claims, the ordered list of the walk slots (unclaimed, no list): the same three, with
+    // the scan scratch above.  (The straggler list of such a pass lies in ids[2], which only two-phase shading uses.)
+    DevBuf<unsigned int> walk_slots, walk_u32;
+    DevBuf<unsigned long long> walk_mask;
     DevBuf<unsigned char> rad;          // float4 per path of a pass
     DevBuf<unsigned long long> rad_mask;  // split pipeline: one bit per path, "its radiance was stored" (PathArrays::rad_mask)
     // VMX_SAMPLING_ELIDE_DEAD: live bits per 64 paths; [popcounts | their exclusive scan | list length]; the list; scan scratch

@@ -96,7 +96,11 @@ struct WorkDev {
     // one triangle test in k_trace_w<0> instead of the BVH walk
     const unsigned int *claims;
     // ... and one list record (kListWords words) per local pixel or NULL: the rays of a pixel without a claim that
-    // pc_list_settle settles skip the walk too; list_ctr: the frame's counters (DevCounters::listed)
+    // pc_list_settle settles skip the walk too; list_ctr: the frame's counters (DevCounters::listed).  Who runs the rule: in
+    // a pass that fuses its claimed pixels k_raygen<0, true>, on the ray it forms (it is handed the lists and, in qids —
+    // ids, counts[0], sub_capacity —, the straggler list for the path ids of the rays the rule leaves to the walk; the
+    // traversal kernel is then handed no lists, the walk slots as `unclaimed`, and the stragglers in qids as its last
+    // source, nsrc = bands + 1); in every other form k_trace_w<0> at refill time
     const unsigned int *claim_lists;
     DevCounters *list_ctr;
     // fused claimed pixels (render_pass; plain dense camera pass with claims): k_raygen<0> and k_trace_w<0> work on the
@@ -241,6 +245,14 @@ int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, u
                       unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, void *stream);
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
                            unsigned long long *mask, unsigned int *cnt, void *stream);
+// ... and, in a run with list claims, of the walk slots: the unclaimed slots whose pixel has no list either (lists: the
+// list records, kListWords words per local pixel).  One word of their bits and its popcount per 64 slots, then
+// launch_live_compact: the ordered list and its length.  k_trace_w<0> works on that list and on the straggler list that
+// k_raygen<0, true> leaves in wk.qids (ids, counts[0], sub_capacity) — launch_raygen launches that form when it is handed
+// unclaimed, claim_lists and qids.ids; launch_trace_q's kernel takes the stragglers as its last source when qids.ids is
+// set (nsrc = the bands + 1)
+int launch_walk_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
+                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, void *stream);
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
                    DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide = nullptr,
                    unsigned int *visits = nullptr);

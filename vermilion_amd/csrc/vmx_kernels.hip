@@ -9,8 +9,11 @@
 //   k_trace        BVH::getIntersection for explicit rays          (bvh.cpp:47-145)
 //   k_raycast      MeshEngine::RayCast for explicit rays           (meshEngine.cpp:239-509)
 //   k_raygen       camera rays of a pass, each with the step_bits of its first Radiance step (pathtracer.cpp:251-280);
-//                  <1> + k_raygen_live: only the live ones (VMX_SAMPLING_ELIDE_DEAD, with path_compact.hip)
-//   k_trace_w      persistent BVH traversal of camera / bounce rays (bvh.cpp:47-145); <.., SORT>: settles the finished rays
+//                  <1> + k_raygen_live: only the live ones (VMX_SAMPLING_ELIDE_DEAD, with path_compact.hip);
+//                  <0, true>: settles the rays of pixels with a list claim itself (pc_list_settle), in a pass that fuses its claimed pixels
+//   k_trace_w      persistent BVH traversal of camera / bounce rays (bvh.cpp:47-145); <0> settles a camera ray by its pixel's
+//                  claim or list at refill time, except where the pass handed it only the rays that walk (the slots without
+//                  claim or list, and the stragglers of k_raygen<0, true>); <.., SORT>: settles the finished rays
 //                  whose step ends by its draws, hands the others on as records (DESIGN_HISTORY.md 5.1); k_trace_q: counting form
 //   k_shade        RayCast tail + one Radiance step, id compaction  (meshEngine.cpp:365-508, pathtracer.cpp:36-196);
 //                  k_shade_ends: the two-phase form's first phase
@@ -1895,6 +1898,23 @@ k_unclaimed_words(const unsigned int *__restrict__ active, uint32_t n_active, ui
     }
 }
 
+// k_walk_words — the same for the third list of such a pass when the run has list claims: the bits of the slots whose
+// pixel has neither a claim nor a list.  Every ray of such a pixel walks the tree, so these slots, in order, are what
+// k_trace_w<0> works on; the rays of the other unclaimed pixels are settled where they are formed (k_raygen<0, true>).
+__global__ void __launch_bounds__(256)
+k_walk_words(const unsigned int *__restrict__ active, uint32_t n_active, uint32_t n_pad, const unsigned int *__restrict__ claims,
+             const unsigned int *__restrict__ lists, unsigned long long *__restrict__ mask, unsigned int *__restrict__ cnt) {
+    for (uint32_t s_idx = blockIdx.x * blockDim.x + threadIdx.x; s_idx < n_pad; s_idx += gridDim.x * blockDim.x) {
+        bool walk = false;
+        if (s_idx < n_active) {
+            const uint32_t lp = active[s_idx];
+            walk = claims[lp] == kClaimNone && lists[(size_t)lp * kListWords] == kClaimNone;
+        }
+        const unsigned long long bits = __builtin_amdgcn_ballot_w64(walk);
+        if ((threadIdx.x & 63u) == 0) mask[s_idx >> 6] = bits, cnt[s_idx >> 6] = (uint32_t)__popcll(bits);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // k_raygen — camera rays of one pass (pathtracer.cpp:251-280), written to rayA[pid] as
 // (direction, flag word): all camera rays share the frame's origin, so 16 bytes per ray suffice.
@@ -1904,10 +1924,19 @@ k_unclaimed_words(const unsigned int *__restrict__ active, uint32_t n_active, ui
 // LIVE 0: every camera ray of the pass, rayA[pid].   LIVE 1 (VMX_SAMPLING_ELIDE_DEAD): nothing is written but one word
 // of live bits and its popcount per 64 consecutive path ids; launch_live_compact turns those into the ordered list of
 // live path ids and k_raygen_live writes their rays, densely, to rayA[position in that list].
-template <int LIVE>
+// LISTS (LIVE 0; a pass that fuses its claimed pixels in a run with list claims, pixel-major, whole chunks of 64): the
+// kernel settles the rays of a listed pixel where it forms them.  A wave's rays are samples of ONE pixel, so the pixel's
+// list record and its members' camera-relative records are wave-uniform and come through the scalar cache; every lane
+// with a sample runs pc_list_settle (pixel_claim.h: the function and the operands of k_trace_w<0>'s refill branch, so
+// the same rays settle with the same bits) on the direction it stores.  A settled lane writes hit[pid] beside its ray;
+// the path id of any other goes to the straggler list (wk.qids: ids, counts[0], sub_capacity), which k_trace_w<0>
+// traces as a work source of its own.  The pixels without a list are left to that kernel's walk-slot list.
+template <int LIVE, bool LISTS = false>
 __global__ void __launch_bounds__(256)
 k_raygen(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa) {
+    static_assert(!LISTS || !LIVE, "list pixels are settled in the plain form");
     const uint32_t total = wk.samples * wk.n_pad;
+    [[maybe_unused]] uint32_t n_listed = 0;  // (wave-uniform) LISTS: rays settled by their pixel's list
     if (wk.pixel_major && (wk.samples & 63u) == 0) {
         // a wave's 64 path ids are 64 samples of ONE pixel: slot, pixel and cursor are wave-uniform — one division and one
         // scalar fetch each per wave instead of per lane (round 3: 3.2 -> 2.9 ms for the 530.8 M rays of the bench frame)
@@ -1933,6 +1962,10 @@ k_raygen(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa) 
                 const bool lights = (LIVE || fr.camera_bits) && pixel_may_reach_a_light(sc, fr, pixel);
                 const uint32_t cur = px.cursor[lp];  // (sample_index, with the cursor fetched once)
                 const uint32_t k0 = cur & ~kCursorStrided, kstep = (cur & kCursorStrided) ? fr.quarter : 1u;
+                // LISTS: the pixel's list record, one scalar fetch (an empty list: the pixel's rays walk, k_trace_w<0>)
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                [[maybe_unused]] u32x4 lrec = {kClaimNone, kClaimNone, kClaimNone, kClaimNone};
+                if constexpr (LISTS) lrec = ((const __attribute__((address_space(4))) u32x4 *)(uintptr_t)wk.claim_lists)[lp];
                 for (uint32_t ch = 0; ch < chunks; ++ch) {
                     const uint32_t j = ch * 64u + lane;
                     const uint32_t k = (fr.lead != 0 && j >= fr.lead) ? (j - fr.lead + 1u) * fr.quarter : k0 + j * kstep;
@@ -1960,6 +1993,32 @@ k_raygen(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa) 
                         const unsigned long long bits = __builtin_amdgcn_ballot_w64(live);
                         if (lane == 0) wk.live_mask[(pid_base >> 6) + ch] = bits, wk.live_cnt[(pid_base >> 6) + ch] = (uint32_t)__popcll(bits);
                     }
+                    if constexpr (LISTS) {
+                        if (lrec.x != kClaimNone) {  // (wave-uniform)
+                            // the member records are read at wave-uniform addresses of the frame's constant triangle
+                            // table: through the scalar cache, as the CLAIMED form of k_shade<0> takes its claimed triangle
+                            const float *ctris = (const float *)(const __attribute__((address_space(4))) float *)(uintptr_t)wk.cam_tris;
+                            const bool has = depth != 0xFFFFFFFFu;  // the slot has a sample
+                            float t = 0.f;
+                            uint32_t m = 0;
+                            const bool settled = has && pc_list_settle(ctris, lrec.x, lrec.y, lrec.z, lrec.w, dx, dy, dz, t, m);
+                            if (settled) ((float2 *)pa.hit)[pid_base + j] = make_float2(t, __int_as_float((int)m));
+                            n_listed += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(settled));
+                            // the stragglers' path ids: one ballot, and one atomic per chunk that has any
+                            const bool strag = has && !settled;
+                            const unsigned long long sm = __builtin_amdgcn_ballot_w64(strag);
+                            if (sm != 0) {
+                                uint32_t base = 0;
+                                if (lane == 0) base = atomicAdd(wk.qids.counts, (uint32_t)__popcll(sm));
+                                base = __builtin_amdgcn_readfirstlane(base);
+                                const uint32_t at = base + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
+                                // (the list holds every path id of a pass: `at` stays below its end; an entry that would
+                                // not is reported instead of written, as k_trace_w's fallback_append reports one)
+                                if (strag && at < wk.qids.sub_capacity) wk.qids.ids[at] = pid_base + j;
+                                else if (strag) atomicAdd(&wk.list_ctr->overflow, 1ull);
+                            }
+                        }
+                    }
                 }
             } else {
                 // padding slots of the pass: marked like sample slots past a pixel's last sample
@@ -1968,6 +2027,9 @@ k_raygen(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, PathArrays pa) 
                     if (LIVE && lane == 0) wk.live_mask[(pid_base >> 6) + ch] = 0ull, wk.live_cnt[(pid_base >> 6) + ch] = 0u;
                 }
             }
+        }
+        if constexpr (LISTS) {
+            if (lane == 0 && n_listed) atomicAdd(&wk.list_ctr->listed, (unsigned long long)n_listed);
         }
         return;
     }
@@ -3514,7 +3576,18 @@ int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pix
     uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256u * 32u);
     if (grid == 0) grid = 1;
     if (wk.live_mask) hipLaunchKernelGGL(k_raygen<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
-    else hipLaunchKernelGGL(k_raygen<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
+    else if (wk.unclaimed && wk.claim_lists && wk.qids.ids) {
+        // a fused pass of a run with list claims (render_pass): the form that settles the listed pixels' rays itself
+        if (!wk.pixel_major || (wk.samples & 63u) != 0 || !wk.cam_tris || !wk.list_ctr || !wk.qids.counts) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_raygen<0, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
+    } else hipLaunchKernelGGL(k_raygen<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
+    return launch_status();
+}
+
+int launch_walk_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
+                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, void *stream) {
+    const uint32_t grid = std::max(1u, std::min<uint32_t>((n_pad + 255) / 256, 4096u));
+    hipLaunchKernelGGL(k_walk_words, dim3(grid), dim3(256), 0, (hipStream_t)stream, active, n_active, n_pad, claims, lists, mask, cnt);
     return launch_status();
 }
 

@@ -271,9 +271,11 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa, GuideDev gd) {
                         const uint32_t n = *wk.live_count, seg = live_band(n);
                         lim = min(seg, n - min(n, src * seg));
                     }
-                    if (SRC == 0 && !LIVE && !SORT && wk.unclaimed) {  // the pass's unclaimed slots, in nsrc bands of the ordered list
-                        const uint32_t n = *wk.unclaimed_count, seg = (n + nsrc - 1u) / nsrc;
-                        lim = min(seg, n - min(n, src * seg)) * wk.samples;
+                    if (SRC == 0 && !LIVE && !SORT && wk.unclaimed) {  // the pass's listed slots, in bands of the ordered list
+                        // (wk.qids.ids: the last source is the straggler list k_raygen<0, true> left, path ids in any order)
+                        const uint32_t nband = wk.qids.ids ? nsrc - 1u : nsrc;
+                        const uint32_t n = *wk.unclaimed_count, seg = (n + nband - 1u) / nband;
+                        lim = src == nband ? min(wk.qids.counts[0], wk.qids.sub_capacity) : min(seg, n - min(n, src * seg)) * wk.samples;
                     }
                     uint32_t base = 0;
                     if (lane == 0) base = atomicAdd(&wk.heads[src * 32], kReserve);
@@ -307,20 +309,31 @@ k_trace_w(SceneDev sc, FrameDev fr, WorkDev wk, PathArrays pa, GuideDev gd) {
                         pid = src * live_band(*wk.live_count) + item;  // list position
                     } else if (SRC == 0) {
                         uint32_t j, s_idx;
+                        bool straggler = false;  // (wave-uniform) a path id of the straggler list: a ray of a listed pixel that its list did not settle
                         if (!SORT && wk.unclaimed) {  // (a fused pass is pixel-major) band-local item -> (list entry, sample)
-                            const uint32_t sl = fast_div(item, wk.div_samples), n = *wk.unclaimed_count;
-                            j = item - sl * wk.samples, s_idx = wk.unclaimed[src * ((n + nsrc - 1u) / nsrc) + sl];
+                            const uint32_t nband = wk.qids.ids ? nsrc - 1u : nsrc;
+                            if (src == nband) {
+                                straggler = true, j = 0, s_idx = 0;
+                            } else {
+                                const uint32_t sl = fast_div(item, wk.div_samples), n = *wk.unclaimed_count;
+                                j = item - sl * wk.samples, s_idx = wk.unclaimed[src * ((n + nband - 1u) / nband) + sl];
+                            }
                         } else if (wk.pixel_major) {
                             const uint32_t sl = fast_div(item, wk.div_samples);
                             j = item - sl * wk.samples, s_idx = src * band_slots + sl;
                         } else {
                             j = item / band_slots, s_idx = src * band_slots + (item - j * band_slots);
                         }
-                        valid = s_idx < wk.n_active;
-                        pid = path_id(wk, j, s_idx);
-                        if (wk.claims && valid) claim = wk.claims[wk.active[s_idx]];
-                        // (a fused pass hands no claims on — its listed slots have none — but the lists, if the run has any)
-                        if (wk.claim_lists && valid && claim == kClaimNone) lrec = ((const uint4 *)wk.claim_lists)[wk.active[s_idx]];
+                        if (!SORT && straggler) {
+                            pid = wk.qids.ids[item];  // (its pixel is active and unclaimed, and its list has had its say)
+                        } else {
+                            valid = s_idx < wk.n_active;
+                            pid = path_id(wk, j, s_idx);
+                            if (wk.claims && valid) claim = wk.claims[wk.active[s_idx]];
+                            // (a fused pass hands no claims on — its listed slots have none — and no lists either where
+                            // k_raygen<0, true> has run the rule: then the listed slots are the walk slots)
+                            if (wk.claim_lists && valid && claim == kClaimNone) lrec = ((const uint4 *)wk.claim_lists)[wk.active[s_idx]];
+                        }
                     } else {
                         pid = wk.qids.ids[(size_t)src * wk.qids.sub_capacity + item];
                     }
