@@ -4,7 +4,9 @@
 //
 //   g++ -std=c++17 -I include examples/render_cornell.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_cornell     (done by __graft_entry__.build())
-//   ./examples/render_cornell out.ppm 256 256 64 [seed]
+//   ./examples/render_cornell out.ppm 256 256 64 [seed] [--nee]
+// --nee: the light-sampling integrator (vmx_render_nee: VMX_SAMPLING_CORRECTED, every diffuse step samples the emitters)
+// instead of PathTracer::Render.
 //
 // Writes a binary PPM the way Camera::saveFrame quantises (floor(x*255), core/camera/camera.cpp:150-170)
 // and prints the statistics the reference cannot report (camera.h:101-102 are never incremented).
@@ -35,6 +37,13 @@ void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &
 }  // namespace
 
 int main(int argc, char **argv) {
+    bool nee = false;
+    int kept = 1;
+    for (int i = 1; i < argc; ++i) {  // --nee may stand anywhere: the positional arguments close up
+        if (std::strcmp(argv[i], "--nee") == 0) nee = true;
+        else argv[kept++] = argv[i];
+    }
+    argc = kept;
     const char *out = argc > 1 ? argv[1] : "cornell.ppm";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 64;
@@ -70,7 +79,8 @@ int main(int argc, char **argv) {
     opts.sampling = VMX_SAMPLING_PARITY;
     std::vector<float> frame((size_t)W * H * 5);
     vmx_stats st;
-    if (vmx_render(scene, &cam, &opts, frame.data(), &st) != VMX_OK) {
+    if (nee) opts.early_stop = 0, opts.sampling = VMX_SAMPLING_CORRECTED;
+    if ((nee ? vmx_render_nee(scene, &cam, &opts, frame.data(), &st) : vmx_render(scene, &cam, &opts, frame.data(), &st)) != VMX_OK) {
         std::fprintf(stderr, "render: %s\n", vmx_last_error());
         vmx_scene_destroy(scene);
         return 1;

@@ -171,7 +171,7 @@ typedef struct vmx_stats {
 #define VMX_K_FUSED 6         /* k_paths<0>: whole small passes in one fused kernel        */
 #define VMX_K_RESOLVE 7       /* k_resolve                                                 */
 #define VMX_K_BRUTEFORCE 8    /* k_bruteforce                                              */
-#define VMX_K_OTHER 9         /* k_pixel_claims; first-generation kernels (pipeline forms 2, 3) */
+#define VMX_K_OTHER 9         /* k_pixel_claims; k_nee (vmx_render_nee*, vmx_radiance_nee); first-generation kernels (pipeline forms 2, 3) */
 #define VMX_K_COUNT 10
 typedef struct vmx_timings {
     double ms[VMX_K_COUNT];          /* summed over the launches of the call */
@@ -1155,6 +1155,50 @@ int vmx_render_bruteforce(const vmx_scene *scene, const vmx_camera *cam, const v
                           float *out_rgbaz, vmx_stats *stats);
 int vmx_render_bruteforce_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags,
                                  void *d_out_rgbaz, void *stream, vmx_stats *stats);
+
+/* ---- light sampling: a path integrator with next-event estimation ---------------------------
+ * A third integrator entry beside vmx_render* and vmx_render_bruteforce*; this build's own (the reference has none).
+ * Under VMX_SAMPLING_CORRECTED a path of vmx_render collects light only by hitting a VMX_SPHERE_EMIT sphere by chance.
+ * Here every diffuse step samples the emitters directly.  The estimator is Radiance (pathtracer.cpp:21-198) with r2 = U
+ * and one more bit of state per path, `lit`, false at the start:
+ *   1. RayCast; a miss returns.
+ *   2. !lit: accumColour += accumRadiance * hitColour.  At depth 0, accumColour.w = distance.
+ *   3. length(hitColour) > 1 returns, lit or not (the path distribution stays that of `corrected`).
+ *   4. Russian roulette, the texture sample, the branch draw and the arms follow the reference draw for draw, the three
+ *      unused draws of an arm included.  The specular arm sets lit = false.
+ *   5. A diffuse arm (triangle or sphere) has w, the flipped normal, has multiplied accumRadiance by the sample colour
+ *      (triangle arm), moves the origin to x = hit - dir * 0.001 and draws the bounce direction.
+ *   6. It then runs the emitter loop over the VMX_SPHERE_EMIT spheres in table order, float32 unless stated:
+ *        op_i = c_i - x, C_i = dot(op_i, op_i), R2_i = r_i * r_i, as sphereIntersect forms them.
+ *        If C_i <= R2_i for any emitter (x inside or on it): no draw is consumed and lit = false.
+ *        Else for every emitter i two draws xi1, xi2 (always consumed), then in DOUBLE
+ *          s2 = R2_i / C_i,  q_i = s2 / (1 + sqrt(1 - s2)),  Omega = 2 pi q_i,
+ *          z = xi1 q_i,  cos t = 1 - z,  sin t = sqrt(z (2 - z));
+ *        phi = float(2 pi xi2), its cosine and sine by cosf / sinf (VMX_SAMPLING_LIBM_DOUBLE: C's double functions);
+ *        a_i = normalize(op_i), u = normalize(cross(|a.x| > .1 ? (0,1,0) : (1,0,0), a)), v = cross(a, u);
+ *        omega = normalize((u cos(phi) float(sin t) + v sin(phi) float(sin t)) + a float(cos t)).
+ *        The sample is dropped if 0.5 * double(|omega - a_j|^2) <= q_j for an emitter j < i (overlapping cones count
+ *        once: the earlier emitter's sample owns the direction), or if dot(w, omega) <= 0.  Otherwise RayCast(x, omega)
+ *        and accumColour.rgb += (accumRadiance.rgb * hitColour) * float(double(dot(w, omega)) / pi * Omega).
+ *        Then lit = true.
+ * RayCast's own hitColour is used, so the reference's quirks stay: an emitter shines through a nearer non-emitting
+ * sphere that the table lists after it, and a later nearer triangle-less wall never clears the colour.
+ *
+ * vmx_opts: (sampling & VMX_SAMPLING_MODE_MASK) must be VMX_SAMPLING_CORRECTED (parity's r2 = 10 U has no estimator to
+ * improve); VMX_SAMPLING_LIBM_DOUBLE is honoured; seed and samples_per_batch apply as in vmx_render.  VMX_ERR_INVALID,
+ * with a message naming it, for VMX_SAMPLING_ELIDE_DEAD, early_stop != 0, world > 1, collect_counters and a non-zero
+ * reserved[0].  Frame layout as vmx_render: W * H * 5 floats, rgb = clamp(sum / n, 0, 1) with the samples added in
+ * ascending k, alpha 1, the fifth float n; sample k of pixel p uses the stream keyed (seed, p, k): two jitter draws,
+ * then the path.  vmx_stats: rays_primary as vmx_render, rays_secondary = bounce rays + the shadow rays traced, samples.
+ * vmx_render_nee_device follows vmx_render_device's stream and output conventions.  vmx_radiance_nee treats ray i as
+ * vmx_radiance does: stream (seed, i, 0) past its two jitter draws, unclamped accumColour, w = primary hit distance.
+ * Valid after vmx_scene_update*, vmx_scene_set_spheres and vmx_scene_bind_texture, on scenes of any builder.
+ */
+int vmx_render_nee(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats);
+int vmx_render_nee_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz,
+                          vmx_stats *stats, void *stream);
+int vmx_radiance_nee(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
+                     float *out4, vmx_stats *stats);
 
 /* ---- frame output (the step after the path; replaces the conversion loop of
  * Camera::saveFrame, core/camera/camera.cpp:140-175, for the default RGBAZ mode) ------------ */

@@ -1,0 +1,181 @@
+// api_nee.inc — part of vmx_api.cpp: the light-sampling integrator, vmx_render_nee* and vmx_radiance_nee (k_nee, vmx_nee.inc)
+namespace {
+
+// what the entries accept of a vmx_opts (include/vermilion_hip.h, "light sampling")
+int nee_check_opts(const vmx_opts *o) {
+    if ((o->sampling & VMX_SAMPLING_MODE_MASK) > VMX_SAMPLING_CORRECTED ||
+        (o->sampling & ~(VMX_SAMPLING_MODE_MASK | VMX_SAMPLING_LIBM_DOUBLE | VMX_SAMPLING_ELIDE_DEAD)))
+        return fail(VMX_ERR_INVALID, "unknown sampling mode");
+    if (o->sampling & VMX_SAMPLING_ELIDE_DEAD) return fail(VMX_ERR_INVALID, "light sampling: VMX_SAMPLING_ELIDE_DEAD does not apply");
+    if ((o->sampling & VMX_SAMPLING_MODE_MASK) != VMX_SAMPLING_CORRECTED)
+        return fail(VMX_ERR_INVALID, "light sampling: sampling must be VMX_SAMPLING_CORRECTED");
+    if (o->early_stop) return fail(VMX_ERR_INVALID, "light sampling: early_stop is not supported");
+    if (o->world > 1) return fail(VMX_ERR_INVALID, "light sampling: world > 1 is not supported");
+    if (o->collect_counters) return fail(VMX_ERR_INVALID, "light sampling: collect_counters is not supported");
+    if (o->reserved[0]) return fail(VMX_ERR_INVALID, "light sampling: reserved[0] must be 0");
+    return VMX_OK;
+}
+
+// the stack and the persistent grid of a k_nee launch over `items` work items
+int nee_launch_cfg(vmx_scene *sc, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg) {
+    int blocks = 0;
+    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks));
+    if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
+    cfg = paths_cfg(sc, tn.lds_entries, items, blocks);
+    return bind_stack(sc, tn, tn.lds_entries, cfg.grid, items, wk);
+}
+
+// One frame: vmx_render's set-up, per-pixel state, batching by samples_per_batch and k_resolve; each pass's paths run in
+// k_nee, which leaves their radiance in the workspace's `rad`
+int nee_render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, float *d_out, hipStream_t s, vmx_stats *stats) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RenderJob job;
+    int rc = render_setup(sc, cam, opts, &sc->ws.pixels, d_out, s, job);
+    if (rc) return rc;
+    if (job.npix == 0) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return VMX_OK;
+    }
+    Workspace &ws = sc->ws;
+    const FrameDev &fr = job.fr;
+    if ((rc = sc->upd.done.wait(s))) return rc;
+    ws.events.reset();
+    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
+    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(ev0, s));
+    if (ws.heads.ensure(kSubQueues * 32) || ws.rad.ensure((size_t)job.n_pad_max * job.smax * 16) || ws.next_count.ensure(32) ||
+        ws.counters.ensure(1))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the render workspace");
+    HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+    if ((rc = render_init_pixels(sc, job))) return rc;
+    const PixelStateDev px{job.pixels->accum.p, job.pixels->count.p, job.pixels->cursor.p};
+    uint32_t n_active = job.npix, done = 0;
+    int cur = 0;
+    while (n_active > 0 && done < fr.kmax) {
+        const uint32_t S = std::min(job.smax, fr.kmax - done);
+        const uint32_t n_pad = (n_active + 63u) & ~63u;
+        const uint64_t items = (uint64_t)n_pad * S;
+        WorkDev wk;
+        std::memset(&wk, 0, sizeof(wk));
+        wk.heads = ws.heads.p;
+        wk.active = job.pixels->active[cur].p;
+        wk.n_active = n_active, wk.n_pad = n_pad, wk.samples = S, wk.div_samples = make_fastdiv(S);
+        wk.pixel_major = 1;
+        LaunchCfg cfg;
+        if ((rc = nee_launch_cfg(sc, job.tn, items, false, wk, cfg))) return rc;
+        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
+        if ((rc = timed_begin(ws, job.timed, s, 0, VMX_K_OTHER))) return rc;
+        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, px, nullptr, nullptr, (uint32_t)items, ws.rad.p, ws.counters.p, cfg, s));
+        if ((rc = timed_end(job.timed, s))) return rc;
+        HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
+        if ((rc = timed_begin(ws, job.timed, s, -1, VMX_K_RESOLVE))) return rc;
+        LAUNCH_TRY(launch_resolve(fr, wk.active, n_active, S, true, ws.rad.p, nullptr, px, job.pixels->active[cur ^ 1].p, ws.next_count.p,
+                                  d_out, ws.counters.p, s));
+        if ((rc = timed_end(job.timed, s))) return rc;
+        unsigned int h_next[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h_next, ws.next_count.p, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_active = h_next[0];
+        cur ^= 1;
+        done += S;
+        job.launches += 2;
+        job.passes++;
+    }
+    HIP_TRY(hipEventRecord(ev1, s));
+    return finish_stats(sc, s, job.timed, ev0, ev1, stats, job.launches, job.passes, t0);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmx_render_nee_device(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz, vmx_stats *stats,
+                          void *stream) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!cam || !opts || !d_out_rgbaz) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts)) return rc;
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");  // (last: the checks above need no scene)
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
+    return nee_render_impl(sc, cam, opts, (float *)d_out_rgbaz, s, stats);
+}
+
+int vmx_render_nee(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!cam || !opts || !out_rgbaz) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts)) return rc;
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    FrameDev fr;
+    rc = make_frame(*cam, *opts, fr);
+    if (rc) return rc;
+    const size_t nfloats = (size_t)fr.width * fr.local_rows * 5;
+    if (sc->ws.out.ensure(nfloats)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the frame buffer");
+    rc = nee_render_impl(sc, cam, opts, sc->ws.out.p, sc->stream, stats);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_rgbaz, sc->ws.out.p, nfloats * 4, hipMemcpyDeviceToHost));
+    return VMX_OK;
+}
+
+int vmx_radiance_nee(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts, float *out4,
+                     vmx_stats *stats) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!origin || !dir || !opts || !out4) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts)) return rc;
+    if (n == 0) return VMX_OK;  // (nothing to do, whatever the scene)
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    Workspace &ws = sc->ws;
+    hipStream_t s = sc->stream;
+    if ((rc = sc->upd.done.wait(s))) return rc;
+    const Tuning tn = make_tuning(sc, opts);
+    FrameDev fr;
+    std::memset(&fr, 0, sizeof(fr));
+    fr.r2scale = 1.0f;
+    fr.libm_double = (opts->sampling & VMX_SAMPLING_LIBM_DOUBLE) ? 1u : 0u;
+    fr.seed = opts->seed;
+    DevBuf<float> d_o, d_d;
+    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || ws.rad.ensure((size_t)n * 16) || ws.heads.ensure(kSubQueues * 32) ||
+        ws.counters.ensure(1))
+        return fail(VMX_ERR_NOMEM, "hipMalloc failed");
+    WorkDev wk;
+    std::memset(&wk, 0, sizeof(wk));
+    wk.heads = ws.heads.p;
+    LaunchCfg cfg;
+    if ((rc = nee_launch_cfg(sc, tn, n, true, wk, cfg))) return rc;
+    ws.events.reset();
+    std::vector<TimedLaunch> timed;
+    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
+    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
+    auto body = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_o.p, origin, (size_t)n * 12, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_d.p, dir, (size_t)n * 12, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev0, s));
+        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
+        int r;
+        if ((r = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return r;
+        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o.p, d_d.p, n, ws.rad.p, ws.counters.p, cfg, s));
+        if ((r = timed_end(timed, s))) return r;
+        HIP_TRY(hipEventRecord(ev1, s));
+        HIP_TRY(hipMemcpyAsync(out4, ws.rad.p, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+        return finish_stats(sc, s, timed, ev0, ev1, stats, 1, 1, t0);
+    };
+    rc = body();
+    if (rc) (void)hipStreamSynchronize(s);  // (what was enqueued may still use d_o / d_d, which are freed here)
+    if (rc == VMX_OK && stats) stats->samples = n;
+    return rc;
+}
+
+}  // extern "C"

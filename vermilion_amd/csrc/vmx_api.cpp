@@ -40,6 +40,7 @@ using namespace vmx;
 #include "vmx_host.h"          // shared: error reporting, the owners of device resources, the scene and its workspace, frame set-up
 #include "api_ab.inc"          // what only the A/B library runs, behind ab_* hooks (the host side's one VMX_AB_KERNELS conditional)
 #include "api_render.inc"      // the pass loop, BruteForceTracer; vmx_render*, vmx_local_rows
+#include "api_nee.inc"         // light sampling: vmx_render_nee*, vmx_radiance_nee
 #include "api_scene.inc"       // vmx_scene_create / destroy / bind_texture / describe / timings / bvh
 #include "api_query.inc"       // vmx_trace, vmx_raycast*, vmx_query*, vmx_primary_ids, vmx_radiance, vmx_trig
 #include "api_image.inc"       // shared by the image-space entries below: handle, overlap and params checks; vmx_variance_default_params

@@ -412,6 +412,13 @@ struct SphereMotionDev {
 };
 int launch_motion_spheres(const void *rayhit, uint32_t n, const SphereMotionDev &tb, const void *motion_in, void *out,
                           void *stream);
+// light sampling (vmx_nee.inc; the estimator is stated in include/vermilion_hip.h): the persistent kernel k_nee.  wk: heads
+// (its first counter, zeroed before the launch), reserve and the stack fields; camera paths (o == NULL): active, n_active,
+// samples, div_samples, and `items` = padded slots * samples path ids, numbered pixel-major as k_resolve reads `rad`;
+// explicit rays (o, d): ray i on stream (fr.seed, i, 0), `items` of them, rad[i] its accumColour
+int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, const float *o, const float *d,
+               uint32_t items, void *rad, DevCounters *counters, LaunchCfg cfg, void *stream);
+int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

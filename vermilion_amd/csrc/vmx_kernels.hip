@@ -3841,6 +3841,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 #include "vmx_motion.inc"
 // ... and for pixels on an analytic sphere that vmx_scene_set_spheres moved
 #include "vmx_motion_spheres.inc"
+// light sampling: the path integrator with next-event estimation
+#include "vmx_nee.inc"
 
 #ifdef VMX_AB_KERNELS
 // first-generation kernels (pipeline forms 2, 3): only in the A/B library of `make ab`, never in the product

@@ -785,6 +785,33 @@ class Scene:
                                           C.c_void_p(stream_ptr or 0), C.byref(st)))
         return st.as_dict()
 
+    # -- light sampling -----------------------------------------------------------
+    def render_nee(self, cam, opts):
+        """vmx_render_nee: the path integrator with next-event estimation (opts.sampling: VMX_SAMPLING_CORRECTED, no
+        early stop) into a host array [H, W, 5] (RGBAZ, the fifth float the sample count)."""
+        out = np.empty((cam.image_res[1], cam.image_res[0], 5), np.float32)
+        st = L.Stats()
+        self._check(self._lib.vmx_render_nee(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def render_nee_device(self, cam, opts, d_out_ptr, stream_ptr=None):
+        """Same, into device memory (e.g. a torch tensor's data_ptr()) on `stream_ptr`."""
+        st = L.Stats()
+        self._check(self._lib.vmx_render_nee_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(d_out_ptr), C.byref(st),
+                                                    C.c_void_p(stream_ptr or 0)))
+        return st.as_dict()
+
+    def radiance_nee(self, origin, direction, opts):
+        """vmx_radiance_nee: light-sampled Radiance of explicit camera rays, ray i on stream (seed, i, 0): unclamped
+        accumColour [n, 4] (w: the primary hit distance) and the call's statistics."""
+        o, d = _f32(origin, 3), _f32(direction, 3)
+        n = o.shape[0]
+        out = np.empty((n, 4), np.float32)
+        st = L.Stats()
+        self._check(self._lib.vmx_radiance_nee(self._h, o.ctypes.data, d.ctypes.data, n, C.byref(opts), out.ctypes.data,
+                                               C.byref(st)))
+        return out, st.as_dict()
+
 
 class Progressive:
     """One vmx_progressive handle: `step` issues samples, `preview` shows the frame so far, and the frame a completed
