@@ -13,6 +13,12 @@
 //     still uncertain, by the library's default parameters — until the mean count per pixel reaches the given spp or
 //     nothing is selected any more, and the final PREVIEW is written: unfinished pixels show the mean of their own samples.
 //
+//   ./examples/render_progressive --nee [--budget] out.ppm 256 256 16 [seed [samples_per_step [frame.f32]]]
+//     light sampling: the handle is begun with vmx_progressive_begin_nee (VMX_SAMPLING_CORRECTED, fixed spp) and ends at
+//     vmx_render_nee's frame.  With --budget it works as --adaptive does, but after the 8 uniform samples every step is one
+//     vmx_progressive_step_budgeted: each pixel takes the number of samples its own error asks for, at most
+//     samples_per_step (max_step), in one pass.  --nee --adaptive: vmx_progressive_step_adaptive on the light-sampled handle.
+//
 // Writes the last preview's rgba8 form as a binary PPM (Camera::saveFrame's quantisation, done on the device) and,
 // if a third file name is given, the RGBAZ floats of the frame as they are.
 #include <cmath>
@@ -42,13 +48,15 @@ void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool adaptive = false;
-    for (int i = 1; i < argc; ++i)
-        if (!std::strcmp(argv[i], "--adaptive")) {
-            adaptive = true;
+    bool adaptive = false, nee = false, budget = false;
+    for (int i = 1; i < argc; ++i) {
+        const bool a = !std::strcmp(argv[i], "--adaptive"), n = !std::strcmp(argv[i], "--nee"), b = !std::strcmp(argv[i], "--budget");
+        if (a || n || b) {
+            adaptive = adaptive || a || b, nee = nee || n || b, budget = budget || b;  // (budgeted steps are light-sampled and adaptive)
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc, --i;
         }
+    }
     const char *out = argc > 1 ? argv[1] : "cornell.ppm";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 64;
@@ -82,10 +90,15 @@ int main(int argc, char **argv) {
     vmx_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.seed = seed;
-    opts.early_stop = adaptive ? 0 : 1;  // (selected steps need the fixed-spp schedule)
-    opts.sampling = VMX_SAMPLING_PARITY;
+    opts.early_stop = adaptive || nee ? 0 : 1;  // (selected steps need the fixed-spp schedule; light sampling has no other)
+    opts.sampling = nee ? VMX_SAMPLING_CORRECTED : VMX_SAMPLING_PARITY;
+    vmx_sampling_budget_params bprm;
+    vmx_sampling_budget_default_params(&bprm);
+    bprm.max_step = per_step;
     vmx_progressive *job = nullptr;
-    if (vmx_progressive_begin_ex(scene, &cam, &opts, adaptive ? VMX_PROGRESSIVE_MOMENTS : 0u, nullptr, &job) != VMX_OK) {
+    const uint32_t flags = adaptive ? VMX_PROGRESSIVE_MOMENTS : 0u;
+    if ((nee ? vmx_progressive_begin_nee(scene, &cam, &opts, flags, nullptr, &job)
+             : vmx_progressive_begin_ex(scene, &cam, &opts, flags, nullptr, &job)) != VMX_OK) {
         std::fprintf(stderr, "begin: %s\n", vmx_last_error());
         vmx_scene_destroy(scene);
         return 1;
@@ -100,7 +113,8 @@ int main(int argc, char **argv) {
         vmx_stats st;
         if (adaptive && info.steps > 0) {
             uint32_t selected = 0;
-            if ((rc = vmx_progressive_step_adaptive(job, per_step, nullptr, &st, &selected)) != VMX_OK) break;
+            if ((rc = budget ? vmx_progressive_step_budgeted(job, &bprm, &st, &selected)
+                             : vmx_progressive_step_adaptive(job, per_step, nullptr, &st, &selected)) != VMX_OK) break;
             if (selected == 0) {  // every pixel is below the threshold: more steps would select nothing either
                 std::printf("converged: no pixel selected\n");
                 break;

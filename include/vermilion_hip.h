@@ -1111,8 +1111,9 @@ int vmx_multi_render_bruteforce(vmx_multi *m, const vmx_camera *cam, const vmx_o
  * select_device and step_adaptive are VMX_ERR_INVALID on a handle begun without VMX_PROGRESSIVE_MOMENTS.
  * Defaults (vmx_sampling_default_params): threshold 0.5f, floor 0.05f, min_samples 8, radius 1 — threshold and floor as
  * chosen from the grid of profiles/sampling_quality.txt.  tests/sampling_spec.py restates the arithmetic.
- * Out of scope: selection on early-stop handles, per-pixel sample budgets within one step, windows across ranks, adaptive
- * sampling inside vmx_render and vmx_multi_*. */
+ * Out of scope: selection on early-stop handles, per-pixel sample budgets on handles that are not light-sampled (the
+ * budgeted steps of the light sampling section), windows across ranks, adaptive sampling inside vmx_render and
+ * vmx_multi_*. */
 #define VMX_PROGRESSIVE_MOMENTS 1u
 int vmx_progressive_begin_ex(vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
                              vmx_progressive **out);
@@ -1199,6 +1200,63 @@ int vmx_render_nee_device(const vmx_scene *scene, const vmx_camera *cam, const v
                           vmx_stats *stats, void *stream);
 int vmx_radiance_nee(const vmx_scene *scene, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts,
                      float *out4, vmx_stats *stats);
+
+/* ---- light sampling in progressive handles, with per-pixel sample budgets ---------------------------------------------
+ * begin_nee: a vmx_progressive whose passes run the light-sampling integrator.  flags is 0 or VMX_PROGRESSIVE_MOMENTS; it
+ *   accepts exactly the vmx_opts vmx_render_nee accepts, with the same messages.  The refusals that need no device come
+ *   in the order cam / opts, out, flags, opts contents, frame, scene.  Every entry that takes a handle works on it with
+ *   its documented meaning: step, info_get, end, the plain, filtered and demodulated previews, state_device,
+ *   step_selected_device, error_device, select_device, step_adaptive; "scene updated since vmx_progressive_begin" and the
+ *   `failed` latch apply as on plain handles.  Sample k of local pixel p runs on stream (seed, p, k) and a pixel's samples
+ *   are folded in ascending k: whatever the schedule of steps, maps and budgets, a handle run to completion holds
+ *   vmx_render_nee's frame, bit for bit.  A moments handle folds l*l right after the three colour adds and is otherwise a
+ *   plain light-sampled handle bit for bit.
+ *
+ * Budgeted steps (handles begun with begin_nee only).  A selected step gives every selected pixel the same samples; the
+ * error statistic says how many each needs: the standard error of a mean falls as 1 / sqrt(n), so a pixel at error e with
+ * n samples needs about n (e / threshold)^2.  One budgeted step gives every pixel its own count, in ONE pass.
+ * B = the handle's effective samples_per_batch; cap = max_step ? min(max_step, B) : B.
+ * budget_device: d_budget[p], one uint32 per local pixel; d_total (one uint64, or NULL) receives their sum.  Enqueued on
+ *   the handle's stream without synchronising.  Per local pixel p, n = count, fn = (float)n, e_q exactly error_device's
+ *   error under select.floor; all float, one rounding per written operation, `/` correctly rounded, denormals kept:
+ *     cursor_p >= kmax                  : b = 0
+ *     n < select.min_samples            : want = select.min_samples - n
+ *     else  E = max over select_device's window of e_q   (x > E ? x : E from E = 0: a NaN never wins)
+ *           !(E > select.threshold)     : b = 0
+ *           else r = E / select.threshold;  t = (fn * r) * r;  d = ceilf(t) - fn
+ *                want = d >= (float)cap ? cap : (d >= 1.f ? (uint32_t)d : 1)     (a NaN d gives 1; inf gives cap)
+ *     b = min(want, cap, kmax - n)
+ *   b_p != 0 exactly where select_device writes 1 under the same `select` params.
+ * step_budget_device: every active pixel p takes min(d_budget[p], B, kmax - n_p) samples, the next ones in its own order,
+ *   in one pass (the clamp by B keeps the pass within the radiance workspace the handle already sizes).  Pixels with
+ *   budget 0 keep their state bit for bit and stay active.  A step whose budgets are all 0 is VMX_OK, issues nothing and
+ *   does not count as a step.  *selected (may be NULL) is the number of pixels that took samples, stats.samples the samples
+ *   folded, stats.passes 1.  Afterwards the handle is ragged, exactly as after a selected step.  d_budget is a DEVICE
+ *   pointer, read during the call.
+ * step_budgeted: budget_device into a plane the handle owns, then step_budget_device: the same state as the two calls by
+ *   hand.
+ * Order of checks: params, then the pointers (NULL, 4-byte alignment, 8-byte for d_total, buffers that meet in their
+ * first element), then the handle and how it was begun, then what needs the device (pointer kinds, overlaps at the image's
+ * size), then the handle's state.  All three are VMX_ERR_INVALID on a handle not begun with begin_nee (budgeted steps are
+ * built for light-sampled handles only); budget_device and step_budgeted on a handle without VMX_PROGRESSIVE_MOMENTS.
+ * Defaults (vmx_sampling_budget_default_params): select as vmx_sampling_default_params, max_step 0.
+ * tests/budget_spec.py restates the rule and a budgeted step's fold.
+ * Out of scope: budgeted steps on plain handles (k_raygen / k_paths would need the same per-item work source, and this
+ * section leaves them untouched); splitting a budget above B over several passes; multi-device light-sampled handles. */
+int vmx_progressive_begin_nee(vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                              vmx_progressive **out);
+typedef struct vmx_sampling_budget_params {
+    vmx_sampling_params select; /* as vmx_sampling_default_params */
+    uint32_t max_step;          /* 0: the handle's samples per batch; default 0 */
+    uint32_t reserved[3];       /* must be 0 */
+} vmx_sampling_budget_params;
+int vmx_sampling_budget_default_params(vmx_sampling_budget_params *out);
+int vmx_progressive_budget_device(vmx_progressive *p, const vmx_sampling_budget_params *params, void *d_budget,
+                                  void *d_total /* one uint64, or NULL */);
+int vmx_progressive_step_budget_device(vmx_progressive *p, const void *d_budget, vmx_stats *stats,
+                                       uint32_t *selected /* or NULL */);
+int vmx_progressive_step_budgeted(vmx_progressive *p, const vmx_sampling_budget_params *params, vmx_stats *stats,
+                                  uint32_t *selected /* or NULL */);
 
 /* ---- frame output (the step after the path; replaces the conversion loop of
  * Camera::saveFrame, core/camera/camera.cpp:140-175, for the default RGBAZ mode) ------------ */

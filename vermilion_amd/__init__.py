@@ -13,7 +13,7 @@ from ._lib import VMX_SIGMA_LUMINANCE_DEFAULT as SIGMA_LUMINANCE_DEFAULT
 from ._lib import VMX_VARIANCE_EPS as VARIANCE_EPS
 from .scene import (MOTION_DTYPE, MultiScene, Progressive, Scene, default_spheres,
                     local_row_indices, local_rows, low_camera, make_adaptive_params, make_camera, make_filter_params, make_opts,
-                    make_sampling_params, make_temporal_params, make_upsample_params, make_variance_params, motion_vectors, sphere_motion_vectors,
+                    make_sampling_budget_params, make_sampling_params, make_temporal_params, make_upsample_params, make_variance_params, motion_vectors, sphere_motion_vectors,
                     spheres_array)
 from .image import Filter, Temporal, Upsample
 from .api import (Camera, Integrator, MeshEngine, PathTracer, RenderEngine, cameraSettings, float3,
@@ -21,7 +21,7 @@ from .api import (Camera, Integrator, MeshEngine, PathTracer, RenderEngine, came
 from . import scenes
 
 __all__ = [
-    "Scene", "MultiScene", "Progressive", "Filter", "make_filter_params", "Upsample", "make_upsample_params", "low_camera", "Temporal", "make_temporal_params", "make_variance_params", "make_adaptive_params", "make_sampling_params", "ADAPTIVE_EPS", "VARIANCE_EPS", "SIGMA_LUMINANCE_DEFAULT", "motion_vectors", "sphere_motion_vectors", "MOTION_DTYPE", "ALBEDO_FLOOR", "make_camera", "make_opts", "spheres_array", "default_spheres", "local_rows",
+    "Scene", "MultiScene", "Progressive", "Filter", "make_filter_params", "Upsample", "make_upsample_params", "low_camera", "Temporal", "make_temporal_params", "make_variance_params", "make_adaptive_params", "make_sampling_params", "make_sampling_budget_params", "ADAPTIVE_EPS", "VARIANCE_EPS", "SIGMA_LUMINANCE_DEFAULT", "motion_vectors", "sphere_motion_vectors", "MOTION_DTYPE", "ALBEDO_FLOOR", "make_camera", "make_opts", "spheres_array", "default_spheres", "local_rows",
     "local_row_indices", "Camera", "Integrator", "MeshEngine", "PathTracer", "RenderEngine",
     "cameraSettings", "float3", "pixelValue", "vermRenderMode", "scenes", "VmxError",
     "VMX_SAMPLING_PARITY", "VMX_SAMPLING_CORRECTED", "VMX_SAMPLING_LIBM_DOUBLE", "VMX_SAMPLING_ELIDE_DEAD",

@@ -258,6 +258,17 @@ class SamplingParams(C.Structure):
                 "reserved": list(self.reserved)}
 
 
+class SamplingBudgetParams(C.Structure):
+    _fields_ = [
+        ("select", SamplingParams),
+        ("max_step", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+    def as_dict(self):
+        return {"select": self.select.as_dict(), "max_step": self.max_step, "reserved": list(self.reserved)}
+
+
 class UpsampleParams(C.Structure):
     _fields_ = [
         ("normal_squarings", C.c_uint32),
@@ -323,6 +334,11 @@ SYMBOLS = {
     "vmx_progressive_select_device": (C.c_int, [_P, C.POINTER(SamplingParams), _P, _P]),
     "vmx_progressive_step_adaptive": (C.c_int, [_P, C.c_uint32, C.POINTER(SamplingParams), C.POINTER(Stats),
                                                 C.POINTER(C.c_uint32)]),
+    "vmx_progressive_begin_nee": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P, C.POINTER(_P)]),
+    "vmx_sampling_budget_default_params": (C.c_int, [C.POINTER(SamplingBudgetParams)]),
+    "vmx_progressive_budget_device": (C.c_int, [_P, C.POINTER(SamplingBudgetParams), _P, _P]),
+    "vmx_progressive_step_budget_device": (C.c_int, [_P, _P, C.POINTER(Stats), C.POINTER(C.c_uint32)]),
+    "vmx_progressive_step_budgeted": (C.c_int, [_P, C.POINTER(SamplingBudgetParams), C.POINTER(Stats), C.POINTER(C.c_uint32)]),
     "vmx_filter_default_params": (C.c_int, [C.POINTER(FilterParams)]),
     "vmx_filter_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "vmx_filter_destroy": (C.c_int, [_P]),

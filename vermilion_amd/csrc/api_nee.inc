@@ -16,75 +16,19 @@ int nee_check_opts(const vmx_opts *o) {
     return VMX_OK;
 }
 
-// the stack and the persistent grid of a k_nee launch over `items` work items
-int nee_launch_cfg(vmx_scene *sc, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg) {
-    int blocks = 0;
-    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks));
-    if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
-    cfg = paths_cfg(sc, tn.lds_entries, items, blocks);
-    return bind_stack(sc, tn, tn.lds_entries, cfg.grid, items, wk);
-}
-
-// One frame: vmx_render's set-up, per-pixel state, batching by samples_per_batch and k_resolve; each pass's paths run in
-// k_nee, which leaves their radiance in the workspace's `rad`
+// One frame: vmx_render's set-up and pass loop (render_run), whose passes run their paths in k_nee (RenderJob::nee) — the
+// routine a light-sampled progressive handle steps through
 int nee_render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, float *d_out, hipStream_t s, vmx_stats *stats) {
     const auto t0 = std::chrono::steady_clock::now();
     RenderJob job;
     int rc = render_setup(sc, cam, opts, &sc->ws.pixels, d_out, s, job);
     if (rc) return rc;
+    job.nee = true;
     if (job.npix == 0) {
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return VMX_OK;
     }
-    Workspace &ws = sc->ws;
-    const FrameDev &fr = job.fr;
-    if ((rc = sc->upd.done.wait(s))) return rc;
-    ws.events.reset();
-    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
-    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(ev0, s));
-    if (ws.heads.ensure(kSubQueues * 32) || ws.rad.ensure((size_t)job.n_pad_max * job.smax * 16) || ws.next_count.ensure(32) ||
-        ws.counters.ensure(1))
-        return fail(VMX_ERR_NOMEM, "hipMalloc failed for the render workspace");
-    HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
-    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
-    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
-    if ((rc = render_init_pixels(sc, job))) return rc;
-    const PixelStateDev px{job.pixels->accum.p, job.pixels->count.p, job.pixels->cursor.p};
-    uint32_t n_active = job.npix, done = 0;
-    int cur = 0;
-    while (n_active > 0 && done < fr.kmax) {
-        const uint32_t S = std::min(job.smax, fr.kmax - done);
-        const uint32_t n_pad = (n_active + 63u) & ~63u;
-        const uint64_t items = (uint64_t)n_pad * S;
-        WorkDev wk;
-        std::memset(&wk, 0, sizeof(wk));
-        wk.heads = ws.heads.p;
-        wk.active = job.pixels->active[cur].p;
-        wk.n_active = n_active, wk.n_pad = n_pad, wk.samples = S, wk.div_samples = make_fastdiv(S);
-        wk.pixel_major = 1;
-        LaunchCfg cfg;
-        if ((rc = nee_launch_cfg(sc, job.tn, items, false, wk, cfg))) return rc;
-        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
-        if ((rc = timed_begin(ws, job.timed, s, 0, VMX_K_OTHER))) return rc;
-        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, px, nullptr, nullptr, (uint32_t)items, ws.rad.p, ws.counters.p, cfg, s));
-        if ((rc = timed_end(job.timed, s))) return rc;
-        HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
-        if ((rc = timed_begin(ws, job.timed, s, -1, VMX_K_RESOLVE))) return rc;
-        LAUNCH_TRY(launch_resolve(fr, wk.active, n_active, S, true, ws.rad.p, nullptr, px, job.pixels->active[cur ^ 1].p, ws.next_count.p,
-                                  d_out, ws.counters.p, s));
-        if ((rc = timed_end(job.timed, s))) return rc;
-        unsigned int h_next[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(h_next, ws.next_count.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        n_active = h_next[0];
-        cur ^= 1;
-        done += S;
-        job.launches += 2;
-        job.passes++;
-    }
-    HIP_TRY(hipEventRecord(ev1, s));
-    return finish_stats(sc, s, job.timed, ev0, ev1, stats, job.launches, job.passes, t0);
+    return render_run(sc, job, 0, stats, t0);
 }
 
 }  // namespace

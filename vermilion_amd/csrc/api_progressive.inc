@@ -27,6 +27,11 @@ struct VMX_OPAQUE vmx_progressive {
     DevBuf<unsigned char> list_tmp;         // scan scratch
     size_t list_words = 0, list_tmp_bytes = 0;
     DevBuf<unsigned char> select_map;       // vmx_progressive_step_adaptive's map, on first use
+    // budgeted steps (light-sampled handles): vmx_progressive_step_budgeted's plane; the step's sample counts and their
+    // exclusive scan (one entry per local pixel and one more each), the scan's scratch — all on first use
+    DevBuf<unsigned int> budget_map, item_cnt, item_base;
+    DevBuf<unsigned char> item_tmp;
+    size_t item_tmp_bytes = 0;
 };
 
 // a step of a ragged handle (api_sampling.inc); d_select NULL: every active pixel
@@ -37,12 +42,17 @@ int vmx_progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *
     return vmx_progressive_begin_ex(sc, cam, opts, 0, stream, out);
 }
 
-int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
-                             vmx_progressive **out) {
+// nee: a light-sampled handle (vmx_progressive_begin_nee), whose passes run k_nee (RenderJob::nee)
+static int progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                             vmx_progressive **out, bool nee) {
     // checks that need no device, in this order so that each can be seen alone; the scene comes last
     if (!cam || !opts) return fail(VMX_ERR_INVALID, "NULL argument: cam or opts");
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
-    if (flags & ~VMX_PROGRESSIVE_MOMENTS) return fail(VMX_ERR_INVALID, "vmx_progressive_begin_ex: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)");
+    if (flags & ~VMX_PROGRESSIVE_MOMENTS)
+        return fail(VMX_ERR_INVALID, nee ? "vmx_progressive_begin_nee: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)"
+                                         : "vmx_progressive_begin_ex: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)");
+    if (nee)
+        if (int rc = nee_check_opts(opts)) return rc;
     {
         FrameDev fr;
         if (int rc = make_frame(*cam, *opts, fr)) return rc;
@@ -58,6 +68,7 @@ int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opt
     p->generation = sc->generation;
     int rc = render_setup(sc, cam, opts, &p->pixels, nullptr, stream ? (hipStream_t)stream : sc->stream, p->job);
     p->job.moments = (flags & VMX_PROGRESSIVE_MOMENTS) != 0;
+    p->job.nee = nee;
     if (rc == VMX_OK && p->job.npix) {
         if (p->frame.ensure((size_t)p->job.npix * 5)) rc = fail(VMX_ERR_NOMEM, "hipMalloc failed for the frame buffer");
         p->job.d_out = p->frame.p;
@@ -72,6 +83,16 @@ int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opt
     sc->progressive_open++;
     *out = p.release();
     return VMX_OK;
+}
+
+int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                             vmx_progressive **out) {
+    return progressive_begin(sc, cam, opts, flags, stream, out, false);
+}
+
+int vmx_progressive_begin_nee(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                              vmx_progressive **out) {
+    return progressive_begin(sc, cam, opts, flags, stream, out, true);
 }
 
 int vmx_progressive_step(vmx_progressive *p, uint32_t samples, vmx_stats *stats) {

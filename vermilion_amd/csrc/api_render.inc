@@ -473,6 +473,15 @@ int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t n
     return VMX_OK;
 }
 
+// the stack and the persistent grid of a k_nee launch over `items` work items
+int nee_launch_cfg(vmx_scene *sc, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg, bool budgeted = false) {
+    int blocks = 0;
+    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks, budgeted));
+    if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
+    cfg = paths_cfg(sc, tn.lds_entries, items, blocks);
+    return bind_stack(sc, tn, tn.lds_entries, cfg.grid, items, wk);
+}
+
 // run_samples: the most samples a pixel takes in this run (0: the rest of the frame)
 int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
     Workspace &ws = sc->ws;
@@ -480,6 +489,14 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
     const Tuning &tn = job.tn;
     const uint32_t smax = job.smax, n_pad_max = job.n_pad_max;
     hipStream_t s = job.s;
+    if (job.nee) {  // k_nee leaves a pass's radiance in `rad`; no path arrays, camera tables or claims
+        if (ws.heads.ensure(kSubQueues * 32) || ws.rad.ensure((size_t)n_pad_max * smax * 16) || ws.next_count.ensure(32) ||
+            ws.counters.ensure(1))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the render workspace");
+        job.px = PixelStateDev{job.pixels->accum.p, job.pixels->count.p, job.pixels->cursor.p};
+        job.claims = job.claim_lists = nullptr;
+        return VMX_OK;
+    }
     if (job.split_any) {
         int rc = ensure_paths(sc, (size_t)n_pad_max * smax, job.pa, job.qi);
         if (rc == VMX_ERR_NOMEM && smax > 1 && !job.opts.samples_per_batch)
@@ -639,8 +656,8 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     *taken = S;
     const uint32_t n_pad = (n_active + 63u) & ~63u;
     // the form this pass runs in
-    const bool split = pipeline == 4 || (pipeline == 0 && (uint64_t)n_pad * S >= ((fr.early_stop && job.frame_passes > 0) ? kHybridLeftover : kHybridPaths));
-    const bool refill = pipeline == 1 || (pipeline == 0 && !split);
+    const bool split = !job.nee && (pipeline == 4 || (pipeline == 0 && (uint64_t)n_pad * S >= ((fr.early_stop && job.frame_passes > 0) ? kHybridLeftover : kHybridPaths)));
+    const bool refill = !job.nee && (pipeline == 1 || (pipeline == 0 && !split));
     // the work source of a pass's first kernel: the active pixels' samples, in 8 bands of the list
     WorkDev wk;
     std::memset(&wk, 0, sizeof(wk));
@@ -652,7 +669,16 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     wk.band_slots = (((n_pad + 7u) / 8u) + 63u) & ~63u;
     wk.band_items = wk.band_slots * S;
     wk.pixel_major = 1;
-    if (split) {
+    if (job.nee) {  // light sampling: one persistent launch, one work counter
+        const uint64_t items = (uint64_t)n_pad * S;
+        LaunchCfg cfg;
+        if ((rc = nee_launch_cfg(sc, tn, items, false, wk, cfg))) return rc;
+        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
+        if ((rc = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return rc;
+        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, px, nullptr, nullptr, (uint32_t)items, ws.rad.p, ws.counters.p, cfg, s));
+        if ((rc = timed_end(timed, s))) return rc;
+        launches++;
+    } else if (split) {
         wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
         wk.cam_n_inner = sc->n_inner;
         wk.claims = job.claims;
@@ -773,7 +799,7 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     }
     HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
     if ((rc = timed_begin(ws, timed, s, -1, VMX_K_RESOLVE))) return rc;
-    LAUNCH_TRY(launch_resolve(fr, act_cur, n_active, S, split || refill, ws.rad.p, split ? pa.rad_mask : nullptr, px, act_next,
+    LAUNCH_TRY(launch_resolve(fr, act_cur, n_active, S, split || refill || job.nee, ws.rad.p, split ? pa.rad_mask : nullptr, px, act_next,
                               ws.next_count.p, job.d_out, ws.counters.p, s, job.moments));
     if ((rc = timed_end(timed, s))) return rc;
     launches++;

@@ -200,4 +200,183 @@ int vmx_progressive_step_adaptive(vmx_progressive *p, uint32_t samples, const vm
     return progressive_step_list(p, samples, p->select_map.p, stats, selected, t0);
 }
 
+// ---- budgeted steps: every pixel takes the number of samples its own error asks for, in one pass (light-sampled handles) ----
+static const vmx_sampling_budget_params kBudgetDefaults = {{0.5f, 0.05f, 8u, 1u, {0u, 0u, 0u, 0u}}, 0u, {0u, 0u, 0u}};
+
+static int budget_params(const vmx_sampling_budget_params *in, vmx_sampling_budget_params &out) {
+    out = in ? *in : kBudgetDefaults;
+    vmx_sampling_params sel;
+    if (int rc = sampling_params(&out.select, sel)) return rc;
+    if (!reserved_zero(out.reserved)) return fail(VMX_ERR_INVALID, "vmx_sampling_budget_params: reserved words must be 0");
+    return VMX_OK;
+}
+
+int vmx_sampling_budget_default_params(vmx_sampling_budget_params *out) { return default_params(out, kBudgetDefaults); }
+
+// how the handle was begun (no device needed)
+static int budget_refusals(const vmx_progressive *p, bool needs_moments) {
+    if (!p->job.nee)
+        return fail(VMX_ERR_INVALID, "budgeted steps are built for light-sampled handles only: begin the handle with vmx_progressive_begin_nee");
+    return selection_refusals(p, true, needs_moments);
+}
+
+static BudgetPass budget_pass(const vmx_progressive *p, const vmx_sampling_budget_params &prm) {
+    BudgetPass b{};
+    b.a = sampling_pass(p, prm.select);
+    const uint32_t B = p->job.smax;
+    b.cap = prm.max_step ? std::min(prm.max_step, B) : B;
+    return b;
+}
+
+// One budgeted pass.  The caller holds the scene's lock, has bound its device and has checked the handle's generation and
+// `failed`; d_budget is read until the call returns.
+static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_budget, vmx_stats *stats, uint32_t *selected,
+                                   std::chrono::steady_clock::time_point t0) {
+    vmx_scene *sc = p->sc;
+    RenderJob &job = p->job;
+    Workspace &ws = sc->ws;
+    hipStream_t s = job.s;
+    vmx_stats st;
+    std::memset(&st, 0, sizeof(st));
+    uint32_t n_sel = 0;
+    auto body = [&]() -> int {
+        if (job.npix == 0) return VMX_OK;
+        if (!job.ragged)
+            if (int rc = progressive_make_ragged(p)) return rc;
+        const uint32_t n_master = p->n_master;
+        if (n_master == 0) return VMX_OK;
+        const size_t tmp = item_base_tmp_bytes(job.npix);
+        if (p->item_cnt.ensure((size_t)job.npix + 1) || p->item_base.ensure((size_t)job.npix + 1) || p->item_tmp.ensure(tmp + 256))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the step's item bases");
+        p->item_tmp_bytes = tmp;
+        if (int rc = sc->upd.done.wait(s)) return rc;
+        // the step's list: the master list compacted by "has a budget and is unfinished"; its sample counts and their scan;
+        // the list's length and the items come back in one round trip
+        unsigned int *act = job.pixels->active[job.cur_list].p, *act_next = job.pixels->active[job.cur_list ^ 1].p;
+        const unsigned int *master = p->master[p->cur_master].p;
+        const uint32_t nwords = (n_master + 63u) / 64u;
+        unsigned int *cnt = p->list_u32.p, *offs = cnt + p->list_words, *len = offs + p->list_words;
+        LAUNCH_TRY(launch_list_words_budget(master, n_master, d_budget, p->pixels.cursor.p, job.fr.kmax, p->list_mask.p, cnt, s));
+        HIP_TRY((hipError_t)launch_list_compact(p->list_mask.p, cnt, nwords, offs, master, act, len, p->list_tmp.p, p->list_tmp_bytes, s));
+        HIP_TRY((hipError_t)launch_item_base(act, len, n_master, d_budget, p->pixels.cursor.p, job.fr.kmax, job.smax, p->item_cnt.p,
+                                             p->item_base.p, p->item_tmp.p, p->item_tmp_bytes, s));
+        unsigned int h[2] = {0, 0};  // [0] the list's length, [1] the pass's items
+        HIP_TRY(hipMemcpyAsync(&h[0], len, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&h[1], p->item_base.p + n_master, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_sel = h[0];
+        const uint32_t items = h[1];
+        if (n_sel == 0) return VMX_OK;
+        if (n_sel > n_master || items < n_sel || (uint64_t)items > (uint64_t)job.n_pad_max * job.smax)
+            return fail(VMX_ERR_HIP, "budgeted step: the item scan does not fit the pass's workspace");
+        // the pass: k_nee over the items, k_resolve_budget over the list
+        ws.events.reset();
+        job.timed.clear();
+        job.passes = 0;
+        hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
+        if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
+        HIP_TRY(hipEventRecord(ev0, s));
+        if (int rc = render_bind(sc, job, 0)) return rc;
+        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+        WorkDev wk;
+        std::memset(&wk, 0, sizeof(wk));
+        wk.heads = ws.heads.p;
+        wk.active = act;
+        wk.n_active = n_sel, wk.n_pad = (n_sel + 63u) & ~63u, wk.samples = 1, wk.div_samples = make_fastdiv(1);
+        wk.pixel_major = 1;
+        wk.flat_ids = p->item_base.p;
+        LaunchCfg cfg;
+        if (int rc = nee_launch_cfg(sc, job.tn, items, false, wk, cfg, true)) return rc;
+        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
+        if (int rc = timed_begin(ws, job.timed, s, 0, VMX_K_OTHER)) return rc;
+        LAUNCH_TRY(launch_nee(sc->dev, job.fr, wk, job.px, nullptr, nullptr, items, ws.rad.p, ws.counters.p, cfg, s));
+        if (int rc = timed_end(job.timed, s)) return rc;
+        HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
+        if (int rc = timed_begin(ws, job.timed, s, -1, VMX_K_RESOLVE)) return rc;
+        LAUNCH_TRY(launch_resolve_budget(job.fr, act, n_sel, p->item_base.p, ws.rad.p, job.px, act_next, ws.next_count.p, job.d_out,
+                                         ws.counters.p, s, job.moments));
+        if (int rc = timed_end(job.timed, s)) return rc;
+        job.launches += 2;
+        job.passes = 1;
+        job.frame_passes++;
+        HIP_TRY(hipEventRecord(ev1, s));
+        int rc = finish_stats(sc, s, job.timed, ev0, ev1, &st, job.launches, job.passes, t0);
+        job.launches = 0;
+        if (rc) return rc;
+        // the master list without the pixels this step completed, in order
+        uint32_t left = 0;
+        if ((rc = progressive_compact(p, p->master[p->cur_master].p, p->n_master, nullptr, p->master[p->cur_master ^ 1].p, &left))) return rc;
+        p->cur_master ^= 1, p->n_master = left;
+        p->samples += st.samples, p->passes += st.passes, p->steps++;
+        return VMX_OK;
+    };
+    if (int rc = body()) {
+        p->failed = true;
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return rc;
+    }
+    if (job.ragged) job.n_active = p->n_master;
+    if (stats) *stats = st;
+    if (selected) *selected = n_sel;
+    return VMX_OK;
+}
+
+int vmx_progressive_budget_device(vmx_progressive *p, const vmx_sampling_budget_params *params, void *d_budget, void *d_total) {
+    vmx_sampling_budget_params prm;
+    if (int rc = budget_params(params, prm)) return rc;
+    if (!d_budget) return fail(VMX_ERR_INVALID, "NULL d_budget");
+    if ((uintptr_t)d_budget & 3u) return fail(VMX_ERR_INVALID, "d_budget must be 4-byte aligned");
+    if ((uintptr_t)d_total & 7u) return fail(VMX_ERR_INVALID, "d_total must be 8-byte aligned");
+    if (spans_meet(Span{d_budget, 4}, Span{d_total, 8})) return fail(VMX_ERR_INVALID, "d_budget and d_total overlap");
+    if (!p) return fail(VMX_ERR_INVALID, "NULL handle");
+    if (int rc = budget_refusals(p, true)) return rc;
+    vmx_scene *sc = p->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    if (int rc = check_device_ptrs(sc->device, {{d_budget, "d_budget"}, {d_total, "d_total"}})) return rc;
+    if (spans_meet(Span{d_budget, (size_t)p->job.npix * 4}, Span{d_total, 8})) return fail(VMX_ERR_INVALID, "d_budget and d_total overlap");
+    if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, p->job.s));
+    LAUNCH_TRY(launch_sampling_budget(budget_pass(p, prm), (unsigned int *)d_budget, (unsigned long long *)d_total, p->job.s));
+    return VMX_OK;
+}
+
+int vmx_progressive_step_budget_device(vmx_progressive *p, const void *d_budget, vmx_stats *stats, uint32_t *selected) {
+    if (!d_budget) return fail(VMX_ERR_INVALID, "NULL d_budget");
+    if ((uintptr_t)d_budget & 3u) return fail(VMX_ERR_INVALID, "d_budget must be 4-byte aligned");
+    if (!p) return fail(VMX_ERR_INVALID, "NULL handle");
+    if (int rc = budget_refusals(p, false)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    vmx_scene *sc = p->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    if (int rc = check_device_ptrs(sc->device, {{d_budget, "d_budget"}})) return rc;
+    if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
+    if (p->failed) return fail(VMX_ERR_INVALID, "an earlier step of this handle failed: end it and begin again");
+    return progressive_step_budget(p, (const unsigned int *)d_budget, stats, selected, t0);
+}
+
+int vmx_progressive_step_budgeted(vmx_progressive *p, const vmx_sampling_budget_params *params, vmx_stats *stats, uint32_t *selected) {
+    vmx_sampling_budget_params prm;
+    if (int rc = budget_params(params, prm)) return rc;
+    if (!p) return fail(VMX_ERR_INVALID, "NULL handle");
+    if (int rc = budget_refusals(p, true)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    vmx_scene *sc = p->sc;
+    std::lock_guard<std::mutex> lock(sc->mu);
+    if (int rc = bind_device(sc)) return rc;
+    if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
+    if (p->failed) return fail(VMX_ERR_INVALID, "an earlier step of this handle failed: end it and begin again");
+    if (p->job.npix == 0) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        if (selected) *selected = 0;
+        return VMX_OK;
+    }
+    if (p->budget_map.ensure(p->job.npix)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the budget plane");
+    LAUNCH_TRY(launch_sampling_budget(budget_pass(p, prm), p->budget_map.p, nullptr, p->job.s));
+    return progressive_step_budget(p, p->budget_map.p, stats, selected, t0);
+}
+
 } /* extern "C" */

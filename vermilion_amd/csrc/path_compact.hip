@@ -65,7 +65,40 @@ k_list_scatter(const unsigned long long *__restrict__ mask, const unsigned int *
     }
 }
 
+// a budgeted step's sample counts, one per slot of its pixel list and one behind the last: what the step's items are
+// scanned from.  *len is the list's length on the device (launch_list_compact); slots at or past it count 0
+__global__ void __launch_bounds__(256)
+k_item_counts(const unsigned int *__restrict__ list, const unsigned int *__restrict__ len, uint32_t n_max,
+              const unsigned int *__restrict__ budget, const unsigned int *__restrict__ cursor, uint32_t kmax, uint32_t B,
+              unsigned int *__restrict__ cnt) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot > n_max) return;
+    uint32_t c = 0;
+    if (slot < n_max && slot < *len) {
+        const uint32_t lp = list[slot];
+        const uint32_t at = cursor[lp];
+        c = min(min(budget[lp], B), at < kmax ? kmax - at : 0u);
+    }
+    cnt[slot] = c;
+}
+
 }  // namespace
+
+size_t item_base_tmp_bytes(uint32_t n_max) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (unsigned int *)nullptr, (unsigned int *)nullptr, (int)n_max + 1, nullptr);
+    return bytes;
+}
+
+int launch_item_base(const unsigned int *list, const unsigned int *len, uint32_t n_max, const unsigned int *budget,
+                     const unsigned int *cursor, uint32_t kmax, uint32_t B, unsigned int *cnt, unsigned int *base, void *tmp,
+                     size_t tmp_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_item_counts, dim3((n_max + 1 + 255) / 256), dim3(256), 0, s, list, len, n_max, budget, cursor, kmax, B, cnt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return (int)hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, base, (int)n_max + 1, s);
+}
 
 size_t live_compact_tmp_bytes(uint32_t nwords) {
     size_t bytes = 0;

@@ -454,6 +454,9 @@ struct RenderJob {
     Tuning tn;
     uint32_t npix = 0, pipeline = 0;
     bool count = false, split_any = false, legacy = false, elide = false;
+    // the light-sampling integrator (api_nee.inc; set by the caller right after render_setup): a pass's paths run in k_nee,
+    // whatever the pipeline form, and a run binds only what that kernel and k_resolve use
+    bool nee = false;
     bool claims_on = false;  // split passes may use per-pixel claims (pixel_claim.h): not counting, not eliding, reserved[0] bit 11 clear
     bool lists_on = false;   // ... and the pixels without a claim get list claims (reserved[0] bit 13 clear)
     bool fuse_on = false;    // ... and a dense plain camera pass fuses its claimed pixels into k_shade<0> (reserved[0] bit 12 clear)

@@ -418,7 +418,30 @@ int launch_motion_spheres(const void *rayhit, uint32_t n, const SphereMotionDev 
 // explicit rays (o, d): ray i on stream (fr.seed, i, 0), `items` of them, rad[i] its accumColour
 int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, const float *o, const float *d,
                uint32_t items, void *rad, DevCounters *counters, LaunchCfg cfg, void *stream);
-int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks);
+// a budgeted step of a light-sampled progressive handle (o == NULL, wk.flat_ids != NULL): k_nee's third work source.
+// wk.active / n_active: the step's pixel list; wk.flat_ids: the exclusive scan of the pixels' sample counts, n_active + 1
+// entries, every count >= 1; `items` = its last entry; item i is sample i - base[s] of slot s, rad[i] its accumColour
+int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks, bool budgeted = false);
+// ... and its fold: k_resolve's statements over rad[base[s] + j], j < base[s + 1] - base[s], per slot s in order
+int launch_resolve_budget(const FrameDev &fr, const unsigned int *active, uint32_t n_active, const unsigned int *base, const void *rad,
+                          PixelStateDev px, unsigned int *next_active, unsigned int *next_count, float *out_rgbaz, DevCounters *counters,
+                          void *stream, bool moments);
+// per-pixel sample budgets of a moments handle (vmx_sampling.inc; the rule is stated in include/vermilion_hip.h): budget[p]
+// for every local pixel, *total (or NULL; zeroed by the caller) += their sum
+struct BudgetPass {
+    SamplingPass a;
+    uint32_t cap;  // min(max_step, B) or B
+};
+int launch_sampling_budget(const BudgetPass &b, unsigned int *budget, unsigned long long *total, void *stream);
+// launch_list_words over a word map: slot i < n is set if its pixel lp = list[i] has cursor[lp] < kmax and budget[lp] != 0
+int launch_list_words_budget(const unsigned int *list, uint32_t n, const unsigned int *budget, const unsigned int *cursor, uint32_t kmax,
+                             unsigned long long *mask, unsigned int *cnt, void *stream);
+// the step's sample counts and their exclusive scan: cnt[s] = min(budget[list[s]], B, kmax - cursor) for s < *len, 0 for
+// *len <= s <= n_max; base[0 .. n_max] their exclusive sums, so base[*len] = base[n_max] = the step's items
+size_t item_base_tmp_bytes(uint32_t n_max);
+int launch_item_base(const unsigned int *list, const unsigned int *len, uint32_t n_max, const unsigned int *budget,
+                     const unsigned int *cursor, uint32_t kmax, uint32_t B, unsigned int *cnt, unsigned int *base, void *tmp,
+                     size_t tmp_bytes, void *stream);
 int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth, void *stream);
 int launch_assemble(const float *gathered, uint64_t rank_stride_floats, uint32_t width, uint32_t height,
                     uint32_t stripe_rows, uint32_t world, float *frame, void *stream);

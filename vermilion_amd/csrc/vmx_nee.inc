@@ -27,7 +27,11 @@ __device__ __forceinline__ void nee_cone(float4 g, float ox, float oy, float oz,
 }
 
 // SRC 0: camera paths — item = path id = slot * samples + j of the pass's active pixels (pixel-major, as k_paths numbers
-//        them for k_resolve); SRC 1: explicit rays o / d — item i on stream (seed, i, 0), jitter draws skipped
+//        them for k_resolve); SRC 1: explicit rays o / d — item i on stream (seed, i, 0), jitter draws skipped;
+//        SRC 2: a budgeted step's camera paths — slot s of the step's list owns the items [base[s], base[s + 1]) of the
+//        exclusive scan wk.flat_ids (n_active + 1 entries, strictly increasing: every listed pixel takes a sample), item
+//        i is sample j = i - base[s] of its pixel; a lane finds s by bisection when it takes the item (log2 of the list's
+//        length dependent 4-byte loads per path of some 55 rays), and rad[i] is where k_resolve_budget looks for it
 // TEX: accumRadiance is carried (a texture is bound); else it stays (1, 1, 1, 1)
 template <int SRC, bool TEX>
 __global__ void __launch_bounds__(256)
@@ -99,6 +103,21 @@ k_nee(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, const float *__res
                                 primary_ray(fr, global_pixel(fr, lp), k, P.rng, P.dx, P.dy, P.dz);
                                 P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz;
                             }
+                        }
+                    } else if (SRC == 2) {
+                        const unsigned int *__restrict__ base = wk.flat_ids;
+                        uint32_t lo = 0, hi = wk.n_active;  // base[lo] <= item < base[hi]
+                        while (hi - lo > 1u) {
+                            const uint32_t mid = lo + ((hi - lo) >> 1);
+                            if (base[mid] <= item) lo = mid;
+                            else hi = mid;
+                        }
+                        const uint32_t lp = wk.active[lo];
+                        const uint32_t k = sample_index(fr, px, lp, item - base[lo]);
+                        valid = k < fr.kmax;
+                        if (valid) {
+                            primary_ray(fr, global_pixel(fr, lp), k, P.rng, P.dx, P.dy, P.dz);
+                            P.ox = fr.px, P.oy = fr.py, P.oz = fr.pz;
                         }
                     } else {
                         rng_init(P.rng, fr.seed, item, 0);
@@ -241,7 +260,8 @@ k_nee(SceneDev sc, FrameDev fr, WorkDev wk, PixelStateDev px, const float *__res
 }
 
 // wk: heads (one counter, zeroed), reserve, the stack fields; camera paths (rays == NULL): active, n_active, samples,
-// div_samples, `items` = padded slots * samples; explicit rays: o / d, `items` rays
+// div_samples, `items` = padded slots * samples; explicit rays: o / d, `items` rays; a budgeted step (rays == NULL,
+// wk.flat_ids the item bases): active, n_active, `items` = base[n_active]
 int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, const float *o, const float *d,
                uint32_t items, void *rad, DevCounters *counters, LaunchCfg cfg, void *stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -250,6 +270,9 @@ int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelS
     if (o) {
         if (sc.tex) VMX_GO(1, true);
         else VMX_GO(1, false);
+    } else if (wk.flat_ids) {
+        if (sc.tex) VMX_GO(2, true);
+        else VMX_GO(2, false);
     } else {
         if (sc.tex) VMX_GO(0, true);
         else VMX_GO(0, false);
@@ -258,10 +281,13 @@ int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelS
     return launch_status();
 }
 
-int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks) {
+int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks, bool budgeted) {
     int a = 0, b = 0;
     hipError_t e;
-    if (rays) {
+    if (budgeted) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_nee<2, true>, (int)block, lds_bytes);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_nee<2, false>, (int)block, lds_bytes);
+    } else if (rays) {
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_nee<1, true>, (int)block, lds_bytes);
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_nee<1, false>, (int)block, lds_bytes);
     } else {
@@ -270,4 +296,73 @@ int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *
     }
     if (blocks) *blocks = a < b ? a : b;
     return (int)e;
+}
+
+// A budgeted step's fold (vmx_progressive_step_budget_device): slot s of the step's list folds rad[base[s] + j], j < base[s + 1]
+// - base[s], in order — k_resolve's statements for a taken sample: ++n, the three colour adds, the l*l fold — advances
+// count and cursor, writes the pixels that finished and appends the others to the next list.  No early stop (light
+// sampling refuses it), so the cursor is a plain sample index and every listed sample is taken.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256)
+k_resolve_budget(FrameDev fr, const unsigned int *__restrict__ active, uint32_t n_active, const unsigned int *__restrict__ base,
+                 const float4 *__restrict__ rad, PixelStateDev px, unsigned int *__restrict__ next_active, unsigned int *next_count,
+                 float *__restrict__ out, DevCounters *ctr) {
+    __shared__ unsigned int s_keep, s_base, s_taken, s_done;
+    if (threadIdx.x == 0) s_keep = 0, s_taken = 0, s_done = 0;
+    __syncthreads();
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    bool keep = false;
+    uint32_t lp = 0, taken = 0, done = 0;
+    if (slot < n_active) {
+        lp = active[slot];
+        float4 acc = ((float4 *)px.accum)[lp];
+        uint32_t n = px.count[lp];
+        const uint32_t cursor = px.cursor[lp];
+        const uint32_t b0 = base[slot];
+        uint32_t cnt = base[slot + 1] - b0;
+        cnt = min(cnt, cursor < fr.kmax ? fr.kmax - cursor : 0u);  // (the scan's counts are clamped so already)
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const float4 s = rad[b0 + j];
+            ++n;
+            acc.x = acc.x + s.x;
+            acc.y = acc.y + s.y;
+            acc.z = acc.z + s.z;
+            if (MOMENTS) {
+                const float l = luminance(s.x, s.y, s.z);
+                acc.w = acc.w + l * l;
+            }
+        }
+        taken = cnt;
+        const uint32_t next = cursor + cnt;
+        if (next >= fr.kmax) {
+            resolved_pixel(acc, n, out + (size_t)lp * 5);
+            done = 1;
+        } else {
+            keep = true;
+        }
+        ((float4 *)px.accum)[lp] = acc;
+        px.count[lp] = n;
+        px.cursor[lp] = next;
+    }
+    uint32_t my = 0;
+    if (keep) my = atomicAdd(&s_keep, 1u);
+    if (taken) atomicAdd(&s_taken, taken);
+    if (done) atomicAdd(&s_done, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s_base = s_keep ? atomicAdd(next_count, s_keep) : 0u;
+        if (s_taken) atomicAdd(&ctr->samples, (unsigned long long)s_taken);
+        if (s_done) atomicAdd(&ctr->pixels_done, (unsigned long long)s_done);
+    }
+    __syncthreads();
+    if (keep) next_active[s_base + my] = lp;
+}
+
+int launch_resolve_budget(const FrameDev &fr, const unsigned int *active, uint32_t n_active, const unsigned int *base, const void *rad,
+                          PixelStateDev px, unsigned int *next_active, unsigned int *next_count, float *out_rgbaz, DevCounters *counters,
+                          void *stream, bool moments) {
+    if (n_active == 0) return 0;
+    hipLaunchKernelGGL(moments ? k_resolve_budget<true> : k_resolve_budget<false>, dim3((n_active + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, fr, active, n_active, base, (const float4 *)rad, px, next_active, next_count, out_rgbaz, counters);
+    return launch_status();
 }

@@ -15,6 +15,9 @@
 //                      halo of 3) straight from the state — 24 B per pixel — into one LDS plane (2128 B); a pixel outside
 //                      the local image is staged as -1, which no threshold >= 0 lets through.  Then the window test over
 //                      (2 * radius + 1)^2 taps, the map's byte, and the number of selected pixels by one atomic per wave.
+//   k_list_words_budget, k_budget   budgeted steps of a light-sampled handle (stated in the header's "light sampling in
+//                      progressive handles"; restated in tests/budget_spec.py): the word-map form of k_list_words, and the
+//                      per-pixel sample budgets, staged and windowed as k_sampling_select.
 constexpr float kSamplingNoEstimate = 3.402823466e+38f;  // e of a pixel with fewer than two samples
 
 // (e, var) of one pixel; n its count, acc its (r, g, b sums, m2)
@@ -90,6 +93,96 @@ __global__ void __launch_bounds__(kFilterBlock) k_sampling_select(SamplingPass a
     }
     const unsigned long long bits = __ballot(sel);
     if (count && (threadIdx.x & 63u) == 0 && bits) atomicAdd(count, (unsigned int)__popcll(bits));
+}
+
+// k_list_words over a word map: the slot stays if its pixel is unfinished and has a budget (a budgeted step: the handle's
+// master list -> the step's list).  A kernel of its own: the byte-map forms above stay what they compile to.
+__global__ void __launch_bounds__(256)
+k_list_words_budget(const unsigned int *__restrict__ list, uint32_t n, const unsigned int *__restrict__ budget,
+                    const unsigned int *__restrict__ cursor, uint32_t kmax, unsigned long long *__restrict__ mask,
+                    unsigned int *__restrict__ cnt) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    bool stays = false;
+    if (slot < n) {
+        const uint32_t lp = list[slot];
+        stays = cursor[lp] < kmax && budget[lp] != 0;
+    }
+    const unsigned long long bits = __ballot(stays);
+    if ((threadIdx.x & 63u) == 0 && slot < ((n + 63u) & ~63u)) {
+        mask[slot >> 6] = bits;
+        cnt[slot >> 6] = (uint32_t)__popcll(bits);
+    }
+}
+
+// k_budget: one lane per pixel of an image_tile, staged as k_sampling_select stages its window.  E is the largest e of the
+// window (x > E ? x : E from 0: a NaN never wins, and the -1 of a tap outside the image never does); a pixel whose E is
+// above the threshold asks for the samples that bring its standard error down to it, n (E / threshold)^2 - n, within
+// [1, cap].  budget[p] != 0 exactly where k_sampling_select writes 1.  The budgets' sum: a wave reduction, one atomic per
+// wave.
+__global__ void __launch_bounds__(kFilterBlock) k_budget(BudgetPass b, unsigned int *__restrict__ budget,
+                                                         unsigned long long *__restrict__ total) {
+    __shared__ float s_e[kSelectN];
+    const SamplingPass &a = b.a;
+    const uint32_t W = a.width, H = a.height;
+    const ImageTile tile = image_tile(W, H);
+    for (uint32_t i = threadIdx.x; i < kSelectN; i += kFilterBlock) {
+        const uint32_t ry = i / kSelectW, rx = i - ry * kSelectW;
+        const int qx = (int)(tile.bx0 + rx) - kSelectHalo, qy = (int)(tile.by0 + ry) - kSelectHalo;
+        float e = -1.f;
+        if ((uint32_t)qx < W && (uint32_t)qy < H) {
+            const uint32_t q = (uint32_t)qy * W + (uint32_t)qx;
+            float var;
+            e = sampling_error(((const float4 *)a.px.accum)[q], a.px.count[q], a.floor, var);
+        }
+        s_e[i] = e;
+    }
+    __syncthreads();
+    uint32_t out = 0;
+    if (tile.live) {
+        const uint32_t p = tile.p;
+        const uint32_t n = a.px.count[p];
+        if (a.px.cursor[p] < a.kmax) {
+            uint32_t want = 0;
+            if (n < a.min_samples) {
+                want = a.min_samples - n;
+            } else {
+                const uint32_t li = (threadIdx.x / kFilterBX + kSelectHalo) * kSelectW + (threadIdx.x & (kFilterBX - 1)) + kSelectHalo;
+                const int r = (int)a.radius;  // (0..3: within the halo)
+                float E = 0.f;
+                for (int dy = -r; dy <= r; ++dy)
+                    for (int dx = -r; dx <= r; ++dx) {
+                        const float x = s_e[(uint32_t)((int)li + dy * (int)kSelectW + dx)];
+                        E = x > E ? x : E;
+                    }
+                if (E > a.threshold) {
+                    const float fn = (float)n;
+                    const float q = E / a.threshold;
+                    const float t = (fn * q) * q;
+                    const float d = ceilf(t) - fn;
+                    want = d >= (float)b.cap ? b.cap : (d >= 1.f ? (uint32_t)d : 1u);
+                }
+            }
+            const uint32_t room = n < a.kmax ? a.kmax - n : 0u;
+            out = min(min(want, b.cap), room);
+        }
+        budget[p] = out;
+    }
+    const uint32_t sum = wave_sum(out);
+    if (total && (threadIdx.x & 63u) == 0 && sum) atomicAdd(total, (unsigned long long)sum);
+}
+
+int launch_sampling_budget(const BudgetPass &b, unsigned int *budget, unsigned long long *total, void *stream) {
+    if (b.a.width == 0 || b.a.height == 0) return 0;
+    hipLaunchKernelGGL(k_budget, image_grid(b.a.width, b.a.height), dim3(kFilterBlock), 0, (hipStream_t)stream, b, budget, total);
+    return launch_status();
+}
+
+int launch_list_words_budget(const unsigned int *list, uint32_t n, const unsigned int *budget, const unsigned int *cursor, uint32_t kmax,
+                             unsigned long long *mask, unsigned int *cnt, void *stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_list_words_budget, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, list, n, budget, cursor, kmax, mask,
+                       cnt);
+    return launch_status();
 }
 
 int launch_list_words(const unsigned int *list, uint32_t n, const unsigned char *select, const unsigned int *cursor, uint32_t kmax,

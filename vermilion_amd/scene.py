@@ -173,6 +173,24 @@ def make_sampling_params(threshold=None, floor=None, min_samples=None, radius=No
     return p
 
 
+def make_sampling_budget_params(threshold=None, floor=None, min_samples=None, radius=None, max_step=None):
+    """vmx_sampling_budget_params: the library's defaults (vmx_sampling_budget_default_params) with the given fields
+    replaced; threshold, floor, min_samples and radius are its `select` member's"""
+    p = L.SamplingBudgetParams()
+    L.check(L.lib().vmx_sampling_budget_default_params(C.byref(p)))
+    if threshold is not None:
+        p.select.threshold = float(threshold)
+    if floor is not None:
+        p.select.floor = float(floor)
+    if min_samples is not None:
+        p.select.min_samples = int(min_samples)
+    if radius is not None:
+        p.select.radius = int(radius)
+    if max_step is not None:
+        p.max_step = int(max_step)
+    return p
+
+
 def make_upsample_params(normal_squarings=None, sigma_depth=None):
     """vmx_upsample_params: the library's defaults (vmx_upsample_default_params) with the given fields replaced"""
     p = L.UpsampleParams()
@@ -794,6 +812,12 @@ class Scene:
         self._check(self._lib.vmx_render_nee(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
+    def progressive_nee(self, cam, opts, stream=None, moments=False):
+        """vmx_progressive_begin_nee: the frame `render_nee(cam, opts)` returns, rendered in resumable steps (a
+        context-managed Progressive whose passes run the light-sampling integrator).  Every method of Progressive works on
+        it; `budget_device`, `step_budget` and `step_budgeted` work on such a handle only."""
+        return Progressive(self, cam, opts, stream, moments, nee=True)
+
     def render_nee_device(self, cam, opts, d_out_ptr, stream_ptr=None):
         """Same, into device memory (e.g. a torch tensor's data_ptr()) on `stream_ptr`."""
         st = L.Stats()
@@ -817,9 +841,10 @@ class Progressive:
     """One vmx_progressive handle: `step` issues samples, `preview` shows the frame so far, and the frame a completed
     handle previews is `Scene.render`'s, bit for bit, whatever the steps were."""
 
-    def __init__(self, scene, cam, opts, stream=None, moments=False):
+    def __init__(self, scene, cam, opts, stream=None, moments=False, nee=False):
         self._scene = scene  # (keeps the scene alive: it cannot be destroyed before its handles)
         self.moments = bool(moments)
+        self.nee = bool(nee)
         self._lib = scene._lib
         self._h = None
         self.device = scene.device
@@ -828,7 +853,10 @@ class Progressive:
         self.shape = (rows, int(cam.image_res[0]))
         h = C.c_void_p()
         sptr = C.c_void_p(stream.cuda_stream if stream is not None else 0)
-        if moments:
+        if nee:
+            scene._check(self._lib.vmx_progressive_begin_nee(scene._h, C.byref(cam), C.byref(opts),
+                                                             L.VMX_PROGRESSIVE_MOMENTS if moments else 0, sptr, C.byref(h)))
+        elif moments:
             scene._check(self._lib.vmx_progressive_begin_ex(scene._h, C.byref(cam), C.byref(opts), L.VMX_PROGRESSIVE_MOMENTS,
                                                             sptr, C.byref(h)))
         else:
@@ -924,6 +952,38 @@ class Progressive:
         st, n = L.Stats(), C.c_uint32(0)
         prm = None if params is None else C.byref(params)
         self._scene._check(self._lib.vmx_progressive_step_adaptive(self._h, int(samples), prm, C.byref(st), C.byref(n)))
+        return st.as_dict(), int(n.value)
+
+    def budget_device(self, budget, total=None, params=None):
+        """vmx_progressive_budget_device (a light-sampled moments handle): budget[p] = the samples pixel p's error asks
+        for (int32 [local_rows, W], read as uint32); total: an int64 tensor of one element that receives their sum.
+        params: make_sampling_budget_params(...).  Enqueued on the handle's stream; returns (budget, total)."""
+        import torch
+        self._plane(budget, "budget", torch.int32)
+        if total is not None:
+            _frame_tensor(total, "total", torch.int64, (1,), torch.device("cuda", self.device))
+        prm = None if params is None else C.byref(params)
+        self._scene._check(self._lib.vmx_progressive_budget_device(self._h, prm, C.c_void_p(budget.data_ptr()),
+                                                                   None if total is None else C.c_void_p(total.data_ptr())))
+        return budget, total
+
+    def step_budget(self, budget):
+        """vmx_progressive_step_budget_device (a light-sampled handle): every active pixel p takes min(budget[p], samples
+        per batch, kmax - its count) samples in one pass (budget: int32 [local_rows, W] on the scene's device).  Blocks;
+        returns (this step's vmx_stats as a dict, the number of pixels that took samples)."""
+        import torch
+        self._plane(budget, "budget", torch.int32)
+        st, n = L.Stats(), C.c_uint32(0)
+        self._scene._check(self._lib.vmx_progressive_step_budget_device(self._h, C.c_void_p(budget.data_ptr()), C.byref(st),
+                                                                        C.byref(n)))
+        return st.as_dict(), int(n.value)
+
+    def step_budgeted(self, params=None):
+        """vmx_progressive_step_budgeted (a light-sampled moments handle): `budget_device` into a plane of the handle's,
+        then `step_budget` with it.  Blocks; returns (this step's vmx_stats as a dict, the pixels that took samples)."""
+        st, n = L.Stats(), C.c_uint32(0)
+        prm = None if params is None else C.byref(params)
+        self._scene._check(self._lib.vmx_progressive_step_budgeted(self._h, prm, C.byref(st), C.byref(n)))
         return st.as_dict(), int(n.value)
 
     def info(self):
