@@ -3,7 +3,10 @@
 // device-to-device gather on the first device (vmx_multi_*, include/vermilion_hip.h).  A device may be
 // listed more than once (rehearsal on a box with fewer GPUs); the picture does not depend on the list.
 //
-//   ./examples/render_multi out.ppm 256 256 64 [seed] [devices, e.g. 0,1,2,3,4,5,6,7]
+//   ./examples/render_multi out.ppm 256 256 64 [seed] [devices, e.g. 0,1,2,3,4,5,6,7] [--nee]
+//
+// --nee (anywhere on the line): the light-sampling integrator over the same device list (vmx_multi_render_nee: corrected
+// sampling, fixed sample count) instead of PathTracer::Render.
 //
 // Writes a binary PPM the way Camera::saveFrame quantises (floor(x*255), core/camera/camera.cpp:150-170)
 // and prints the statistics the reference cannot report (camera.h:101-102 are never incremented).
@@ -34,6 +37,13 @@ void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &
 }  // namespace
 
 int main(int argc, char **argv) {
+    bool nee = false;
+    for (int i = 1; i < argc; ++i)
+        if (!std::strcmp(argv[i], "--nee")) {
+            nee = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            --argc, --i;
+        }
     const char *out = argc > 1 ? argv[1] : "cornell.ppm";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 64;
@@ -72,11 +82,12 @@ int main(int argc, char **argv) {
     vmx_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.seed = seed;
-    opts.early_stop = 1;
-    opts.sampling = VMX_SAMPLING_PARITY;
+    opts.early_stop = nee ? 0 : 1;
+    opts.sampling = nee ? VMX_SAMPLING_CORRECTED : VMX_SAMPLING_PARITY;
     std::vector<float> frame((size_t)W * H * 5);
     vmx_stats st;
-    if (vmx_multi_render(scene, &cam, &opts, frame.data(), &st) != VMX_OK) {
+    if ((nee ? vmx_multi_render_nee(scene, &cam, &opts, frame.data(), &st)
+             : vmx_multi_render(scene, &cam, &opts, frame.data(), &st)) != VMX_OK) {
         std::fprintf(stderr, "render: %s\n", vmx_last_error());
         vmx_multi_destroy(scene);
         return 1;
@@ -94,7 +105,7 @@ int main(int argc, char **argv) {
         std::fwrite(rgb, 1, 3, f);
     }
     std::fclose(f);
-    std::printf("%u device(s): ", vmx_multi_world(scene));
+    std::printf("%u device(s)%s: ", vmx_multi_world(scene), nee ? ", light sampling" : "");
     std::printf("frame %ux%u spp %u seed %llu: rays %llu (+%llu secondary), samples %llu, %.2f ms device, checksum %.9g\n", W, H,
                 spp, (unsigned long long)seed, (unsigned long long)st.rays_primary, (unsigned long long)st.rays_secondary,
                 (unsigned long long)st.samples, st.ms_device, sum);

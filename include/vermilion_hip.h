@@ -1258,6 +1258,52 @@ int vmx_progressive_step_budget_device(vmx_progressive *p, const void *d_budget,
 int vmx_progressive_step_budgeted(vmx_progressive *p, const vmx_sampling_budget_params *params, vmx_stats *stats,
                                   uint32_t *selected /* or NULL */);
 
+/* ---- light sampling across ranks and devices, and on device batches ---------------------------------------------------
+ * The entries above keep their contract exactly, "world > 1 is not supported" included.  The entries below reach the
+ * library's scale-out seams through the same routine and the same kernels (k_nee keys every stream by the GLOBAL pixel,
+ * so no frame depends on how it is cut).
+ *
+ * vmx_render_nee_rank / _rank_device: vmx_render_nee / vmx_render_nee_device with opts.rank, opts.world and
+ *   opts.stripe_rows honoured as vmx_render / vmx_render_device honour them: the output is the rank's rows of
+ *   vmx_render_nee's frame, bit for bit, packed in ascending order — vmx_local_rows() rows of W * 5 floats; world 0 or 1
+ *   gives the whole frame; vmx_stats covers the rank's pixels only.  Refusals that need no device, in this order: a NULL
+ *   cam / opts / output, the opts contents (vmx_render_nee's checks and messages in their order, without the world one),
+ *   the frame (vmx_render's checks, "rank must be < world" among them), the NULL scene.  A rank that owns no row (more
+ *   ranks than stripes) behaves as in vmx_render_device: VMX_OK, nothing is launched, the output is not written (it must
+ *   still be non-NULL) and *stats is zeroed.
+ * vmx_progressive_begin_nee_rank: vmx_progressive_begin_nee with world > 1 accepted.  Every entry that takes a handle
+ *   works on it with LOCAL pixel indices, as on a plain handle begun with world > 1: step, the previews (the filtered and
+ *   demodulated ones stay "whole images only"), state_device, the selected and adaptive steps, budget_device,
+ *   step_budget_device, step_budgeted.  The windows of select_device and budget_device are taken in the rank's packed rows
+ *   and stop at the rank's own rows: they never see another rank's pixels, so a rank's maps and budgets near a stripe
+ *   border differ from what the whole image would give.  Whatever the schedule, a handle run to completion holds the
+ *   rank's rows of vmx_render_nee's frame, bit for bit.
+ * vmx_multi_render_nee / _device: vmx_multi_render / _device whose replicas render their stripes through the routine of
+ *   vmx_render_nee_rank_device; gather, assembly and vmx_multi_timings are those of vmx_multi_render.  The frame is
+ *   vmx_render_nee's, bit for bit, for any device list; rays and samples are summed over the replicas, times are the
+ *   slowest replica's.  The library sets rank and world: the caller's opts are checked as vmx_render_nee checks them, so a
+ *   caller's world > 1 is refused.  Order: NULL cam / opts / output, the opts contents, the NULL vmx_multi.  Valid after
+ *   vmx_multi_update, vmx_multi_set_spheres and vmx_multi_bind_texture.
+ * vmx_radiance_nee_device: vmx_radiance_nee on DEVICE arrays of the scene's device — d_origin and d_dir n x 3 floats,
+ *   d_out4 n x 4 floats — enqueued on `stream` (NULL: the scene's stream).  Like vmx_render_nee_device it returns when the
+ *   batch is done (vmx_stats is the counters' read-back).  Order of checks: NULL d_origin / d_dir / opts / d_out4, the opts
+ *   contents, n == 0 (VMX_OK, whatever follows), the rays' 4-byte alignment, d_out4's 16-byte alignment, n > 2^31 - 1,
+ *   d_out4 overlapping either ray array (results are written while other rays are still read), the NULL scene; then, on
+ *   the device, the pointer kinds as vmx_raycast_device checks them (origin, dir, d_out4).  vmx_radiance_nee is an upload,
+ *   this routine and a download.
+ * Measured on one device only (profiles/nee_multi.txt): no node with several GPUs has run this project, so peer copies
+ * between distinct devices stay unexecuted and no scaling curve is claimed.
+ * Out of scope: early stop under light sampling, windows across ranks, multi-device progressive handles. */
+int vmx_render_nee_rank(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, float *out_local, vmx_stats *stats);
+int vmx_render_nee_rank_device(const vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, void *d_out_local,
+                               vmx_stats *stats, void *stream);
+int vmx_progressive_begin_nee_rank(vmx_scene *scene, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                                   vmx_progressive **out);
+int vmx_multi_render_nee(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats);
+int vmx_multi_render_nee_device(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz, vmx_stats *stats);
+int vmx_radiance_nee_device(const vmx_scene *scene, const void *d_origin, const void *d_dir, uint32_t n, const vmx_opts *opts,
+                            void *d_out4, vmx_stats *stats, void *stream);
+
 /* ---- frame output (the step after the path; replaces the conversion loop of
  * Camera::saveFrame, core/camera/camera.cpp:140-175, for the default RGBAZ mode) ------------ */
 /*

@@ -125,4 +125,24 @@ void HipBruteForceTracer::Render(std::vector<Vermilion::Camera *> &cameraList, M
     }
 }
 
+void HipLightSamplingTracer::Render(std::vector<Vermilion::Camera *> &cameraList, MeshEngine *mEng) {
+    if (!mEng || !upload(mEng)) return;
+    for (Camera *cam : cameraList) {
+        const vmx_camera c = describe(cam);
+        vmx_opts o;
+        std::memset(&o, 0, sizeof(o));
+        o.seed = mSeed;
+        o.sampling = VMX_SAMPLING_CORRECTED;  // the one mode light sampling accepts; no early stop
+        std::vector<float> frame((size_t)cam->RenderTargetSize * 5);
+        vmx_stats st;
+        const int rc = mMulti ? vmx_multi_render_nee(mMulti, &c, &o, frame.data(), &st) : vmx_render_nee(mScene, &c, &o, frame.data(), &st);
+        if (rc != VMX_OK) {
+            std::fprintf(stderr, "HipLightSamplingTracer: %s\n", vmx_last_error());
+            continue;
+        }
+        cam->uRaysFired = st.rays_primary + st.rays_secondary;  // bounce and shadow rays
+        writeBack(cam, frame);
+    }
+}
+
 }  // namespace Vermilion

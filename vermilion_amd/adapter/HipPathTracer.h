@@ -88,4 +88,15 @@ class HipBruteForceTracer : public HipIntegratorBase {
     uint32_t mFlags;
 };
 
+// A third integrator, this build's own (the reference has none): `corrected` path tracing with next-event estimation
+// (vmx_render_nee, include/vermilion_hip.h "light sampling"; over a device list vmx_multi_render_nee).  Installed like
+// the other two.  Fixed sample count (the reference's early stop does not apply), VMX_SAMPLING_CORRECTED; the frame's
+// fifth float, written to pixelValue::depth like PathTracer's, is the sample count.
+class HipLightSamplingTracer : public HipIntegratorBase {
+   public:
+    explicit HipLightSamplingTracer(uint64_t seed = 1, int device = 0) : HipIntegratorBase(seed, {device}) {}
+    HipLightSamplingTracer(uint64_t seed, std::vector<int> devices) : HipIntegratorBase(seed, std::move(devices)) {}
+    void Render(std::vector<Vermilion::Camera *> &cameraList, MeshEngine *mEng) override;
+};
+
 }  // namespace Vermilion

@@ -321,6 +321,29 @@ int vmx_multi_render_bruteforce(vmx_multi *m, const vmx_camera *cam, const vmx_o
                         });
 }
 
+// Light sampling over the device list: every replica renders its stripes through the routine of vmx_render_nee_rank*
+// (nee_render_impl).  The opts are checked as vmx_render_nee checks them — a caller's world > 1 is refused, the library
+// sets rank and world — and the vmx_multi comes last, so that each refusal can be seen without a device.
+static int multi_render_nee(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, float *out_host, void *d_out_root,
+                            vmx_stats *stats) {
+    if (!cam || !opts || (!out_host && !d_out_root)) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts)) return rc;
+    if (!m) return fail(VMX_ERR_INVALID, "NULL vmx_multi");
+    std::lock_guard<std::mutex> lock(m->mu);
+    return multi_render(m, cam, opts, out_host, d_out_root, stats,
+                        [&](vmx_scene *sc, const vmx_opts *o, float *d_out, vmx_stats *st) {
+                            return nee_render_impl(sc, cam, o, d_out, sc->stream, st);
+                        });
+}
+
+int vmx_multi_render_nee(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats) {
+    return multi_render_nee(m, cam, opts, out_rgbaz, nullptr, stats);
+}
+
+int vmx_multi_render_nee_device(vmx_multi *m, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz, vmx_stats *stats) {
+    return multi_render_nee(m, cam, opts, nullptr, d_out_rgbaz, stats);
+}
+
 } /* extern "C" */
 
 extern "C" {

@@ -1,8 +1,15 @@
-// api_nee.inc — part of vmx_api.cpp: the light-sampling integrator, vmx_render_nee* and vmx_radiance_nee (k_nee, vmx_nee.inc)
+// api_nee.inc — part of vmx_api.cpp: the light-sampling integrator, vmx_render_nee*, their rank forms and vmx_radiance_nee* (k_nee, vmx_nee.inc)
+extern "C" {
+namespace {
+int check_device_ptr(const void *p, int device, const char *what);  // api_query.inc
+}
+}
+
 namespace {
 
-// what the entries accept of a vmx_opts (include/vermilion_hip.h, "light sampling")
-int nee_check_opts(const vmx_opts *o) {
+// what the entries accept of a vmx_opts (include/vermilion_hip.h, "light sampling"); ranks: the entry renders a rank's
+// stripes (the *_rank entries), so world > 1 passes here and make_frame checks the rank against it
+int nee_check_opts(const vmx_opts *o, bool ranks = false) {
     if ((o->sampling & VMX_SAMPLING_MODE_MASK) > VMX_SAMPLING_CORRECTED ||
         (o->sampling & ~(VMX_SAMPLING_MODE_MASK | VMX_SAMPLING_LIBM_DOUBLE | VMX_SAMPLING_ELIDE_DEAD)))
         return fail(VMX_ERR_INVALID, "unknown sampling mode");
@@ -10,7 +17,7 @@ int nee_check_opts(const vmx_opts *o) {
     if ((o->sampling & VMX_SAMPLING_MODE_MASK) != VMX_SAMPLING_CORRECTED)
         return fail(VMX_ERR_INVALID, "light sampling: sampling must be VMX_SAMPLING_CORRECTED");
     if (o->early_stop) return fail(VMX_ERR_INVALID, "light sampling: early_stop is not supported");
-    if (o->world > 1) return fail(VMX_ERR_INVALID, "light sampling: world > 1 is not supported");
+    if (o->world > 1 && !ranks) return fail(VMX_ERR_INVALID, "light sampling: world > 1 is not supported");
     if (o->collect_counters) return fail(VMX_ERR_INVALID, "light sampling: collect_counters is not supported");
     if (o->reserved[0]) return fail(VMX_ERR_INVALID, "light sampling: reserved[0] must be 0");
     return VMX_OK;
@@ -31,27 +38,34 @@ int nee_render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, 
     return render_run(sc, job, 0, stats, t0);
 }
 
-}  // namespace
-
-extern "C" {
-
-int vmx_render_nee_device(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz, vmx_stats *stats,
-                          void *stream) {
+// vmx_render_nee_device and its rank form: the checks that need no device, the scene last
+int nee_render_device_entry(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, void *d_out, vmx_stats *stats,
+                            void *stream, bool ranks) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
-    if (!cam || !opts || !d_out_rgbaz) return fail(VMX_ERR_INVALID, "NULL argument");
-    if (int rc = nee_check_opts(opts)) return rc;
+    if (!cam || !opts || !d_out) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts, ranks)) return rc;
+    if (ranks) {  // (the rank against the world, with make_frame's other checks, before the scene: each can be seen alone)
+        FrameDev fr;
+        if (int rc = make_frame(*cam, *opts, fr)) return rc;
+    }
     if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");  // (last: the checks above need no scene)
     std::lock_guard<std::mutex> lock(sc->mu);
     int rc = bind_device(sc);
     if (rc) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : sc->stream;
-    return nee_render_impl(sc, cam, opts, (float *)d_out_rgbaz, s, stats);
+    return nee_render_impl(sc, cam, opts, (float *)d_out, s, stats);
 }
 
-int vmx_render_nee(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats) {
+// vmx_render_nee and its rank form
+int nee_render_host_entry(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, float *out, vmx_stats *stats,
+                          bool ranks) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
-    if (!cam || !opts || !out_rgbaz) return fail(VMX_ERR_INVALID, "NULL argument");
-    if (int rc = nee_check_opts(opts)) return rc;
+    if (!cam || !opts || !out) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts, ranks)) return rc;
+    if (ranks) {
+        FrameDev fr;
+        if (int rc = make_frame(*cam, *opts, fr)) return rc;
+    }
     if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
     std::lock_guard<std::mutex> lock(sc->mu);
     int rc = bind_device(sc);
@@ -59,14 +73,103 @@ int vmx_render_nee(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *
     FrameDev fr;
     rc = make_frame(*cam, *opts, fr);
     if (rc) return rc;
-    const size_t nfloats = (size_t)fr.width * fr.local_rows * 5;
+    const size_t nfloats = (size_t)fr.width * fr.local_rows * 5;  // (0: a rank that owns no row — nothing is copied)
     if (sc->ws.out.ensure(nfloats)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the frame buffer");
     rc = nee_render_impl(sc, cam, opts, sc->ws.out.p, sc->stream, stats);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_rgbaz, sc->ws.out.p, nfloats * 4, hipMemcpyDeviceToHost));
+    if (nfloats) HIP_TRY(hipMemcpy(out, sc->ws.out.p, nfloats * 4, hipMemcpyDeviceToHost));
     return VMX_OK;
 }
 
+// One batch of n rays in k_nee's ray form, device to device on `s`; blocks until it is done (the stats are the counters'
+// read-back).  The caller holds sc->mu, has bound the device and has checked the pointers.
+int radiance_nee_run(vmx_scene *sc, const float *d_o, const float *d_d, uint32_t n, const vmx_opts *opts, void *d_out4,
+                     vmx_stats *stats, hipStream_t s, std::chrono::steady_clock::time_point t0) {
+    Workspace &ws = sc->ws;
+    int rc;
+    if ((rc = sc->upd.done.wait(s))) return rc;
+    const Tuning tn = make_tuning(sc, opts);
+    FrameDev fr;
+    std::memset(&fr, 0, sizeof(fr));
+    fr.r2scale = 1.0f;
+    fr.libm_double = (opts->sampling & VMX_SAMPLING_LIBM_DOUBLE) ? 1u : 0u;
+    fr.seed = opts->seed;
+    if (ws.heads.ensure(kSubQueues * 32) || ws.counters.ensure(1)) return fail(VMX_ERR_NOMEM, "hipMalloc failed");
+    WorkDev wk;
+    std::memset(&wk, 0, sizeof(wk));
+    wk.heads = ws.heads.p;
+    LaunchCfg cfg;
+    if ((rc = nee_launch_cfg(sc, tn, n, true, wk, cfg))) return rc;
+    ws.events.reset();
+    std::vector<TimedLaunch> timed;
+    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
+    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(ev0, s));
+    HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+    HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
+    if ((rc = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return rc;
+    LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o, d_d, n, d_out4, ws.counters.p, cfg, s));
+    if ((rc = timed_end(timed, s))) return rc;
+    HIP_TRY(hipEventRecord(ev1, s));
+    rc = finish_stats(sc, s, timed, ev0, ev1, stats, 1, 1, t0);
+    if (rc == VMX_OK && stats) stats->samples = n;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmx_render_nee_device(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, void *d_out_rgbaz, vmx_stats *stats,
+                          void *stream) {
+    return nee_render_device_entry(csc, cam, opts, d_out_rgbaz, stats, stream, false);
+}
+
+int vmx_render_nee(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, float *out_rgbaz, vmx_stats *stats) {
+    return nee_render_host_entry(csc, cam, opts, out_rgbaz, stats, false);
+}
+
+int vmx_render_nee_rank_device(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, void *d_out_local,
+                               vmx_stats *stats, void *stream) {
+    return nee_render_device_entry(csc, cam, opts, d_out_local, stats, stream, true);
+}
+
+int vmx_render_nee_rank(const vmx_scene *csc, const vmx_camera *cam, const vmx_opts *opts, float *out_local, vmx_stats *stats) {
+    return nee_render_host_entry(csc, cam, opts, out_local, stats, true);
+}
+
+int vmx_radiance_nee_device(const vmx_scene *csc, const void *d_origin, const void *d_dir, uint32_t n, const vmx_opts *opts,
+                            void *d_out4, vmx_stats *stats, void *stream) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    // checks that need no device, in this order so that each can be seen alone; the scene comes last
+    if (!d_origin || !d_dir || !opts || !d_out4) return fail(VMX_ERR_INVALID, "NULL argument");
+    if (int rc = nee_check_opts(opts)) return rc;
+    if (n == 0) return VMX_OK;  // (nothing to do, whatever the scene)
+    if (((uintptr_t)d_origin | (uintptr_t)d_dir) & 3u) return fail(VMX_ERR_INVALID, "the rays must be 4-byte aligned");
+    if ((uintptr_t)d_out4 & 15u) return fail(VMX_ERR_INVALID, "d_out4 must be 16-byte aligned");
+    if (n > 0x7FFFFFFFu) return fail(VMX_ERR_INVALID, "more than 2^31 - 1 rays");
+    {
+        // the results are written while other rays are still read: [out, out + 16 n) must not meet either ray array
+        const uintptr_t a = (uintptr_t)d_out4, b = a + (uintptr_t)n * 16;
+        const uintptr_t ro[2] = {(uintptr_t)d_origin, (uintptr_t)d_dir};
+        for (uintptr_t r : ro)
+            if (r < b && a < r + (uintptr_t)n * 12) return fail(VMX_ERR_INVALID, "d_out4 overlaps the rays");
+    }
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lock(sc->mu);
+    int rc = bind_device(sc);
+    if (rc) return rc;
+    if ((rc = check_device_ptr(d_origin, sc->device, "origin")) || (rc = check_device_ptr(d_dir, sc->device, "dir")) ||
+        (rc = check_device_ptr(d_out4, sc->device, "d_out4")))
+        return rc;
+    return radiance_nee_run(sc, (const float *)d_origin, (const float *)d_dir, n, opts, d_out4, stats,
+                            stream ? (hipStream_t)stream : sc->stream, t0);
+}
+
+// upload, vmx_radiance_nee_device's routine, download
 int vmx_radiance_nee(const vmx_scene *csc, const float *origin, const float *dir, uint32_t n, const vmx_opts *opts, float *out4,
                      vmx_stats *stats) {
     vmx_scene *sc = const_cast<vmx_scene *>(csc);
@@ -80,45 +183,18 @@ int vmx_radiance_nee(const vmx_scene *csc, const float *origin, const float *dir
     if (rc) return rc;
     Workspace &ws = sc->ws;
     hipStream_t s = sc->stream;
-    if ((rc = sc->upd.done.wait(s))) return rc;
-    const Tuning tn = make_tuning(sc, opts);
-    FrameDev fr;
-    std::memset(&fr, 0, sizeof(fr));
-    fr.r2scale = 1.0f;
-    fr.libm_double = (opts->sampling & VMX_SAMPLING_LIBM_DOUBLE) ? 1u : 0u;
-    fr.seed = opts->seed;
     DevBuf<float> d_o, d_d;
-    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || ws.rad.ensure((size_t)n * 16) || ws.heads.ensure(kSubQueues * 32) ||
-        ws.counters.ensure(1))
+    if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3) || ws.rad.ensure((size_t)n * 16))
         return fail(VMX_ERR_NOMEM, "hipMalloc failed");
-    WorkDev wk;
-    std::memset(&wk, 0, sizeof(wk));
-    wk.heads = ws.heads.p;
-    LaunchCfg cfg;
-    if ((rc = nee_launch_cfg(sc, tn, n, true, wk, cfg))) return rc;
-    ws.events.reset();
-    std::vector<TimedLaunch> timed;
-    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
-    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
     auto body = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_o.p, origin, (size_t)n * 12, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_d.p, dir, (size_t)n * 12, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ev0, s));
-        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
-        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
-        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
-        HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
-        int r;
-        if ((r = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return r;
-        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o.p, d_d.p, n, ws.rad.p, ws.counters.p, cfg, s));
-        if ((r = timed_end(timed, s))) return r;
-        HIP_TRY(hipEventRecord(ev1, s));
-        HIP_TRY(hipMemcpyAsync(out4, ws.rad.p, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-        return finish_stats(sc, s, timed, ev0, ev1, stats, 1, 1, t0);
+        if (int r = radiance_nee_run(sc, d_o.p, d_d.p, n, opts, ws.rad.p, stats, s, t0)) return r;
+        HIP_TRY(hipMemcpy(out4, ws.rad.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+        return VMX_OK;
     };
     rc = body();
     if (rc) (void)hipStreamSynchronize(s);  // (what was enqueued may still use d_o / d_d, which are freed here)
-    if (rc == VMX_OK && stats) stats->samples = n;
     return rc;
 }
 

@@ -42,9 +42,10 @@ int vmx_progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *
     return vmx_progressive_begin_ex(sc, cam, opts, 0, stream, out);
 }
 
-// nee: a light-sampled handle (vmx_progressive_begin_nee), whose passes run k_nee (RenderJob::nee)
+// nee: a light-sampled handle (vmx_progressive_begin_nee), whose passes run k_nee (RenderJob::nee); ranks: its rank form
+// (vmx_progressive_begin_nee_rank), which accepts world > 1
 static int progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
-                             vmx_progressive **out, bool nee) {
+                             vmx_progressive **out, bool nee, bool ranks = false) {
     // checks that need no device, in this order so that each can be seen alone; the scene comes last
     if (!cam || !opts) return fail(VMX_ERR_INVALID, "NULL argument: cam or opts");
     if (!out) return fail(VMX_ERR_INVALID, "NULL out");
@@ -52,7 +53,7 @@ static int progressive_begin(vmx_scene *sc, const vmx_camera *cam, const vmx_opt
         return fail(VMX_ERR_INVALID, nee ? "vmx_progressive_begin_nee: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)"
                                          : "vmx_progressive_begin_ex: unknown flag (0 or VMX_PROGRESSIVE_MOMENTS)");
     if (nee)
-        if (int rc = nee_check_opts(opts)) return rc;
+        if (int rc = nee_check_opts(opts, ranks)) return rc;
     {
         FrameDev fr;
         if (int rc = make_frame(*cam, *opts, fr)) return rc;
@@ -93,6 +94,11 @@ int vmx_progressive_begin_ex(vmx_scene *sc, const vmx_camera *cam, const vmx_opt
 int vmx_progressive_begin_nee(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
                               vmx_progressive **out) {
     return progressive_begin(sc, cam, opts, flags, stream, out, true);
+}
+
+int vmx_progressive_begin_nee_rank(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, uint32_t flags, void *stream,
+                                   vmx_progressive **out) {
+    return progressive_begin(sc, cam, opts, flags, stream, out, true, true);
 }
 
 int vmx_progressive_step(vmx_progressive *p, uint32_t samples, vmx_stats *stats) {

@@ -38,6 +38,30 @@ def assemble_host(parts, width, height, stripe_rows, world):
     return frame
 
 
+def render_nee_local(scene, cam, opts, stream=None):
+    """One rank's share of a light-sampled frame (Scene.render_nee_rank_device): the rows (opts.rank, opts.world,
+    opts.stripe_rows) owns, packed, as a cuda tensor [local_rows, W, 5] on the scene's device, and the rank's statistics.
+    A rank without rows returns an empty tensor.  stream: a torch stream to render on (default: the scene's own)."""
+    import torch
+    rows = len(local_row_indices(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world))
+    width = int(cam.image_res[0])
+    # (at least one float: the entry wants a pointer even where it writes nothing)
+    buf = torch.empty((max(rows * width * 5, 1),), dtype=torch.float32, device="cuda:%d" % scene.device)
+    st = scene.render_nee_rank_device(cam, opts, buf.data_ptr(), stream.cuda_stream if stream is not None else None)
+    return buf[: rows * width * 5].view(rows, width, 5), st
+
+
+def render_nee_gathered(scene, cam, opts, dst=0, group=None, times=None):
+    """The process-per-GPU form of Scene.render_nee: this rank renders its stripes (render_nee_local) and the packed rows
+    go through gather_frame, which does not depend on the integrator.  Returns (frame [H, W, 5] on dst, None elsewhere;
+    this rank's statistics)."""
+    local, st = render_nee_local(scene, cam, opts)
+    stripe = opts.stripe_rows if opts.stripe_rows else 16
+    frame = gather_frame(local, int(cam.image_res[0]), int(cam.image_res[1]), stripe, opts.rank, max(opts.world, 1), dst=dst,
+                         group=group, times=times)
+    return frame, st
+
+
 class ExchangeTimes:
     """The exchange step of gather_frame timed apart from the rendering ("gather time separately"): event
     pairs on the current HIP stream around the gather and around the de-interleave kernel (wall-clock pairs for CPU

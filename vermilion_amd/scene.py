@@ -812,11 +812,13 @@ class Scene:
         self._check(self._lib.vmx_render_nee(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
         return out, st.as_dict()
 
-    def progressive_nee(self, cam, opts, stream=None, moments=False):
+    def progressive_nee(self, cam, opts, stream=None, moments=False, rank=False):
         """vmx_progressive_begin_nee: the frame `render_nee(cam, opts)` returns, rendered in resumable steps (a
         context-managed Progressive whose passes run the light-sampling integrator).  Every method of Progressive works on
-        it; `budget_device`, `step_budget` and `step_budgeted` work on such a handle only."""
-        return Progressive(self, cam, opts, stream, moments, nee=True)
+        it; `budget_device`, `step_budget` and `step_budgeted` work on such a handle only.  rank
+        (vmx_progressive_begin_nee_rank): opts.world > 1 is accepted and the handle holds `render_nee_rank`'s rows; its
+        planes, maps and budgets are indexed by local pixel and their windows stop at the rank's own rows."""
+        return Progressive(self, cam, opts, stream, moments, nee=True, rank=rank)
 
     def render_nee_device(self, cam, opts, d_out_ptr, stream_ptr=None):
         """Same, into device memory (e.g. a torch tensor's data_ptr()) on `stream_ptr`."""
@@ -836,12 +838,39 @@ class Scene:
                                                C.byref(st)))
         return out, st.as_dict()
 
+    def radiance_nee_device(self, d_origin_ptr, d_dir_ptr, n, opts, d_out4_ptr, stream_ptr=None):
+        """vmx_radiance_nee_device: `radiance_nee` on device arrays of the scene's device (n x 3 floats each, the result
+        n x 4 floats, 16-byte aligned), enqueued on `stream_ptr` (default: the scene's stream); blocks until the batch is
+        done and returns its statistics."""
+        st = L.Stats()
+        self._check(self._lib.vmx_radiance_nee_device(self._h, C.c_void_p(d_origin_ptr), C.c_void_p(d_dir_ptr), int(n),
+                                                      C.byref(opts), C.c_void_p(d_out4_ptr), C.byref(st),
+                                                      C.c_void_p(stream_ptr or 0)))
+        return st.as_dict()
+
+    def render_nee_rank(self, cam, opts):
+        """vmx_render_nee_rank: the rows of `render_nee`'s frame that (opts.rank, opts.world, opts.stripe_rows) owns, packed in
+        ascending order into a host array [local_rows, W, 5]; the statistics cover those pixels only."""
+        rows = local_rows(cam.image_res[1], opts.stripe_rows, opts.rank, opts.world)
+        n = rows * cam.image_res[0] * 5
+        buf = np.empty(max(n, 1), np.float32)  # (a rank without rows still hands the entry a pointer)
+        st = L.Stats()
+        self._check(self._lib.vmx_render_nee_rank(self._h, C.byref(cam), C.byref(opts), buf.ctypes.data, C.byref(st)))
+        return buf[:n].reshape(rows, cam.image_res[0], 5), st.as_dict()
+
+    def render_nee_rank_device(self, cam, opts, d_out_ptr, stream_ptr=None):
+        """Same, into device memory (local_rows * W * 5 floats) on `stream_ptr`; a rank that owns no row writes nothing."""
+        st = L.Stats()
+        self._check(self._lib.vmx_render_nee_rank_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(d_out_ptr),
+                                                         C.byref(st), C.c_void_p(stream_ptr or 0)))
+        return st.as_dict()
+
 
 class Progressive:
     """One vmx_progressive handle: `step` issues samples, `preview` shows the frame so far, and the frame a completed
     handle previews is `Scene.render`'s, bit for bit, whatever the steps were."""
 
-    def __init__(self, scene, cam, opts, stream=None, moments=False, nee=False):
+    def __init__(self, scene, cam, opts, stream=None, moments=False, nee=False, rank=False):
         self._scene = scene  # (keeps the scene alive: it cannot be destroyed before its handles)
         self.moments = bool(moments)
         self.nee = bool(nee)
@@ -853,9 +882,12 @@ class Progressive:
         self.shape = (rows, int(cam.image_res[0]))
         h = C.c_void_p()
         sptr = C.c_void_p(stream.cuda_stream if stream is not None else 0)
+        if rank and not nee:
+            raise ValueError("rank=True is the light-sampled handle's rank form: a plain handle takes opts.world > 1 as it is")
         if nee:
-            scene._check(self._lib.vmx_progressive_begin_nee(scene._h, C.byref(cam), C.byref(opts),
-                                                             L.VMX_PROGRESSIVE_MOMENTS if moments else 0, sptr, C.byref(h)))
+            begin = self._lib.vmx_progressive_begin_nee_rank if rank else self._lib.vmx_progressive_begin_nee
+            scene._check(begin(scene._h, C.byref(cam), C.byref(opts), L.VMX_PROGRESSIVE_MOMENTS if moments else 0, sptr,
+                               C.byref(h)))
         elif moments:
             scene._check(self._lib.vmx_progressive_begin_ex(scene._h, C.byref(cam), C.byref(opts), L.VMX_PROGRESSIVE_MOMENTS,
                                                             sptr, C.byref(h)))
@@ -1166,6 +1198,19 @@ class MultiScene:
         L.check(L.lib().vmx_multi_render_bruteforce(self._h, C.byref(cam), C.byref(opts), int(flags), out.ctypes.data,
                                                     C.byref(st)))
         return out, st.as_dict()
+
+    def render_nee(self, cam, opts):
+        """vmx_multi_render_nee: `Scene.render_nee`'s frame, each replica rendering its stripes; opts.world must be 0 or 1"""
+        out = np.empty((cam.image_res[1], cam.image_res[0], 5), np.float32)
+        st = L.Stats()
+        L.check(L.lib().vmx_multi_render_nee(self._h, C.byref(cam), C.byref(opts), out.ctypes.data, C.byref(st)))
+        return out, st.as_dict()
+
+    def render_nee_device(self, cam, opts, d_out_ptr):
+        """Same, into device memory on devices[0]"""
+        st = L.Stats()
+        L.check(L.lib().vmx_multi_render_nee_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(d_out_ptr), C.byref(st)))
+        return st.as_dict()
 
 
 RAYHIT_DTYPE = np.dtype([
