@@ -456,20 +456,50 @@ uint32_t claim_min_samples() {
 
 // the per-pixel claims of the frame `fr` from the camera tables in the workspace, into ws.claims[0, npix) and the number
 // of claimed pixels into ws.claims[npix]; lists: the list records of the pixels without a claim into ws.claim_lists too, in
-// the same launch
+// a second launch: k_pixel_claims settles the claims and the empty records and marks, per 8 x 8 tile, the pixels whose
+// list is still to be made; those are listed in tile order on the device (the scan of the live list) and k_pixel_lists
+// walks for them in full waves.  The list's length stays on the device: nothing here waits for the stream.
 int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t npix, bool lists, hipStream_t s) {
     Workspace &ws = sc->ws;
-    if (ws.claims.ensure((size_t)npix + 1)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the pixel claims");
+    if (ws.claims.ensure((size_t)npix + 2)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the pixel claims");  // (+ the count, + the claim kernel's work head)
     if (lists && ws.claim_lists.ensure((size_t)npix * kListWords)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the claim lists");
     WorkDev wk;
     std::memset(&wk, 0, sizeof(wk));
     wk.cam_inner = ws.cam_inner.p, wk.cam_tris = ws.cam_inner.p + std::max<size_t>(sc->n_inner, 1) * 64 * 8;
-    const uint32_t tiles = ((fr.width + 7u) / 8u) * ((fr.local_rows + 7u) / 8u);
-    LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, (uint64_t)tiles * 64, 8);
-    int rc = bind_stack(sc, tn, tn.lds_primary, cfg.grid, (uint64_t)tiles * 64, wk);
+    const uint64_t tiles = (uint64_t)((fr.width + 7u) / 8u) * ((fr.local_rows + 7u) / 8u);
+    if (tiles * 64 > 0xFFFFFFFFull) return fail(VMX_ERR_INVALID, "frame too large for the pixel claims");
+    // both kernels run on a resident grid and hand out their work on the device
+    int cblocks = 0;
+    HIP_TRY((hipError_t)query_pixel_claims_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_primary + 1) * 512, &cblocks));
+    if (cblocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
+    LaunchCfg cfg = paths_cfg(sc, tn.lds_primary, tiles * 64, cblocks);
+    LaunchCfg lcfg = cfg;
+    size_t tmp_bytes = 0;
+    if (lists) {
+        // the list kernel's grid, or less for a frame with fewer pixels than that; the
+        // stack binding (LDS levels, overflow slab) is the claim kernel's, sized for the larger of the two grids
+        int blocks = 0;
+        HIP_TRY((hipError_t)query_pixel_lists_blocks_per_cu(kPathsBlock, cfg.lds_bytes, &blocks));
+        if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
+        lcfg = paths_cfg(sc, tn.lds_primary, (uint64_t)npix, blocks);
+        tmp_bytes = live_compact_tmp_bytes((uint32_t)tiles);
+        if (ws.claim_pend_mask.ensure(tiles) || ws.claim_pend_u32.ensure(2 * tiles + 2) || ws.claim_pend_ids.ensure(npix) ||
+            ws.claim_pend_tmp.ensure(tmp_bytes + 256))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the list of pixels without a claim");
+    }
+    int rc = bind_stack(sc, tn, tn.lds_primary, std::max(cfg.grid, lcfg.grid), tiles * 64, wk);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ws.claims.p + npix, 0, 4, s));
-    LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, lists ? ws.claim_lists.p : nullptr, ws.claims.p + npix, cfg, s));
+    HIP_TRY(hipMemsetAsync(ws.claims.p + npix, 0, 8, s));
+    if (!lists) {
+        LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, nullptr, ws.claims.p + npix, nullptr, nullptr, cfg, s));
+    } else {
+        unsigned int *cnt = ws.claim_pend_u32.p, *offs = cnt + tiles, *len = offs + tiles, *head = len + 1;
+        LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, ws.claim_lists.p, ws.claims.p + npix, ws.claim_pend_mask.p, cnt, cfg, s));
+        HIP_TRY(hipMemsetAsync(len, 0, 8, s));  // (the list's length and the list kernel's work head)
+        HIP_TRY((hipError_t)launch_live_compact(ws.claim_pend_mask.p, cnt, (uint32_t)tiles, offs, ws.claim_pend_ids.p, len,
+                                                ws.claim_pend_tmp.p, tmp_bytes, s));
+        LAUNCH_TRY(launch_pixel_lists(sc->dev, fr, wk, ws.claim_pend_ids.p, len, head, ws.claim_lists.p, lcfg, s));
+    }
     return VMX_OK;
 }
 

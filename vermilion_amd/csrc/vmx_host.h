@@ -142,6 +142,11 @@ struct Workspace {
     DevBuf<unsigned char> cam_inner;                    // per-frame camera-relative scene tables: 8 node copies, then the triangles
     DevBuf<unsigned int> claims;                        // per-pixel claims of the run's frame (pixel_claim.h) + the number of claimed pixels
     DevBuf<unsigned int> claim_lists;                   // ... and the list records of its pixels without a claim (kListWords words each)
+    // the pixels whose list k_pixel_lists makes (build_claims): their bits per tile; [popcounts | their exclusive scan |
+    // the list's length, the kernel's work head]; the tile-ordered list; scan scratch
+    DevBuf<unsigned long long> claim_pend_mask;
+    DevBuf<unsigned int> claim_pend_u32, claim_pend_ids;
+    DevBuf<unsigned char> claim_pend_tmp;
     // passes that fuse their claimed pixels: the ordered lists of the pass's unclaimed and claimed slots, rebuilt per pass;
     // "unclaimed" bits per 64 slots; [popcounts | their exclusive scan | the two lists' lengths]; scan scratch
     DevBuf<unsigned int> unclaimed, claimed_slots, unclaimed_u32;

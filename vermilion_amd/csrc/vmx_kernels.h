@@ -230,9 +230,19 @@ int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, in
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
                          void *cam_tris, void *stream);
 // the per-pixel claims of a frame (pixel_claim.h) from the camera tables in wk: claims[local pixel], *n_claimed += the
-// pixels with a slot or a miss claim; lists (or NULL: none): the list records of the pixels without one; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
+// pixels with a slot or a miss claim (n_claimed[1]: the kernel's work head, zeroed by the caller like the count; the grid
+// is persistent, query_pixel_claims_blocks_per_cu blocks per CU); lists (or NULL: none): the list records of the pixels without one; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
+// With lists the launch settles the empty records and leaves, per 8 x 8 tile, one word with the bits of the pixels whose
+// list is still to be made and its popcount (pend_mask, pend_cnt: one per tile), their (cand, other) parked in their
+// records; launch_live_compact lists them in tile order (entry = tile * 64 + lane) and launch_pixel_lists walks for them,
+// one lane per entry: *count entries, *head zeroed by the caller, a persistent grid of query_pixel_lists_blocks_per_cu
+// blocks per CU (wk as above, its overflow slab sized for that grid)
 int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *lists, unsigned int *n_claimed,
-                        LaunchCfg cfg, void *stream);
+                        unsigned long long *pend_mask, unsigned int *pend_cnt, LaunchCfg cfg, void *stream);
+int launch_pixel_lists(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, const unsigned int *entries, const unsigned int *count,
+                       unsigned int *head, unsigned int *lists, LaunchCfg cfg, void *stream);
+int query_pixel_claims_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks);
+int query_pixel_lists_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks);
 int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
 int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
 size_t live_compact_tmp_bytes(uint32_t nwords);

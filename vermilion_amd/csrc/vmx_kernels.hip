@@ -1838,6 +1838,11 @@ __global__ void k_camera_tables(SceneDev sc, uint32_t n_inner, float ox, float o
 // its origin: one lane per pixel, a wave per 8 x 8 tile (neighbouring pixels walk the same nodes), the stack in LDS
 // levels plus the global slab as in k_bruteforce.  The walk itself is the header's, shared with the host program of
 // tests/cpp/pixel_claim_test.cpp: same arithmetic, same table.
+// lists (or NULL): the second plane.  This kernel settles the record of every pixel that gets the empty one — a pixel with
+// a claim, or one whose claim walk left no candidate to start a list from — and parks (cand, other) of the others in
+// their records; per tile it leaves one word with the bits of those pixels and its popcount (pend_mask, pend_cnt:
+// indexed by tile, every tile written).  launch_live_compact lists them in tile order (entry = tile * 64 + lane) and
+// k_pixel_lists walks for them in full waves: the list walks run for a third of the pixels, scattered over most tiles.
 // ---------------------------------------------------------------------------
 struct ClaimStack {
     uint2 *stk, *ovf;
@@ -1848,9 +1853,10 @@ struct ClaimStack {
         ref = e.x, near = __uint_as_float(e.y);
     }
 };
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 7)
 k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, const float *__restrict__ cam_tris,
-               unsigned int *__restrict__ claims, unsigned int *__restrict__ lists, unsigned int *n_claimed, uint32_t lds_levels,
+               unsigned int *__restrict__ claims, unsigned int *__restrict__ lists, unsigned int *n_claimed,
+               unsigned long long *__restrict__ pend_mask, unsigned int *__restrict__ pend_cnt, uint32_t lds_levels,
                uint32_t overflow_entries, void *overflow_stack) {
     extern __shared__ uint2 lds_stack[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -1863,26 +1869,76 @@ k_pixel_claims(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, co
     fm.width = fr.width, fm.height = fr.height, fm.sensor_x = fr.sensor_x, fm.sensor_y = fr.sensor_y, fm.film_dist = fr.film_dist;
     const uint32_t tiles_x = (fr.width + 7u) / 8u, tiles = tiles_x * ((fr.local_rows + 7u) / 8u);
     uint32_t n = 0;
-    for (uint32_t tile = blockIdx.x * (blockDim.x >> 6) + wave; tile < tiles; tile += gridDim.x * (blockDim.x >> 6)) {
+    // a resident grid whose waves take the next tile when they are free (n_claimed[1]: the work head, zeroed with the
+    // count).  With equal shares of the tiles and more waves than are resident, the waves of this launch lived 0.57 ms
+    // of its 1.45 ms (profiles/claim_walks.txt)
+    for (;;) {
+        uint32_t tile = 0;
+        if (lane == 0) tile = atomicAdd(n_claimed + 1, 1u);
+        tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile);
+        if (tile >= tiles) break;
         const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
         const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+        bool walks = false, claimed = false;  // walks: this pixel's list is k_pixel_lists' to make
         if (x < fr.width && y < fr.local_rows) {
             const uint32_t lp = y * fr.width + x;
-            uint32_t c;
-            if (lists) {  // both planes: the list of a pixel without a claim (an empty one for the others)
-                uint32_t l[kListWords];
-                c = pc_pixel_claim_and_list(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk,
-                                            (int)(lds_levels + overflow_entries), l);
-                ((uint4 *)lists)[lp] = make_uint4(l[0], l[1], l[2], l[3]);
-            } else {
-                c = pc_pixel_claim(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk, (int)(lds_levels + overflow_entries));
+            int cand, other;
+            const uint32_t c = pc_pixel_claim_cand(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk,
+                                                   (int)(lds_levels + overflow_entries), cand, other);
+            if (lists) {
+                // (pc_pixel_list returns the empty record for a pixel with a claim and for cand < -1 before it looks at anything else)
+                walks = c == kClaimNone && cand >= -1;
+                ((uint4 *)lists)[lp] = walks ? make_uint4((uint32_t)cand, (uint32_t)other, kClaimNone, kClaimNone)
+                                             : make_uint4(kClaimNone, kClaimNone, kClaimNone, kClaimNone);
             }
             claims[lp] = c;
-            n += c != kClaimNone ? 1u : 0u;
+            claimed = c != kClaimNone;
+        }
+        n += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(claimed));  // (wave-uniform: every lane of the wave is here)
+        if (lists) {
+            const unsigned long long bits = __builtin_amdgcn_ballot_w64(walks);
+            if (lane == 0) pend_mask[tile] = bits, pend_cnt[tile] = (uint32_t)__popcll(bits);
         }
     }
-    n = wave_sum(n);
     if (lane == 0 && n) atomicAdd(n_claimed, n);
+}
+
+// k_pixel_lists — pc_pixel_list for the entries k_pixel_claims left, one lane per entry: persistent waves take 64
+// consecutive entries of the tile-ordered list at a time (*head, zeroed by the host; *count is the list's length, known
+// on the device only), so the lanes of a wave are neighbouring edge pixels.  A pixel's record depends on the pixel and
+// on the (cand, other) parked in it alone, not on the lane or wave that walks for it.
+__global__ void __launch_bounds__(256, 5)
+k_pixel_lists(SceneDev sc, FrameDev fr, const float *__restrict__ cam_inner, const float *__restrict__ cam_tris,
+              const unsigned int *__restrict__ entries, const unsigned int *__restrict__ count, unsigned int *head,
+              unsigned int *__restrict__ lists, uint32_t lds_levels, uint32_t overflow_entries, void *overflow_stack) {
+    extern __shared__ uint2 lds_stack[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    ClaimStack stk;
+    stk.stk = lds_stack + (size_t)wave * (lds_levels + 1) * 64 + lane;
+    stk.ovf = (uint2 *)overflow_stack + ((size_t)(blockIdx.x * (blockDim.x >> 6) + wave) * overflow_entries) * 64 + lane;
+    stk.lds_entries = (int)lds_levels;
+    PcFilm fm;
+    for (int i = 0; i < 9; ++i) fm.m[i] = fr.m[i];
+    fm.width = fr.width, fm.height = fr.height, fm.sensor_x = fr.sensor_x, fm.sensor_y = fr.sensor_y, fm.film_dist = fr.film_dist;
+    const uint32_t tiles_x = (fr.width + 7u) / 8u;
+    const uint32_t n = *count;
+    for (;;) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(head, 64u);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (base >= n) break;
+        if (base + lane < n) {
+            const uint32_t e = entries[base + lane], tile = e >> 6;
+            const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+            const uint32_t lp = (ty * 8u + ((e & 63u) >> 3)) * fr.width + tx * 8u + (e & 7u);
+            uint4 *rec = (uint4 *)lists + lp;
+            const uint4 parked = *rec;
+            uint32_t l[kListWords];
+            pc_pixel_list(fm, global_pixel(fr, lp), cam_inner, cam_tris, sc.root_ref, stk, (int)(lds_levels + overflow_entries),
+                          (int)parked.x, (int)parked.y, l);
+            *rec = make_uint4(l[0], l[1], l[2], l[3]);
+        }
+    }
 }
 
 // k_unclaimed_words — for a pass that fuses its claimed pixels: per 64 slots of the pass's pixel list, one word with the
@@ -3592,11 +3648,28 @@ int launch_walk_words(const unsigned int *active, uint32_t n_active, uint32_t n_
 }
 
 int launch_pixel_claims(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, unsigned int *claims, unsigned int *lists, unsigned int *n_claimed,
-                        LaunchCfg cfg, void *stream) {
+                        unsigned long long *pend_mask, unsigned int *pend_cnt, LaunchCfg cfg, void *stream) {
+    if (lists && (!pend_mask || !pend_cnt)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pixel_claims, dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, (hipStream_t)stream, sc, fr,
-                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, claims, lists, n_claimed, wk.lds_entries, wk.overflow_entries,
-                       wk.overflow_stack);
+                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, claims, lists, n_claimed, pend_mask, pend_cnt,
+                       wk.lds_entries, wk.overflow_entries, wk.overflow_stack);
     return launch_status();
+}
+
+int launch_pixel_lists(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, const unsigned int *entries, const unsigned int *count,
+                       unsigned int *head, unsigned int *lists, LaunchCfg cfg, void *stream) {
+    hipLaunchKernelGGL(k_pixel_lists, dim3(cfg.grid), dim3(cfg.block), cfg.lds_bytes, (hipStream_t)stream, sc, fr,
+                       (const float *)wk.cam_inner, (const float *)wk.cam_tris, entries, count, head, lists, wk.lds_entries,
+                       wk.overflow_entries, wk.overflow_stack);
+    return launch_status();
+}
+
+int query_pixel_claims_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks) {
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k_pixel_claims, (int)block, lds_bytes);
+}
+
+int query_pixel_lists_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks) {
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k_pixel_lists, (int)block, lds_bytes);
 }
 
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
