@@ -260,6 +260,17 @@ int vmx_scene_bind_texture(vmx_scene *scene, const float *data, uint32_t width, 
 int vmx_scene_describe(const vmx_scene *scene, vmx_scene_desc *out);
 int vmx_scene_timings(const vmx_scene *scene, vmx_timings *out);
 /*
+ * The number of compute units the scene sizes its launches for: the device's own count, or less under
+ * VMX_CU_LIMIT (0 for a NULL scene).  Two environment variables are read by the library, both diagnostic:
+ *   VMX_MEM_BUDGET_MB  lowers the memory a render's passes are sized for (read per render);
+ *   VMX_CU_LIMIT       read once when a scene is created: the scene counts min(device's units, limit) compute
+ *                      units, so its persistent grids, block-stride grids and the buffers sized from them are
+ *                      those of a smaller device.  It can only lower the count — unset, empty, 0, unparsable or
+ *                      at least the device's count leave the device's — and it changes no result: every kernel
+ *                      hands out its work on the device and none synchronises across blocks.
+ */
+uint32_t vmx_scene_compute_units(const vmx_scene *scene);
+/*
  * Host-side BVH topology in the reference's flat layout (bvh.h:11-14): per
  * node start, nPrims, rightOffset ([n_nodes] each, any may be NULL), bbox
  * [n_nodes*6] (min,max) and the final build_prims permutation [ntris].

@@ -294,6 +294,7 @@ SYMBOLS = {
     "vmx_scene_bind_texture": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vmx_scene_describe": (C.c_int, [_P, C.POINTER(SceneDesc)]),
     "vmx_scene_timings": (C.c_int, [_P, C.POINTER(Timings)]),
+    "vmx_scene_compute_units": (C.c_uint32, [_P]),
     "vmx_scene_bvh": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "vmx_scene_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
     "vmx_scene_update_device": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),

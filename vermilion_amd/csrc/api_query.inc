@@ -408,7 +408,7 @@ int vmx_radiance(const vmx_scene *csc, const float *origin, const float *dir, ui
             r = ab_radiance_enqueue(sc, fr, q, d_o.p, d_d.p, n, opts->seed, count, tn.tail_threshold, s, timed, launches, bb);
         } else {
             HIP_TRY(hipMemsetAsync(qi[0].counts, 0, kSubQueues * 32 * 4, s));
-            LAUNCH_TRY(launch_radiance_init_ids(d_o.p, d_d.p, n, opts->seed, pa, qi[0], s));
+            LAUNCH_TRY(launch_radiance_init_ids(d_o.p, d_d.p, n, opts->seed, pa, qi[0], (uint32_t)sc->num_cus, s));
             launches += 2;
             r = run_ids(sc, fr, pa, qi, 0, ws.counters.p, count, tn, s, timed, launches, tb, rb);
         }

@@ -134,11 +134,11 @@ int shade_two_phase(vmx_scene *sc, const FrameDev &fr, WorkDev wk, PixelStateDev
         HIP_TRY(hipMemsetAsync(cnt, 0, nwords * 4, s));
         HIP_TRY(hipMemsetAsync(ws.full_mask.p, 0, nwords * 8, s));
     }
-    LAUNCH_TRY(launch_shade_ends(sc->dev, fr, wk, pa, ws.full_mask.p, cnt, max_chunks, ctr, from_queue, s));
+    LAUNCH_TRY(launch_shade_ends(sc->dev, fr, wk, pa, ws.full_mask.p, cnt, max_chunks, ctr, from_queue, (uint32_t)sc->num_cus, s));
     HIP_TRY((hipError_t)launch_live_compact(ws.full_mask.p, cnt, (uint32_t)nwords, offs, q[2].ids, len, ws.full_tmp.p,
-                                            ws.full_tmp_bytes, s));
+                                            ws.full_tmp_bytes, (uint32_t)sc->num_cus, s));
     wk.flat_ids = q[2].ids, wk.flat_count = len;
-    LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qout, max_chunks, ctr, from_queue, s));
+    LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qout, max_chunks, ctr, from_queue, (uint32_t)sc->num_cus, s));
     return VMX_OK;
 }
 
@@ -221,7 +221,7 @@ int run_ids(vmx_scene *sc, const FrameDev &fr, PathArrays pa, IdQueue q[3], int 
         if (tn.two_phase && !tn.sorted && !tn.bounce_records) {
             if ((rc = shade_two_phase(sc, fr, wk, nopx, pa, q, q[cur ^ 1], max_chunks, (size_t)max_chunks * kSubQueues * 4, false, ctr, true, s))) return rc;
         } else {
-            LAUNCH_TRY(launch_shade(sc->dev, fr, wk, nopx, pa, q[cur ^ 1], max_chunks, ctr, true, s));
+            LAUNCH_TRY(launch_shade(sc->dev, fr, wk, nopx, pa, q[cur ^ 1], max_chunks, ctr, true, (uint32_t)sc->num_cus, s));
         }
         if ((rc = timed_end(timed, s))) return rc;
         launches += 4;
@@ -497,7 +497,7 @@ int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t n
         LAUNCH_TRY(launch_pixel_claims(sc->dev, fr, wk, ws.claims.p, ws.claim_lists.p, ws.claims.p + npix, ws.claim_pend_mask.p, cnt, cfg, s));
         HIP_TRY(hipMemsetAsync(len, 0, 8, s));  // (the list's length and the list kernel's work head)
         HIP_TRY((hipError_t)launch_live_compact(ws.claim_pend_mask.p, cnt, (uint32_t)tiles, offs, ws.claim_pend_ids.p, len,
-                                                ws.claim_pend_tmp.p, tmp_bytes, s));
+                                                ws.claim_pend_tmp.p, tmp_bytes, (uint32_t)sc->num_cus, s));
         LAUNCH_TRY(launch_pixel_lists(sc->dev, fr, wk, ws.claim_pend_ids.p, len, head, ws.claim_lists.p, lcfg, s));
     }
     return VMX_OK;
@@ -580,7 +580,7 @@ int render_bind(vmx_scene *sc, RenderJob &job, uint32_t run_samples) {
         if (ws.cam_inner.ensure(n_inner * 64 * 8 + (size_t)sc->ntris * 64))
             return fail(VMX_ERR_NOMEM, "hipMalloc failed for the camera tables");
         LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p,
-                                        ws.cam_inner.p + n_inner * 64 * 8, s));
+                                        ws.cam_inner.p + n_inner * 64 * 8, (uint32_t)sc->num_cus, s));
         job.launches++;
     }
     // the claims follow the camera tables: built with them for every run (the workspace is shared, and geometry may have
@@ -733,10 +733,10 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
             // order the waves finish, the traversal kernel's 8 image bands lose their XCDs' L2 locality, and
             // k_trace_w<0, LIVE> went 8.2 -> 15.9 ms (and the generation itself 4.2 -> 5.6 ms): the ORDERED list is worth its scan)
             wk.live_mask = ws.live_mask.p, wk.live_cnt = cnt;
-            LAUNCH_TRY(launch_raygen(sc->dev, fr, wk, px, pa, s));
-            HIP_TRY((hipError_t)launch_live_compact(ws.live_mask.p, cnt, nwords, offs, ws.live_ids.p, len, ws.live_tmp.p, job.live_tmp_bytes, s));
+            LAUNCH_TRY(launch_raygen(sc->dev, fr, wk, px, pa, (uint32_t)sc->num_cus, s));
+            HIP_TRY((hipError_t)launch_live_compact(ws.live_mask.p, cnt, nwords, offs, ws.live_ids.p, len, ws.live_tmp.p, job.live_tmp_bytes, (uint32_t)sc->num_cus, s));
             wk.live_ids = ws.live_ids.p, wk.live_count = len;
-            LAUNCH_TRY(launch_raygen_live(sc->dev, fr, wk, px, pa, s));
+            LAUNCH_TRY(launch_raygen_live(sc->dev, fr, wk, px, pa, (uint32_t)sc->num_cus, s));
             HIP_TRY(hipMemsetAsync(pa.rad_mask, 0, (size_t)nwords * 8, s));
         } else {
             if (fuse) {
@@ -747,9 +747,9 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
                 // and shades the rays itself.  Per pass: `active` shrinks between passes
                 const uint32_t nwords = n_pad / 64;
                 unsigned int *cnt = ws.unclaimed_u32.p, *offs = cnt + ws.unclaimed_words, *len = offs + ws.unclaimed_words;
-                LAUNCH_TRY(launch_unclaimed_words(act_cur, n_active, n_pad, job.claims, ws.unclaimed_mask.p, cnt, s));
+                LAUNCH_TRY(launch_unclaimed_words(act_cur, n_active, n_pad, job.claims, ws.unclaimed_mask.p, cnt, (uint32_t)sc->num_cus, s));
                 HIP_TRY((hipError_t)launch_slot_lists(ws.unclaimed_mask.p, cnt, nwords, n_active, offs, ws.unclaimed.p, ws.claimed_slots.p, len,
-                                                      ws.unclaimed_tmp.p, ws.unclaimed_tmp_bytes, s));
+                                                      ws.unclaimed_tmp.p, ws.unclaimed_tmp_bytes, (uint32_t)sc->num_cus, s));
                 wk.unclaimed = ws.unclaimed.p, wk.unclaimed_count = len;
                 launches += 3;  // (the scan counted as one launch, whatever hipcub makes of it)
             }
@@ -763,15 +763,15 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
                 const uint32_t nwords = n_pad / 64;
                 unsigned int *cnt = ws.walk_u32.p, *offs = cnt + ws.unclaimed_words;
                 walk_len = offs + ws.unclaimed_words;
-                LAUNCH_TRY(launch_walk_words(act_cur, n_active, n_pad, job.claims, job.claim_lists, ws.walk_mask.p, cnt, s));
+                LAUNCH_TRY(launch_walk_words(act_cur, n_active, n_pad, job.claims, job.claim_lists, ws.walk_mask.p, cnt, (uint32_t)sc->num_cus, s));
                 HIP_TRY((hipError_t)launch_live_compact(ws.walk_mask.p, cnt, nwords, offs, ws.walk_slots.p, walk_len, ws.unclaimed_tmp.p,
-                                                        ws.unclaimed_tmp_bytes, s));
+                                                        ws.unclaimed_tmp_bytes, (uint32_t)sc->num_cus, s));
                 HIP_TRY(hipMemsetAsync(qi[2].counts, 0, 4, s));
                 wr.qids.ids = qi[2].ids, wr.qids.counts = qi[2].counts;
                 wr.qids.sub_capacity = (uint32_t)std::min<uint64_t>((uint64_t)qi[2].sub_capacity * kSubQueues, 0xFFFFFFFFull);
                 launches += 2;
             }
-            LAUNCH_TRY(launch_raygen(sc->dev, fr, wr, px, pa, s));
+            LAUNCH_TRY(launch_raygen(sc->dev, fr, wr, px, pa, (uint32_t)sc->num_cus, s));
             if (rays_settle_lists) stragglers = wr.qids;
         }
         if (tn.sorted) {
@@ -801,12 +801,12 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
             if (fuse) {  // the unclaimed slots, then the claimed ones in the kernel's CLAIMED form
                 WorkDev wsh = wk;
                 wsh.shade_slots = wk.unclaimed, wsh.shade_count = wk.unclaimed_count;
-                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, s));
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, (uint32_t)sc->num_cus, s));
                 wsh.shade_slots = ws.claimed_slots.p, wsh.shade_count = wk.unclaimed_count + 1, wsh.fused = 1;
-                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, s));
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wsh, px, pa, qi[0], 0, ws.counters.p, false, (uint32_t)sc->num_cus, s));
                 launches++;
             } else {
-                LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qi[0], 0, ws.counters.p, false, s));
+                LAUNCH_TRY(launch_shade(sc->dev, fr, wk, px, pa, qi[0], 0, ws.counters.p, false, (uint32_t)sc->num_cus, s));
             }
         }
         if ((rc = timed_end(timed, s))) return rc;
@@ -1015,7 +1015,7 @@ static int pixel_claims_impl(const vmx_scene *csc, const vmx_camera *cam, const 
     if ((rc = sc->upd.done.wait(s))) return rc;
     const size_t n_inner = std::max<size_t>(sc->n_inner, 1);
     if (ws.cam_inner.ensure(n_inner * 64 * 8 + (size_t)sc->ntris * 64)) return fail(VMX_ERR_NOMEM, "hipMalloc failed for the camera tables");
-    LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p, ws.cam_inner.p + n_inner * 64 * 8, s));
+    LAUNCH_TRY(launch_camera_tables(sc->dev, sc->n_inner, fr.px, fr.py, fr.pz, ws.cam_inner.p, ws.cam_inner.p + n_inner * 64 * 8, (uint32_t)sc->num_cus, s));
     if ((rc = build_claims(sc, fr, make_tuning(sc, opts), npix, lists_out != nullptr, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (claims_out) HIP_TRY(hipMemcpy(claims_out, ws.claims.p, (size_t)npix * 4, hipMemcpyDeviceToHost));
@@ -1177,7 +1177,7 @@ static int guide_trace_impl(const vmx_scene *csc, const float *origin, const flo
         HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
         HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
         HIP_TRY(hipMemsetAsync(qi[0].counts, 0, kSubQueues * 32 * 4, s));
-        LAUNCH_TRY(launch_radiance_init_ids(d_o.p, d_d.p, n, opts->seed, pa, qi[0], s));
+        LAUNCH_TRY(launch_radiance_init_ids(d_o.p, d_d.p, n, opts->seed, pa, qi[0], (uint32_t)sc->num_cus, s));
         HIP_TRY(hipMemsetAsync(pa.hit, 0xFF, (size_t)n * 8, s));
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, kSubQueues * 32 * 4, s));
         if (records) HIP_TRY(hipMemsetAsync(ws.out_count.p, 0, 4, s));

@@ -45,7 +45,7 @@ static int progressive_compact(vmx_progressive *p, const unsigned int *src, uint
     const uint32_t nwords = (n + 63u) / 64u;
     unsigned int *cnt = p->list_u32.p, *offs = cnt + p->list_words, *len = offs + p->list_words;
     LAUNCH_TRY(launch_list_words(src, n, select, p->pixels.cursor.p, p->job.fr.kmax, p->list_mask.p, cnt, s));
-    HIP_TRY((hipError_t)launch_list_compact(p->list_mask.p, cnt, nwords, offs, src, dst, len, p->list_tmp.p, p->list_tmp_bytes, s));
+    HIP_TRY((hipError_t)launch_list_compact(p->list_mask.p, cnt, nwords, offs, src, dst, len, p->list_tmp.p, p->list_tmp_bytes, (uint32_t)p->sc->num_cus, s));
     unsigned int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, len, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -257,7 +257,7 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
         const uint32_t nwords = (n_master + 63u) / 64u;
         unsigned int *cnt = p->list_u32.p, *offs = cnt + p->list_words, *len = offs + p->list_words;
         LAUNCH_TRY(launch_list_words_budget(master, n_master, d_budget, p->pixels.cursor.p, job.fr.kmax, p->list_mask.p, cnt, s));
-        HIP_TRY((hipError_t)launch_list_compact(p->list_mask.p, cnt, nwords, offs, master, act, len, p->list_tmp.p, p->list_tmp_bytes, s));
+        HIP_TRY((hipError_t)launch_list_compact(p->list_mask.p, cnt, nwords, offs, master, act, len, p->list_tmp.p, p->list_tmp_bytes, (uint32_t)sc->num_cus, s));
         HIP_TRY((hipError_t)launch_item_base(act, len, n_master, d_budget, p->pixels.cursor.p, job.fr.kmax, job.smax, p->item_cnt.p,
                                              p->item_base.p, p->item_tmp.p, p->item_tmp_bytes, s));
         unsigned int h[2] = {0, 0};  // [0] the list's length, [1] the pass's items

@@ -202,6 +202,18 @@ static void derive_spheres(const std::vector<vmx_sphere> &table, SphereDev *sd, 
     }
 }
 
+// VMX_CU_LIMIT (diagnostic; include/vermilion_hip.h): the compute units a scene counts, min(the device's, the limit).
+// Lower-only: no kernel here synchronises across blocks, so a grid below the resident one is always safe (DESIGN.md §9),
+// while a count above the device's would size "resident" grids that are not.  Unset, empty, 0 or unparsable: the device's.
+static int limited_cus(int device_cus) {
+    const char *e = std::getenv("VMX_CU_LIMIT");
+    if (!e || !*e) return device_cus;
+    char *end = nullptr;
+    const unsigned long v = std::strtoul(e, &end, 10);
+    if (end == e || *end != '\0' || v == 0 || v >= (unsigned long)device_cus) return device_cus;
+    return (int)v;
+}
+
 // device half of scene creation: uploads sc->bvh / sc->spheres to sc->device (used for the first scene
 // and for the replicas of a multi-device scene, which share one host-side build)
 static int scene_upload(vmx_scene *sc) {
@@ -209,7 +221,7 @@ static int scene_upload(vmx_scene *sc) {
     HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
-    sc->num_cus = prop.multiProcessorCount;
+    sc->num_cus = limited_cus(prop.multiProcessorCount);
     HIP_TRY(hipStreamCreateWithFlags(&sc->stream.s, hipStreamNonBlocking));
 
     // room for the largest table from the start: vmx_scene_set_spheres rewrites it in place, whatever its count
@@ -409,6 +421,8 @@ int vmx_scene_timings(const vmx_scene *sc, vmx_timings *out) {
     *out = sc->timings;
     return VMX_OK;
 }
+
+uint32_t vmx_scene_compute_units(const vmx_scene *sc) { return sc ? (uint32_t)sc->num_cus : 0u; }
 
 int vmx_scene_bvh(const vmx_scene *sc, uint32_t *start, uint32_t *nprims, uint32_t *right_offset, float *bbox,
                   uint32_t *prim_order) {

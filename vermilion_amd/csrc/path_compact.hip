@@ -107,34 +107,34 @@ size_t live_compact_tmp_bytes(uint32_t nwords) {
 }
 
 int launch_live_compact(const unsigned long long *live_mask, const unsigned int *live_cnt, uint32_t nwords,
-                        unsigned int *offs, unsigned int *ids, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream) {
+                        unsigned int *offs, unsigned int *ids, unsigned int *count, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (nwords == 0) return (int)hipMemsetAsync(count, 0, 4, s);
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, live_cnt, offs, (int)nwords, s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
+    const uint32_t grid = strided_grid((nwords + 3) / 4, cus, 16);
     hipLaunchKernelGGL(k_live_scatter, dim3(grid), dim3(256), 0, s, live_mask, offs, nwords, ids, count);
     return (int)hipGetLastError();
 }
 
 int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, uint32_t n_active, unsigned int *offs,
-                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, void *stream) {
+                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (nwords == 0) return (int)hipMemsetAsync(counts, 0, 8, s);
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, offs, (int)nwords, s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
+    const uint32_t grid = strided_grid((nwords + 3) / 4, cus, 16);
     hipLaunchKernelGGL(k_slot_scatter, dim3(grid), dim3(256), 0, s, mask, offs, nwords, n_active, unclaimed, claimed, counts);
     return (int)hipGetLastError();
 }
 
 int launch_list_compact(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, unsigned int *offs,
-                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream) {
+                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (nwords == 0) return (int)hipMemsetAsync(count, 0, 4, s);
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, offs, (int)nwords, s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t grid = std::min<uint32_t>((nwords + 3) / 4, 256u * 16u);
+    const uint32_t grid = strided_grid((nwords + 3) / 4, cus, 16);
     hipLaunchKernelGGL(k_list_scatter, dim3(grid), dim3(256), 0, s, mask, offs, nwords, src, dst, count);
     return (int)hipGetLastError();
 }

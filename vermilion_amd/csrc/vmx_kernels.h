@@ -161,6 +161,14 @@ struct LaunchCfg {
     uint32_t lds_bytes;       // dynamic LDS = waves_per_block * stack_entries * 512
 };
 
+// The grid of a launch whose blocks stride over `blocks` blocks' worth of work: at most per_cu blocks for each of the
+// scene's compute units (cus = vmx_scene::num_cus, which VMX_CU_LIMIT lowers), at least one.  The launches below that
+// take `cus` were measured on 256 compute units, where these bounds are the literals they had: 256 * per_cu.
+inline uint32_t strided_grid(uint64_t blocks, uint32_t cus, uint32_t per_cu) {
+    const uint64_t cap = (uint64_t)(cus ? cus : 1u) * per_cu;
+    return (uint32_t)(blocks < cap ? (blocks ? blocks : 1u) : cap);
+}
+
 // ---- parity hooks -----------------------------------------------------------
 int launch_trace(const SceneDev &sc, const float *o, const float *d, uint32_t n, int32_t *tri_id,
                  float *t, DevCounters *counters, bool count, LaunchCfg cfg, void *stream);
@@ -228,7 +236,7 @@ int launch_paths(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
 int query_paths_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, int *blocks, bool guide = false);
 // split wavefront: persistent trace kernel (per-lane refill) ...
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
-                         void *cam_tris, void *stream);
+                         void *cam_tris, uint32_t cus, void *stream);
 // the per-pixel claims of a frame (pixel_claim.h) from the camera tables in wk: claims[local pixel], *n_claimed += the
 // pixels with a slot or a miss claim (n_claimed[1]: the kernel's work head, zeroed by the caller like the count; the grid
 // is persistent, query_pixel_claims_blocks_per_cu blocks per CU); lists (or NULL: none): the list records of the pixels without one; wk: cam_inner, cam_tris, lds_entries, overflow_entries, overflow_stack
@@ -243,18 +251,18 @@ int launch_pixel_lists(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk
                        unsigned int *head, unsigned int *lists, LaunchCfg cfg, void *stream);
 int query_pixel_claims_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks);
 int query_pixel_lists_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blocks);
-int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
-int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream);
+int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, uint32_t cus, void *stream);
+int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, uint32_t cus, void *stream);
 size_t live_compact_tmp_bytes(uint32_t nwords);
 int launch_live_compact(const unsigned long long *live_mask, const unsigned int *live_cnt, uint32_t nwords,
-                        unsigned int *offs, unsigned int *ids, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream);
+                        unsigned int *offs, unsigned int *ids, unsigned int *count, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream);
 // the ordered lists of the slots [0, n_active) whose pixel has no claim / a claim, for a pass that fuses its claimed
 // pixels: one word of "unclaimed" bits and its popcount per 64 slots (mask, cnt: n_pad / 64 words), then launch_slot_lists:
 // set bits -> unclaimed, the other slots below n_active -> claimed; counts[0], counts[1] = the lists' lengths
 int launch_slot_lists(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, uint32_t n_active, unsigned int *offs,
-                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, void *stream);
+                      unsigned int *unclaimed, unsigned int *claimed, unsigned int *counts, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream);
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
-                           unsigned long long *mask, unsigned int *cnt, void *stream);
+                           unsigned long long *mask, unsigned int *cnt, uint32_t cus, void *stream);
 // ... and, in a run with list claims, of the walk slots: the unclaimed slots whose pixel has no list either (lists: the
 // list records, kListWords words per local pixel).  One word of their bits and its popcount per 64 slots, then
 // launch_live_compact: the ordered list and its length.  k_trace_w<0> works on that list and on the straggler list that
@@ -262,7 +270,7 @@ int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32
 // unclaimed, claim_lists and qids.ids; launch_trace_q's kernel takes the stragglers as its last source when qids.ids is
 // set (nsrc = the bands + 1)
 int launch_walk_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
-                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, void *stream);
+                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, uint32_t cus, void *stream);
 int launch_trace_q(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
                    DevCounters *counters, bool count, bool from_queue, LaunchCfg cfg, void *stream, const GuideDev *guide = nullptr,
                    unsigned int *visits = nullptr);
@@ -273,14 +281,14 @@ int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, 
                                 bool guide = false);
 // ... and the wide shading kernel: RayCast tail + Radiance step + id compaction
 int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
-                 IdQueue qout, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream);
+                 IdQueue qout, uint32_t max_chunks, DevCounters *counters, bool from_queue, uint32_t cus, void *stream);
 int launch_shade_ends(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathArrays pa, unsigned long long *full_mask,
-                      unsigned int *full_cnt, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream);
+                      unsigned int *full_cnt, uint32_t max_chunks, DevCounters *counters, bool from_queue, uint32_t cus, void *stream);
 // follows every queued path (ids) to its end in one launch
 int launch_tail(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathArrays pa, DevCounters *counters,
                 bool count, LaunchCfg cfg, void *stream, const GuidePathsDev *guide = nullptr);
 int launch_radiance_init_ids(const float *o, const float *d, uint32_t n, uint64_t seed, PathArrays pa,
-                             IdQueue qout, void *stream);
+                             IdQueue qout, uint32_t cus, void *stream);
 int launch_resolve(const FrameDev &fr, const unsigned int *active, uint32_t n_active, uint32_t samples,
                    bool pixel_major, const void *rad, const unsigned long long *rad_mask, PixelStateDev px, unsigned int *next_active,
                    unsigned int *next_count, float *out_rgbaz, DevCounters *counters, void *stream, bool moments = false);
@@ -291,7 +299,7 @@ int launch_resolve(const FrameDev &fr, const unsigned int *active, uint32_t n_ac
 int launch_list_words(const unsigned int *list, uint32_t n, const unsigned char *select, const unsigned int *cursor, uint32_t kmax,
                       unsigned long long *mask, unsigned int *cnt, void *stream);
 int launch_list_compact(const unsigned long long *mask, const unsigned int *cnt, uint32_t nwords, unsigned int *offs,
-                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, void *stream);
+                        const unsigned int *src, unsigned int *dst, unsigned int *count, void *tmp, size_t tmp_bytes, uint32_t cus, void *stream);
 struct SamplingPass {
     uint32_t width, height;  // the handle's local image
     uint32_t kmax, min_samples, radius;

@@ -3618,19 +3618,17 @@ int launch_tail(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathA
 }
 
 int launch_camera_tables(const SceneDev &sc, uint32_t n_inner, float ox, float oy, float oz, void *cam_inner,
-                         void *cam_tris, void *stream) {
+                         void *cam_tris, uint32_t cus, void *stream) {
     const uint32_t total = n_inner + sc.ntris;
-    uint32_t grid = std::min<uint32_t>((total + 255) / 256, 4096);
-    if (grid == 0) grid = 1;
+    const uint32_t grid = strided_grid((total + 255) / 256, cus, 16);
     hipLaunchKernelGGL(k_camera_tables, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, n_inner, ox, oy, oz,
                        (float4 *)cam_inner, (float4 *)cam_tris);
     return launch_status();
 }
 
-int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream) {
+int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, uint32_t cus, void *stream) {
     const uint64_t total = (uint64_t)wk.samples * wk.n_pad;
-    uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256u * 32u);
-    if (grid == 0) grid = 1;
+    const uint32_t grid = strided_grid((total + 255) / 256, cus, 32);
     if (wk.live_mask) hipLaunchKernelGGL(k_raygen<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
     else if (wk.unclaimed && wk.claim_lists && wk.qids.ids) {
         // a fused pass of a run with list claims (render_pass): the form that settles the listed pixels' rays itself
@@ -3641,8 +3639,8 @@ int launch_raygen(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pix
 }
 
 int launch_walk_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
-                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, void *stream) {
-    const uint32_t grid = std::max(1u, std::min<uint32_t>((n_pad + 255) / 256, 4096u));
+                      const unsigned int *lists, unsigned long long *mask, unsigned int *cnt, uint32_t cus, void *stream) {
+    const uint32_t grid = strided_grid((n_pad + 255) / 256, cus, 16);
     hipLaunchKernelGGL(k_walk_words, dim3(grid), dim3(256), 0, (hipStream_t)stream, active, n_active, n_pad, claims, lists, mask, cnt);
     return launch_status();
 }
@@ -3673,17 +3671,16 @@ int query_pixel_lists_blocks_per_cu(uint32_t block, uint32_t lds_bytes, int *blo
 }
 
 int launch_unclaimed_words(const unsigned int *active, uint32_t n_active, uint32_t n_pad, const unsigned int *claims,
-                           unsigned long long *mask, unsigned int *cnt, void *stream) {
-    const uint32_t grid = std::max(1u, std::min<uint32_t>((n_pad + 255) / 256, 4096u));
+                           unsigned long long *mask, unsigned int *cnt, uint32_t cus, void *stream) {
+    const uint32_t grid = strided_grid((n_pad + 255) / 256, cus, 16);
     hipLaunchKernelGGL(k_unclaimed_words, dim3(grid), dim3(256), 0, (hipStream_t)stream, active, n_active, n_pad, claims, mask, cnt);
     return launch_status();
 }
 
-int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, void *stream) {
+int launch_raygen_live(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa, uint32_t cus, void *stream) {
     // the list's length is known on the device only: a grid for a third of the pass's paths, striding over the rest
     const uint64_t total = ((uint64_t)wk.samples * wk.n_pad + 2) / 3;
-    uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256u * 32u);
-    if (grid == 0) grid = 1;
+    const uint32_t grid = strided_grid((total + 255) / 256, cus, 32);
     hipLaunchKernelGGL(k_raygen_live, dim3(grid), dim3(256), 0, (hipStream_t)stream, sc, fr, wk, px, pa);
     return launch_status();
 }
@@ -3745,18 +3742,19 @@ int query_trace_q_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool count, 
 // from_queue: bounce paths (wk.qids), else the camera paths of the pass.  wk.flat_ids: the second phase after
 // launch_shade_ends + launch_live_compact — only the listed positions.
 int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, PathArrays pa,
-                 IdQueue qout, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream) {
+                 IdQueue qout, uint32_t max_chunks, DevCounters *counters, bool from_queue, uint32_t cus, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const bool flat = wk.flat_ids != nullptr || wk.out_rec != nullptr;  // a list whose length is known on the device only -> a full grid
     // 7 blocks per CU are resident (VMX_SHADE_WPS); more blocks only add end-of-block counter atomics, which a small pass
     // feels (early-stop frame, first pass: 1.70 ms with 4096 blocks, 1.05 with 1792; the bench frame's 530.8 M paths: no change)
-    constexpr uint32_t kShadeGrid = 256u * VMX_SHADE_WPS;
+    // (per compute unit of the scene: 256 * VMX_SHADE_WPS blocks on the device these figures are from)
+    const uint32_t shade_grid = std::max(cus, 1u) * VMX_SHADE_WPS;
     // (k_shade<0>'s dense form: a wave per pixel, four pixels per block and iteration)
     const bool dense = !from_queue && !flat && !wk.live_ids && wk.pixel_major && (wk.samples & 63u) == 0;
-    const uint64_t items = flat ? kShadeGrid
+    const uint64_t items = flat ? shade_grid
                                 : (from_queue ? (uint64_t)max_chunks * kSubQueues
                                               : (dense ? ((uint64_t)wk.n_pad + 3) / 4 : ((uint64_t)wk.samples * wk.n_pad + 255) / 256));
-    uint32_t grid = (uint32_t)std::min<uint64_t>(items, kShadeGrid);
+    uint32_t grid = (uint32_t)std::min<uint64_t>(items, shade_grid);
     if (grid == 0) grid = 1;
 #define VMX_GO(S, T, E, Q, D)                                                                                                    \
     do {  /* (wk.fused: the dense form's CLAIMED instantiation, over the pass's claimed slots) */                                \
@@ -3793,12 +3791,10 @@ int launch_shade(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, Pixe
 // first phase of the two-phase shading (k_shade_ends): finishes the steps that end by their draws alone, queues the
 // others' positions in full_mask / full_cnt (one word per wave of 64 positions) for launch_live_compact + launch_shade
 int launch_shade_ends(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PathArrays pa, unsigned long long *full_mask,
-                      unsigned int *full_cnt, uint32_t max_chunks, DevCounters *counters, bool from_queue, void *stream) {
+                      unsigned int *full_cnt, uint32_t max_chunks, DevCounters *counters, bool from_queue, uint32_t cus, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const uint64_t items = from_queue ? (uint64_t)max_chunks * kSubQueues : ((uint64_t)wk.samples * wk.n_pad + 255) / 256;
-    constexpr uint32_t kEndsGrid = 256u * 8u;  // 8 waves per SIMD resident; see launch_shade
-    uint32_t grid = (uint32_t)std::min<uint64_t>(items, kEndsGrid);
-    if (grid == 0) grid = 1;
+    const uint32_t grid = strided_grid(items, cus, 8);  // 8 waves per SIMD resident; see launch_shade
 #define VMX_GO(S, T, L) \
     hipLaunchKernelGGL((k_shade_ends<S, T, L>), dim3(grid), dim3(256), 0, s, sc, fr, wk, pa, full_mask, full_cnt, max_chunks, counters)
     if (from_queue) {
@@ -3816,9 +3812,8 @@ int launch_shade_ends(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk,
 }
 
 int launch_radiance_init_ids(const float *o, const float *d, uint32_t n, uint64_t seed, PathArrays pa, IdQueue qout,
-                             void *stream) {
-    uint32_t grid = (n + 255) / 256;
-    if (grid > 4096) grid = 4096;
+                             uint32_t cus, void *stream) {
+    const uint32_t grid = strided_grid(((uint64_t)n + 255) / 256, cus, 16);
     hipLaunchKernelGGL(k_radiance_init_ids, dim3(grid), dim3(256), 0, (hipStream_t)stream, o, d, n, seed, pa, qout);
     return launch_status();
 }

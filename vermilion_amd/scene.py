@@ -431,6 +431,11 @@ class Scene:
         self._check(self._lib.vmx_scene_timings(self._h, C.byref(t)))
         return t.as_dict()
 
+    @property
+    def compute_units(self):
+        """the compute units the scene sizes its launches for: the device's, or fewer under VMX_CU_LIMIT"""
+        return int(self._lib.vmx_scene_compute_units(self._h))
+
     def bvh(self):
         n = self.describe()["n_nodes"]
         start = np.zeros(n, np.uint32)
