@@ -4,9 +4,11 @@
 //
 //   g++ -std=c++17 -I include examples/render_cornell.cpp vermilion_amd/libvermilion_hip.so
 //       -Wl,-rpath,$PWD/vermilion_amd -o examples/render_cornell     (done by __graft_entry__.build())
-//   ./examples/render_cornell out.ppm 256 256 64 [seed] [--nee]
+//   ./examples/render_cornell out.ppm 256 256 64 [seed] [--nee [--panel]]
 // --nee: the light-sampling integrator (vmx_render_nee: VMX_SAMPLING_CORRECTED, every diffuse step samples the emitters)
 // instead of PathTracer::Render.
+// --panel (with --nee): a ceiling quad is added and its two triangles are named as emitters (vmx_scene_set_emitters): the
+// reference's meshes carry no emission, so the host says which triangles light the scene.
 //
 // Writes a binary PPM the way Camera::saveFrame quantises (floor(x*255), core/camera/camera.cpp:150-170)
 // and prints the statistics the reference cannot report (camera.h:101-102 are never incremented).
@@ -37,13 +39,18 @@ void quad(std::vector<float> &pos, std::vector<float> &nrm, std::vector<float> &
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool nee = false;
+    bool nee = false, panel = false;
     int kept = 1;
-    for (int i = 1; i < argc; ++i) {  // --nee may stand anywhere: the positional arguments close up
+    for (int i = 1; i < argc; ++i) {  // the flags may stand anywhere: the positional arguments close up
         if (std::strcmp(argv[i], "--nee") == 0) nee = true;
+        else if (std::strcmp(argv[i], "--panel") == 0) panel = true;
         else argv[kept++] = argv[i];
     }
     argc = kept;
+    if (panel && !nee) {
+        std::fprintf(stderr, "--panel needs --nee: only the light-sampling integrator sees emissive triangles\n");
+        return 1;
+    }
     const char *out = argc > 1 ? argv[1] : "cornell.ppm";
     const uint32_t W = argc > 2 ? (uint32_t)std::atoi(argv[2]) : 256, H = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 256;
     const uint32_t spp = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 64;
@@ -59,11 +66,27 @@ int main(int argc, char **argv) {
     quad(pos, nrm, uv, k0, k1, k2, k3, front);
     const float t0[3] = {-250, 400, 0}, t1[3] = {150, 400, 0}, t2[3] = {150, 400, -400}, t3[3] = {-250, 400, -400};
     quad(pos, nrm, uv, t0, t1, t2, t3, up);
+    const uint32_t panel_first = (uint32_t)(pos.size() / 9);  // createBVH-order ids of the panel's two triangles
+    if (panel) {
+        const float down[3] = {0, -1, 0};
+        const float p0[3] = {-300, 880, 300}, p1[3] = {300, 880, 300}, p2[3] = {300, 880, -300}, p3[3] = {-300, 880, -300};
+        quad(pos, nrm, uv, p0, p1, p2, p3, down);
+    }
 
     vmx_scene *scene = nullptr;
     if (vmx_scene_create(pos.data(), nrm.data(), uv.data(), (uint32_t)(pos.size() / 9), nullptr, 0, 4, 0, &scene) != VMX_OK) {
         std::fprintf(stderr, "scene: %s\n", vmx_last_error());
         return 1;
+    }
+    if (panel) {
+        const vmx_emitter lights[2] = {{panel_first, {6.f, 5.f, 4.f}}, {panel_first + 1, {6.f, 5.f, 4.f}}};
+        vmx_emitter_info info[2];
+        uint32_t n = 0;
+        if (vmx_scene_set_emitters(scene, lights, 2) != VMX_OK || vmx_scene_emitters(scene, info, 2, &n) != VMX_OK) {
+            std::fprintf(stderr, "emitters: %s\n", vmx_last_error());
+            return 1;
+        }
+        std::printf("panel: %u emissive triangles, area %.0f + %.0f\n", n, info[0].area, info[1].area);
     }
     vmx_camera cam;
     std::memset(&cam, 0, sizeof(cam));

@@ -1315,6 +1315,66 @@ int vmx_multi_render_nee_device(vmx_multi *m, const vmx_camera *cam, const vmx_o
 int vmx_radiance_nee_device(const vmx_scene *scene, const void *d_origin, const void *d_dir, uint32_t n, const vmx_opts *opts,
                             void *d_out4, vmx_stats *stats, void *stream);
 
+/* ---- light sampling: emissive triangles as area lights -----------------------------------------------------------------
+ * A per-scene table names triangles (by their createBVH-order id) that emit, each with a radiance; both faces emit.  The
+ * table means something to the LIGHT-SAMPLED integrator only (vmx_render_nee*, vmx_radiance_nee*, light-sampled
+ * progressive handles, the rank entries and vmx_multi_render_nee*).  vmx_render*, BruteForceTracer, the queries,
+ * vmx_raycast*, the albedo plane and the image-space chain see ordinary unlit triangles, exactly as before.  A scene
+ * without a table is, bit for bit and instruction for instruction, the scene it was before this section existed.
+ *
+ * vmx_scene_set_emitters replaces the table (NULL, 0 clears it).  VMX_ERR_INVALID, in this order and before any device
+ * work: a NULL scene; NULL with n > 0; n > VMX_MAX_EMITTERS or n > the scene's triangle count; an id >= that count; a
+ * repeated id; a radiance component that is negative or not finite.  vmx_emitters_check runs the checks after the
+ * scene's against a triangle count alone (what a host can validate before it has a scene).  The call takes the scene's
+ * lock and moves its generation on as vmx_scene_set_spheres does: progressive handles begun before it refuse further
+ * steps.  vmx_multi_set_emitters does the same on every replica.
+ * vmx_scene_emitters reads the DERIVED table back: *n = the table's length, out[0 .. min(cap, *n)) filled.
+ *
+ * Definition, in addition to the numbered definition of light sampling above; tests/nee_mesh_spec.py restates it and the
+ * kernel matches it bit for bit.
+ *   E1. Override.  For every RayCast the integrator makes (path rays, cone shadow rays, area shadow rays): if the returned
+ *       hit is the BVH's triangle (tri_id >= 0 and distance == tri_t: no sphere came nearer; the material bit stays set
+ *       behind a sphere and cannot be used) and that triangle is emitter e, hitColour = radiance_e.  hitColour is
+ *       necessarily black there, so no sphere colour is lost.  Steps 2 and 3 then apply unchanged.
+ *   E2. Derived table, in the caller's order, all in DOUBLE from the triangle record's float32 v0, e1 = v1 - v0,
+ *       e2 = v2 - v0 widened:  Nraw = cross(E1, E2) (each component a*b - c*d, two roundings and one subtraction),
+ *       nn = (Nx^2 + Ny^2) + Nz^2,  area = 0.5 sqrt(nn),  N = Nraw / sqrt(nn) per component,
+ *       weight = area * double(luminance(radiance)) with the float32 luminance (0.2126 r + 0.7152 g) + 0.0722 b,
+ *       cdf_e = cdf_{e-1} + weight_e sequentially from 0,  W = cdf_{n-1}.
+ *   E3. The table is derived from the scene's CURRENT records: after any sequence of vmx_scene_update* (refit: the areas
+ *       change; rebuild: the leaf slots permute) and builders, the table and every frame equal those of a fresh scene on
+ *       the same arrays.  (It is rebuilt at the next light-sampled launch or vmx_scene_emitters, keyed by the generation.)
+ *   E4. Sampling: in the emitter loop of a diffuse arm, after the last sphere emitter; skipped (no draw) when the point is
+ *       inside an emitter sphere, by rule 6, or when W == 0.  Three draws xi0, xi1, xi2, always consumed.
+ *         u = xi0 W;  e = the smallest index with cdf_e > u, clamped to n - 1;  p_e = weight_e / W.
+ *         In DOUBLE:  s = sqrt(xi1), b1 = s (1 - xi2), b2 = s xi2,  y = (V0 + b1 E1) + b2 E2,  d = y - X (X = x widened),
+ *         d2 = (dx^2 + dy^2) + dz^2,  omega_d = d * (1 / sqrt(d2)),  omega = float(omega_d) per component (not renormalised),
+ *         cosl = |(Nx ox + Ny oy) + Nz oz| with o = omega_d,  dw = dot(w, omega) in float32,
+ *         pdf = (p_e d2) / (area_e cosl),  wt = float((double(dw) / pi) / pdf).
+ *       Dropped, with no ray: weight_e == 0, d2 == 0, cosl == 0, dw <= 0, wt not finite, the step's own hit was emitter
+ *       e's triangle (E1's condition), or omega lies in the cone of ANY emitter sphere j: 0.5 double(|omega - a_j|^2)
+ *       <= q_j (the spheres own their cones).  Otherwise RayCast(x, omega), and accumColour.rgb += (accumRadiance.rgb *
+ *       hitColour) * wt only if the returned hit is emitter e's triangle.  lit is set as the sphere loop sets it.
+ *       vmx_stats.rays_secondary counts the area shadow rays traced with the others.
+ * Out of scope: one-sided emitters, textured emission, a mode that leaves triangles unsampled, more than one area sample
+ * per step, emission in vmx_render / BruteForceTracer, MIS. */
+#define VMX_MAX_EMITTERS 65536u
+typedef struct vmx_emitter {
+    uint32_t tri_id; /* createBVH-order id */
+    float radiance[3];
+} vmx_emitter;
+typedef struct vmx_emitter_info {
+    uint32_t tri_id;
+    float radiance[3];
+    double area;
+    double weight;
+    double cdf;
+} vmx_emitter_info;
+int vmx_scene_set_emitters(vmx_scene *scene, const vmx_emitter *emitters, uint32_t n);
+int vmx_scene_emitters(const vmx_scene *scene, vmx_emitter_info *out, uint32_t cap, uint32_t *n);
+int vmx_multi_set_emitters(vmx_multi *m, const vmx_emitter *emitters, uint32_t n);
+int vmx_emitters_check(const vmx_emitter *emitters, uint32_t n, uint32_t ntris);
+
 /* ---- frame output (the step after the path; replaces the conversion loop of
  * Camera::saveFrame, core/camera/camera.cpp:140-175, for the default RGBAZ mode) ------------ */
 /*

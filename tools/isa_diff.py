@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two builds of libvermilion_hip.so, instruction stream by instruction stream.
 
-    python tools/isa_diff.py OLD.so NEW.so [--show KERNEL_SUBSTRING]
+    python tools/isa_diff.py OLD.so NEW.so [--show KERNEL_SUBSTRING] [--rename REGEX REPL]...
 
 Every code object in the libraries' offload bundles is disassembled (llvm-objdump -d --no-show-raw-insn), the listing is
 split per kernel symbol, addresses and branch-target comments are dropped, and kernels of the same name are compared.
@@ -59,6 +59,9 @@ def kernels(blob):
             ins = re.sub(r"<[^>]*\+0x[0-9a-f]+>", "<>", ins)  # branch targets by symbol + offset
             if ins != "...":  # (objdump's mark for the zero padding between two symbols)
                 body[name].append(ins)
+    for lines in body.values():  # (the s_nop padding up to the next symbol's alignment is not the kernel's)
+        while lines and lines[-1].startswith("s_nop"):
+            lines.pop()
     meta = {}
     for chunk in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
         m = re.search(r"\.name:\s+(\S+)", chunk)
@@ -79,8 +82,22 @@ def library(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old"), ap.add_argument("new"), ap.add_argument("--show", default=None)
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"),
+                    help="re.sub applied to the kernel symbols of BOTH libraries before they are matched: compares a kernel "
+                         "with its successor under another mangled name (a template or an argument was added)")
     a = ap.parse_args()
     (ob, _), (nb, nm) = library(a.old), library(a.new)
+
+    def renamed(d):
+        out = {}
+        for k, v in d.items():
+            for rx, repl in a.rename:
+                k = re.sub(rx, repl, k)
+            assert k not in out, "two symbols are renamed to " + k
+            out[k] = v
+        return out
+
+    ob, nb, nm = renamed(ob), renamed(nb), renamed(nm)
     same = differ = 0
     for k in sorted(set(ob) & set(nb)):
         if ob[k] == nb[k]:

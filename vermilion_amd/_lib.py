@@ -41,6 +41,7 @@ VMX_SIGMA_LUMINANCE_DEFAULT = 4.0
 VMX_ADAPTIVE_EPS = 1e-10  # the adaptive accumulation's floor of the window mean's squared standard error
 VMX_UPDATE_REFIT = 0
 VMX_UPDATE_REBUILD = 1
+VMX_MAX_EMITTERS = 65536
 
 
 class Sphere(C.Structure):
@@ -52,6 +53,15 @@ class Sphere(C.Structure):
         ("normal_centre", C.c_float * 3),
         ("normal_sign", C.c_float),
     ]
+
+
+class Emitter(C.Structure):
+    _fields_ = [("tri_id", C.c_uint32), ("radiance", C.c_float * 3)]
+
+
+class EmitterInfo(C.Structure):
+    _fields_ = [("tri_id", C.c_uint32), ("radiance", C.c_float * 3), ("area", C.c_double), ("weight", C.c_double),
+                ("cdf", C.c_double)]
 
 
 class CameraDesc(C.Structure):
@@ -397,6 +407,10 @@ SYMBOLS = {
     "vmx_multi_bind_texture": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vmx_multi_update": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32]),
     "vmx_multi_set_spheres": (C.c_int, [_P, _P, C.c_uint32]),
+    "vmx_scene_set_emitters": (C.c_int, [_P, _P, C.c_uint32]),
+    "vmx_scene_emitters": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "vmx_multi_set_emitters": (C.c_int, [_P, _P, C.c_uint32]),
+    "vmx_emitters_check": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "vmx_multi_render": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_device": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), _P, C.POINTER(Stats)]),
     "vmx_multi_render_bruteforce": (C.c_int, [_P, C.POINTER(CameraDesc), C.POINTER(Opts), C.c_uint32, _P,

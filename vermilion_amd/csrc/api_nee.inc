@@ -99,7 +99,7 @@ int radiance_nee_run(vmx_scene *sc, const float *d_o, const float *d_d, uint32_t
     std::memset(&wk, 0, sizeof(wk));
     wk.heads = ws.heads.p;
     LaunchCfg cfg;
-    if ((rc = nee_launch_cfg(sc, tn, n, true, wk, cfg))) return rc;
+    if ((rc = nee_launch_cfg(sc, s, tn, n, true, wk, cfg))) return rc;
     ws.events.reset();
     std::vector<TimedLaunch> timed;
     hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
@@ -110,7 +110,7 @@ int radiance_nee_run(vmx_scene *sc, const float *d_o, const float *d_d, uint32_t
     if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
     HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
     if ((rc = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return rc;
-    LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o, d_d, n, d_out4, ws.counters.p, cfg, s));
+    LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o, d_d, n, d_out4, ws.counters.p, cfg, s, sc->em.dev));
     if ((rc = timed_end(timed, s))) return rc;
     HIP_TRY(hipEventRecord(ev1, s));
     rc = finish_stats(sc, s, timed, ev0, ev1, stats, 1, 1, t0);

@@ -503,10 +503,38 @@ int build_claims(vmx_scene *sc, const FrameDev &fr, const Tuning &tn, uint32_t n
     return VMX_OK;
 }
 
-// the stack and the persistent grid of a k_nee launch over `items` work items
-int nee_launch_cfg(vmx_scene *sc, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg, bool budgeted = false) {
+// The derived table of the scene's emissive triangles (vmx_scene_set_emitters), current for a launch on `s`: rebuilt from
+// the records the scene holds NOW when the generation moved since it was derived — an update rewrote or permuted them,
+// a new table came — and then fenced, since the next launch may run on another stream.  sc->em.dev.n == 0: no table.
+int nee_emitters(vmx_scene *sc, hipStream_t s) {
+    auto &em = sc->em;
+    const uint32_t n = (uint32_t)em.table.size();
+    if (n == 0) {
+        em.dev = EmitDev{};
+        return VMX_OK;
+    }
+    if (em.built != sc->generation) {
+        if (int rc = sc->upd.done.wait(s)) return rc;
+        if (em.rec.ensure(n) || em.area.ensure(n) || em.weight.ensure(n) || em.cdf.ensure(n) || em.slot_em.ensure(sc->ntris) ||
+            em.id_em.ensure(sc->ntris))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the emitter table");
+        em.dev = EmitDev{em.rec.p, em.area.p, em.weight.p, em.cdf.p, em.slot_em.p, n};
+        LAUNCH_TRY(launch_emitter_table(sc->dev.tris, sc->ntris, em.ids.p, em.radiance.p, em.id_em.p, em.dev, s));
+        if (int rc = em.done.record(s)) return rc;
+        em.built = sc->generation;
+        em.builds++;
+    }
+    return em.done.wait(s);
+}
+
+// the stack and the persistent grid of a k_nee launch over `items` work items on `s`; the scene's emitter table is made
+// current first (sc->em.dev is what launch_nee then takes)
+int nee_launch_cfg(vmx_scene *sc, hipStream_t s, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg,
+                   bool budgeted = false) {
+    if (int rc = nee_emitters(sc, s)) return rc;
     int blocks = 0;
-    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks, budgeted));
+    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks, budgeted,
+                                                sc->em.dev.n != 0));
     if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
     cfg = paths_cfg(sc, tn.lds_entries, items, blocks);
     return bind_stack(sc, tn, tn.lds_entries, cfg.grid, items, wk);
@@ -702,10 +730,10 @@ int render_pass(vmx_scene *sc, RenderJob &job, uint32_t cap, uint32_t *taken) {
     if (job.nee) {  // light sampling: one persistent launch, one work counter
         const uint64_t items = (uint64_t)n_pad * S;
         LaunchCfg cfg;
-        if ((rc = nee_launch_cfg(sc, tn, items, false, wk, cfg))) return rc;
+        if ((rc = nee_launch_cfg(sc, s, tn, items, false, wk, cfg))) return rc;
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
         if ((rc = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return rc;
-        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, px, nullptr, nullptr, (uint32_t)items, ws.rad.p, ws.counters.p, cfg, s));
+        LAUNCH_TRY(launch_nee(sc->dev, fr, wk, px, nullptr, nullptr, (uint32_t)items, ws.rad.p, ws.counters.p, cfg, s, sc->em.dev));
         if ((rc = timed_end(timed, s))) return rc;
         launches++;
     } else if (split) {

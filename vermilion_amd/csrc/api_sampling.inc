@@ -288,10 +288,10 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
         wk.pixel_major = 1;
         wk.flat_ids = p->item_base.p;
         LaunchCfg cfg;
-        if (int rc = nee_launch_cfg(sc, job.tn, items, false, wk, cfg, true)) return rc;
+        if (int rc = nee_launch_cfg(sc, s, job.tn, items, false, wk, cfg, true)) return rc;
         HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
         if (int rc = timed_begin(ws, job.timed, s, 0, VMX_K_OTHER)) return rc;
-        LAUNCH_TRY(launch_nee(sc->dev, job.fr, wk, job.px, nullptr, nullptr, items, ws.rad.p, ws.counters.p, cfg, s));
+        LAUNCH_TRY(launch_nee(sc->dev, job.fr, wk, job.px, nullptr, nullptr, items, ws.rad.p, ws.counters.p, cfg, s, sc->em.dev));
         if (int rc = timed_end(job.timed, s)) return rc;
         HIP_TRY(hipMemsetAsync(ws.next_count.p, 0, 8, s));
         if (int rc = timed_begin(ws, job.timed, s, -1, VMX_K_RESOLVE)) return rc;

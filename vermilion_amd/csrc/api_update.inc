@@ -245,9 +245,126 @@ int set_spheres(vmx_scene *sc, const std::vector<vmx_sphere> &table) {
     return VMX_OK;
 }
 
+// ---- the emissive triangles of a live scene (vmx_scene_set_emitters, vmx_multi_set_emitters) ----------------------------
+// argument checks that need no device, in the documented order (ntris: the handle's triangle count)
+int set_emitters_args(const vmx_emitter *e, uint32_t n, uint32_t ntris) {
+    if (!e && n > 0) return fail(VMX_ERR_INVALID, "NULL emitters with n > 0");
+    if (n > VMX_MAX_EMITTERS) return fail(VMX_ERR_INVALID, "more than VMX_MAX_EMITTERS emitters");
+    if (n > ntris) return fail(VMX_ERR_INVALID, "more emitters than the scene has triangles");
+    for (uint32_t i = 0; i < n; ++i)
+        if (e[i].tri_id >= ntris)
+            return fail(VMX_ERR_INVALID, "emitter " + std::to_string(i) + ": triangle id " + std::to_string(e[i].tri_id) +
+                                             " is not below the scene's triangle count " + std::to_string(ntris));
+    {
+        std::vector<uint32_t> ids(n);
+        for (uint32_t i = 0; i < n; ++i) ids[i] = e[i].tri_id;
+        std::sort(ids.begin(), ids.end());
+        const auto dup = std::adjacent_find(ids.begin(), ids.end());
+        if (dup != ids.end()) return fail(VMX_ERR_INVALID, "triangle id " + std::to_string(*dup) + " is listed more than once");
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(e[i].radiance[c]) || e[i].radiance[c] < 0.f)
+                return fail(VMX_ERR_INVALID, "emitter " + std::to_string(i) + ": a radiance component is negative or not finite");
+    return VMX_OK;
+}
+
+// The caller's table goes to the device and the generation moves on, under the scene's lock; the derived table follows at
+// the next light-sampled launch (nee_emitters).  Nothing is still reading: see set_spheres.  A failed call leaves the
+// scene as it was.
+int set_emitters(vmx_scene *sc, const std::vector<vmx_emitter> &table) {
+    auto &em = sc->em;
+    const size_t n = table.size();
+    if (n) {
+        if (int rc = bind_device(sc)) return rc;
+        hipStream_t s = sc->stream;
+        std::vector<uint32_t> ids(n);
+        std::vector<float> rad(n * 3);
+        for (size_t i = 0; i < n; ++i) {
+            ids[i] = table[i].tri_id;
+            for (int c = 0; c < 3; ++c) rad[i * 3 + c] = table[i].radiance[c];
+        }
+        if (int rc = update_wait(sc, s)) return rc;
+        HIP_TRY(hipStreamSynchronize(s));  // (ensure may free what the last launch read)
+        if (em.ids.ensure(n) || em.radiance.ensure(n * 3)) {
+            em.table.clear(), em.dev = EmitDev{};
+            sc->generation++;
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the emitter table (the scene now has none)");
+        }
+        HIP_TRY(hipMemcpy(em.ids.p, ids.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(em.radiance.p, rad.data(), n * 12, hipMemcpyHostToDevice));
+    }
+    em.table = table;
+    em.built = ~0ull;
+    if (n == 0) em.dev = EmitDev{};
+    sc->generation++;
+    return VMX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vmx_scene_set_emitters(vmx_scene *sc, const vmx_emitter *emitters, uint32_t n) {
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    if (int rc = set_emitters_args(emitters, n, sc->ntris)) return rc;
+    const std::vector<vmx_emitter> table(emitters, emitters + n);
+    std::lock_guard<std::mutex> lock(sc->mu);
+    return set_emitters(sc, table);
+}
+
+int vmx_emitters_check(const vmx_emitter *emitters, uint32_t n, uint32_t ntris) { return set_emitters_args(emitters, n, ntris); }
+
+int vmx_scene_emitters(const vmx_scene *csc, vmx_emitter_info *out, uint32_t cap, uint32_t *n_out) {
+    vmx_scene *sc = const_cast<vmx_scene *>(csc);
+    if (!sc) return fail(VMX_ERR_INVALID, "NULL scene");
+    if (!n_out) return fail(VMX_ERR_INVALID, "NULL n");
+    if (!out && cap > 0) return fail(VMX_ERR_INVALID, "NULL out with cap > 0");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    const uint32_t n = (uint32_t)sc->em.table.size();
+    *n_out = n;
+    const uint32_t m = std::min(n, cap);
+    if (m == 0) return VMX_OK;
+    if (int rc = bind_device(sc)) return rc;
+    hipStream_t s = sc->stream;
+    if (int rc = nee_emitters(sc, s)) return rc;
+    std::vector<double> area(m), weight(m), cdf(m);
+    HIP_TRY(hipMemcpyAsync(area.data(), sc->em.area.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(weight.data(), sc->em.weight.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cdf.data(), sc->em.cdf.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < m; ++i) {
+        out[i].tri_id = sc->em.table[i].tri_id;
+        for (int c = 0; c < 3; ++c) out[i].radiance[c] = sc->em.table[i].radiance[c];
+        out[i].area = area[i], out[i].weight = weight[i], out[i].cdf = cdf[i];
+    }
+    return VMX_OK;
+}
+
+int vmx_multi_set_emitters(vmx_multi *m, const vmx_emitter *emitters, uint32_t n) {
+    if (!m) return fail(VMX_ERR_INVALID, "NULL vmx_multi");
+    if (int rc = set_emitters_args(emitters, n, m->replica[0]->ntris)) return rc;
+    const std::vector<vmx_emitter> table(emitters, emitters + n);
+    std::lock_guard<std::mutex> mlock(m->mu);
+    // replica by replica, as vmx_multi_set_spheres: the replicas already changed get the old table back on a failure
+    const std::vector<vmx_emitter> old = m->replica[0]->em.table;
+    for (size_t r = 0; r < m->replica.size(); ++r) {
+        vmx_scene *sc = m->replica[r];
+        int rc;
+        {
+            std::lock_guard<std::mutex> lock(sc->mu);
+            rc = set_emitters(sc, table);
+        }
+        if (rc == VMX_OK) continue;
+        const std::string keep = r ? "device " + std::to_string(sc->device) + ": " + g_err : g_err;
+        for (size_t q = 0; q < r; ++q) {
+            std::lock_guard<std::mutex> lock(m->replica[q]->mu);
+            (void)set_emitters(m->replica[q], old);
+        }
+        return fail(rc, keep);
+    }
+    return VMX_OK;
+}
 
 int vmx_scene_set_spheres(vmx_scene *sc, const vmx_sphere *spheres, uint32_t nspheres) {
     if (int rc = set_spheres_args(sc, spheres, nspheres, "NULL scene")) return rc;

@@ -52,4 +52,4 @@ using namespace vmx;
 #include "api_progressive.inc" // vmx_progressive_*
 #include "api_sampling.inc"    // adaptive sampling: vmx_progressive_state / step_selected / error / select / step_adaptive, vmx_sampling_default_params
 #include "api_multi.inc"       // vmx_multi_*, vmx_assemble_device, vmx_quantize_device
-#include "api_update.inc"      // vmx_scene_update*, vmx_multi_update, vmx_scene_set_spheres, vmx_multi_set_spheres
+#include "api_update.inc"      // vmx_scene_update*, vmx_multi_update, vmx_scene_set_spheres, vmx_multi_set_spheres, vmx_scene_set_emitters, vmx_scene_emitters

@@ -267,6 +267,21 @@ struct vmx_scene {
     // it refuses further steps (its tuning and stack sizing came from the tree it saw); the scene outlives its handles
     uint64_t generation = 0;
     uint32_t progressive_open = 0;
+    // emissive triangles (vmx_scene_set_emitters): the caller's table on the host and on the device, and the table derived
+    // from it and the scene's records (vmx_emitters.inc) — made at the next light-sampled launch after the generation
+    // moved (nee_emitters), so every update and every builder is covered without a hook of its own
+    struct VMX_OPAQUE Emitters {
+        std::vector<vmx_emitter> table;  // empty: the scene has no table
+        DevBuf<uint32_t> ids;
+        DevBuf<float> radiance;
+        DevBuf<EmitRecord> rec;
+        DevBuf<double> area, weight, cdf;
+        DevBuf<int32_t> slot_em, id_em;
+        Fence done;              // recorded after each derivation
+        uint64_t built = ~0ull;  // the generation the derived table belongs to
+        uint64_t builds = 0;     // derivations so far
+        EmitDev dev{};           // what launch_nee takes (n == 0: no table)
+    } em;
     ~vmx_scene() { lbvh_release(lbvh); }
 };
 

@@ -434,12 +434,29 @@ int launch_motion_spheres(const void *rayhit, uint32_t n, const SphereMotionDev 
 // (its first counter, zeroed before the launch), reserve and the stack fields; camera paths (o == NULL): active, n_active,
 // samples, div_samples, and `items` = padded slots * samples path ids, numbered pixel-major as k_resolve reads `rad`;
 // explicit rays (o, d): ray i on stream (fr.seed, i, 0), `items` of them, rad[i] its accumColour
+// ed: the scene's emissive triangles (n == 0: none — the MESH = false instantiations, which never read it)
+struct EmitRecord {  // what one area sample reads of its emitter: 64 bytes, one per emitter in the caller's order
+    float v0[3], e1[3], e2[3];  // the triangle record's
+    float rad[3];
+    uint32_t slot;  // its leaf slot in the current tree
+    uint32_t pad[3];
+};
+static_assert(sizeof(EmitRecord) == 64, "emitter record must be 64 bytes");
+struct EmitDev {
+    const EmitRecord *rec;
+    const double *area, *weight, *cdf;  // [n]; cdf[n - 1] = W
+    const int32_t *slot_em;             // [ntris] leaf slot -> emitter index, -1: not an emitter
+    uint32_t n;
+};
 int launch_nee(const SceneDev &sc, const FrameDev &fr, const WorkDev &wk, PixelStateDev px, const float *o, const float *d,
-               uint32_t items, void *rad, DevCounters *counters, LaunchCfg cfg, void *stream);
+               uint32_t items, void *rad, DevCounters *counters, LaunchCfg cfg, void *stream, const EmitDev &ed);
+// the derived table (vmx_emitters.inc): k_emitter_slots, k_emitter_table, k_emitter_cdf from the scene's current records
+int launch_emitter_table(const void *tris, uint32_t ntris, const uint32_t *ids, const float *radiance, int32_t *id_em,
+                         const EmitDev &ed, void *stream);
 // a budgeted step of a light-sampled progressive handle (o == NULL, wk.flat_ids != NULL): k_nee's third work source.
 // wk.active / n_active: the step's pixel list; wk.flat_ids: the exclusive scan of the pixels' sample counts, n_active + 1
 // entries, every count >= 1; `items` = its last entry; item i is sample i - base[s] of slot s, rad[i] its accumColour
-int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks, bool budgeted = false);
+int query_nee_blocks_per_cu(uint32_t block, uint32_t lds_bytes, bool rays, int *blocks, bool budgeted = false, bool mesh = false);
 // ... and its fold: k_resolve's statements over rad[base[s] + j], j < base[s + 1] - base[s], per slot s in order
 int launch_resolve_budget(const FrameDev &fr, const unsigned int *active, uint32_t n_active, const unsigned int *base, const void *rad,
                           PixelStateDev px, unsigned int *next_active, unsigned int *next_count, float *out_rgbaz, DevCounters *counters,

@@ -3909,6 +3909,8 @@ int launch_quantize(const float *frame, uint64_t npix, void *rgba8, float *depth
 #include "vmx_motion.inc"
 // ... and for pixels on an analytic sphere that vmx_scene_set_spheres moved
 #include "vmx_motion_spheres.inc"
+// emissive triangles: the derived table the light-sampling integrator samples
+#include "vmx_emitters.inc"
 // light sampling: the path integrator with next-event estimation
 #include "vmx_nee.inc"
 

@@ -617,6 +617,23 @@ class Scene:
         self._check(self._lib.vmx_scene_set_spheres(self._h, sp, nsp))
         self._spheres = spheres
 
+    def set_emitters(self, ids=None, radiance=None):
+        """vmx_scene_set_emitters: the scene's emissive triangles — ids [n] (createBVH-order triangle ids) and radiance
+        [n, 3] (or one rgb for all of them); None or an empty list clears the table.  Only the light-sampled integrator
+        (render_nee, radiance_nee, progressive_nee, ...) sees it; progressive renders begun before it refuse further steps."""
+        tb, n = emitter_table(ids, radiance)
+        self._check(self._lib.vmx_scene_set_emitters(self._h, tb, n))
+
+    def emitters(self):
+        """vmx_scene_emitters: the derived table as an EMITTER_DTYPE array (tri_id, radiance, area, weight, cdf), in the
+        caller's order, from the scene's current triangle records"""
+        n = C.c_uint32(0)
+        self._check(self._lib.vmx_scene_emitters(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=EMITTER_DTYPE)
+        if n.value:
+            self._check(self._lib.vmx_scene_emitters(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     # -- moving geometry --------------------------------------------------------
     def update(self, pos=None, nrm=None, uv=None, rebuild=False, stream=None):
         """In-place update of the same triangles (vmx_scene_update / vmx_scene_update_device; semantics in
@@ -1164,6 +1181,11 @@ class MultiScene:
         c = 1 if data.ndim == 2 else data.shape[2]
         L.check(L.lib().vmx_multi_bind_texture(self._h, data.ctypes.data, data.shape[1], data.shape[0], c))
 
+    def set_emitters(self, ids=None, radiance=None):
+        """vmx_multi_set_emitters: Scene.set_emitters on every replica"""
+        tb, n = emitter_table(ids, radiance)
+        L.check(L.lib().vmx_multi_set_emitters(self._h, tb, n))
+
     def set_spheres(self, spheres=None):
         """vmx_multi_set_spheres: Scene.set_spheres on every replica"""
         sp, nsp = _sphere_table(spheres, "spheres")
@@ -1216,6 +1238,24 @@ class MultiScene:
         st = L.Stats()
         L.check(L.lib().vmx_multi_render_nee_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(d_out_ptr), C.byref(st)))
         return st.as_dict()
+
+
+EMITTER_DTYPE = np.dtype([("tri_id", np.uint32), ("radiance", np.float32, 3), ("area", np.float64), ("weight", np.float64),
+                          ("cdf", np.float64)])
+assert EMITTER_DTYPE.itemsize == C.sizeof(L.EmitterInfo) == 40
+
+
+def emitter_table(ids, radiance):
+    """(ctypes array of vmx_emitter or None, n) from ids [n] and radiance [n, 3] or [3]"""
+    if ids is None or len(ids) == 0:
+        return None, 0
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    rad = np.broadcast_to(np.asarray(radiance, np.float32).reshape(-1, 3), (ids.size, 3))
+    if ids.min() < 0 or ids.max() > 0xFFFFFFFF:
+        raise ValueError("emitter ids must be triangle ids")
+    rec = np.empty(ids.size, dtype=[("tri_id", np.uint32), ("radiance", np.float32, 3)])
+    rec["tri_id"], rec["radiance"] = ids, rad
+    return (L.Emitter * ids.size).from_buffer_copy(rec.tobytes()), ids.size
 
 
 RAYHIT_DTYPE = np.dtype([
