@@ -130,7 +130,7 @@ typedef struct vmx_opts {
                               claim; bit 14: bounce rays walk the reference tree alone, not the scene's guide tree),
                               [1] max paths per pass, [2] tail threshold, [3] refill_min, [4] shade_min,
                               [5] bounce reordering key (A/B library only), [6] LDS stack levels — all forms and
-                              settings produce the same frame (see api_render.inc: render_impl, make_tuning) */
+                              settings produce the same frame (see vmx_host.h: kForm*, api_render.inc: render_forms, make_tuning) */
 } vmx_opts;
 
 /* per-stage figures: `primary` = Radiance steps taken at depth 0 (the fused

@@ -115,7 +115,7 @@ def test_device_cosf_sinf_bit_exact():
     assert np.array_equal(bits(cs), bits(rcs)) and np.array_equal(bits(sn), bits(rsn))
 
 
-# Which kernels a call runs (api_render.inc: render_impl, run_ids):
+# Which kernels a call runs (api_render.inc: render_forms, render_pass and its pass_* by form, run_ids; pass_schedule.h):
 #   {}                                  default routing — a pass of < 4 M paths goes to the fused k_paths kernel,
 #                                       bounce generations of <= 16 M live paths to the fused tail (k_paths<2>)
 #   pipeline=4                          the production split wavefront for every pass: k_raygen, k_trace_w<0>

@@ -1,7 +1,7 @@
 """Per-pixel claims (pixel_claim.h) against the samples per pixel: the 1080p bench frame in the headline form at 16 ... 256
 spp, fixed count, claims forced on (the A/B library, `make ab`, reads VMX_CLAIM_MIN_SPP) against claims off (reserved[0] bit 11):
 device time of the frame, of the claim kernel and of the camera traversal, best of three.  The smallest spp at which
-"on" is not slower is the threshold kClaimMinSamples (api_render.inc)."""
+"on" is not slower is the threshold kClaimMinSamples (api_claims.inc)."""
 import os, sys
 os.environ.setdefault("VMX_CLAIM_MIN_SPP", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -15,7 +15,7 @@ int ab_check_forms(const vmx_scene *sc, uint32_t pipeline) {
 
 // vmx_opts.reserved[0] bit 10: the bounce generations of a pass through k_trace_pool
 int ab_check_pool(const vmx_opts *) { return VMX_OK; }
-bool ab_pool_bit(const vmx_opts *o) { return (o->reserved[0] & 0x400u) != 0; }
+bool ab_pool_bit(const vmx_opts *o) { return (o->reserved[0] & kFormPool) != 0; }
 
 // cap on the bounce kernel's blocks per CU (how much of its time is latency hiding: profiles/r04_state_pool.txt)
 int ab_bounce_blocks(int tbb) {
@@ -74,25 +74,25 @@ int legacy_occupancy(const vmx_scene *sc, bool count, int *pb, int *bb) {
 // render_bind of a frame in form 2 or 3: the two path queues and the kernels' blocks per CU
 int ab_bind_legacy(vmx_scene *sc, RenderJob &job) {
     if (int rc = ensure_queues(sc, job.sub_cap, job.q)) return rc;
-    return legacy_occupancy(sc, job.count, &job.pb, &job.bb);
+    return legacy_occupancy(sc, job.f.count, &job.pb, &job.bb);
 }
 
 // a pass of form 2 (k_primary, then k_bounce per generation) or 3 (k_primary follows every path to its end)
 int ab_legacy_pass(vmx_scene *sc, RenderJob &job, const unsigned int *act_cur, uint32_t n_active, uint32_t S) {
     Workspace &ws = sc->ws;
     hipStream_t s = job.s;
-    const bool mega = job.pipeline == 3;
+    const bool mega = job.f.pipeline == 3;
     const uint32_t n_pad = (n_active + 63u) & ~63u;
     const uint32_t tiles8 = (((n_pad + sc->block - 1) / sc->block) + 7u) & ~7u;
     if (!mega) HIP_TRY(hipMemsetAsync(job.q[0].counts, 0, kSubQueues * 32 * 4, s));
     LaunchCfg cfg = trace_cfg(sc, tiles8 * S, job.pb);
     int rc = timed_begin(ws, job.timed, s, 0, VMX_K_OTHER);
     if (rc) return rc;
-    LAUNCH_TRY(launch_primary(sc->dev, job.fr, act_cur, n_active, S, job.px, job.q[0], ws.rad.p, ws.counters.p, job.count, mega, cfg, s));
+    LAUNCH_TRY(launch_primary(sc->dev, job.fr, act_cur, n_active, S, job.px, job.q[0], ws.rad.p, ws.counters.p, job.f.count, mega, cfg, s));
     if ((rc = timed_end(job.timed, s))) return rc;
     job.launches += 2;
     if (mega) return VMX_OK;
-    return run_queue(sc, job.fr, job.q, 0, ws.rad.p, ws.counters.p, job.count, job.tn.tail_threshold, s, job.timed, job.launches, job.bb);
+    return run_queue(sc, job.fr, job.q, 0, ws.rad.p, ws.counters.p, job.f.count, job.tn.tail_threshold, s, job.timed, job.launches, job.bb);
 }
 
 // vmx_radiance in form 2 or 3: the workspace, then the path starts and their generations
@@ -188,7 +188,7 @@ int ab_check_forms(const vmx_scene *, uint32_t pipeline) {
 }
 
 int ab_check_pool(const vmx_opts *o) {
-    if (o->reserved[0] & 0x400u)
+    if (o->reserved[0] & kFormPool)
         return fail(VMX_ERR_INVALID, "k_trace_pool (vmx_opts.reserved[0] bit 10) is a probe of the A/B library (make ab): "
                                      "profiles/r04_state_pool.txt");
     return VMX_OK;
@@ -206,8 +206,8 @@ int ab_reorder(vmx_scene *, const Tuning &tn, bool, const IdQueue &, uint32_t, c
 }
 
 // (never reached: ab_check_forms has refused the forms, and ab_pool_bit leaves Tuning::pool off)
-int ab_bind_legacy(vmx_scene *sc, RenderJob &job) { return ab_check_forms(sc, job.pipeline); }
-int ab_legacy_pass(vmx_scene *sc, RenderJob &job, const unsigned int *, uint32_t, uint32_t) { return ab_check_forms(sc, job.pipeline); }
+int ab_bind_legacy(vmx_scene *sc, RenderJob &job) { return ab_check_forms(sc, job.f.pipeline); }
+int ab_legacy_pass(vmx_scene *sc, RenderJob &job, const unsigned int *, uint32_t, uint32_t) { return ab_check_forms(sc, job.f.pipeline); }
 int ab_radiance_setup(vmx_scene *sc, uint32_t, bool, QueueDev *, int *) { return ab_check_forms(sc, 2); }
 int ab_radiance_enqueue(vmx_scene *sc, const FrameDev &, QueueDev *, const float *, const float *, uint32_t, uint64_t, bool, uint32_t,
                         hipStream_t, std::vector<TimedLaunch> &, uint64_t &, int) {

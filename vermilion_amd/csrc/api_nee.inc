@@ -23,6 +23,43 @@ int nee_check_opts(const vmx_opts *o, bool ranks = false) {
     return VMX_OK;
 }
 
+// The derived table of the scene's emissive triangles (vmx_scene_set_emitters), current for a launch on `s`: rebuilt from
+// the records the scene holds NOW when the generation moved since it was derived — an update rewrote or permuted them,
+// a new table came — and then fenced, since the next launch may run on another stream.  sc->em.dev.n == 0: no table.
+int nee_emitters(vmx_scene *sc, hipStream_t s) {
+    auto &em = sc->em;
+    const uint32_t n = (uint32_t)em.table.size();
+    if (n == 0) {
+        em.dev = EmitDev{};
+        return VMX_OK;
+    }
+    if (em.built != sc->generation) {
+        if (int rc = sc->upd.done.wait(s)) return rc;
+        if (em.rec.ensure(n) || em.area.ensure(n) || em.weight.ensure(n) || em.cdf.ensure(n) || em.slot_em.ensure(sc->ntris) ||
+            em.id_em.ensure(sc->ntris))
+            return fail(VMX_ERR_NOMEM, "hipMalloc failed for the emitter table");
+        em.dev = EmitDev{em.rec.p, em.area.p, em.weight.p, em.cdf.p, em.slot_em.p, n};
+        LAUNCH_TRY(launch_emitter_table(sc->dev.tris, sc->ntris, em.ids.p, em.radiance.p, em.id_em.p, em.dev, s));
+        if (int rc = em.done.record(s)) return rc;
+        em.built = sc->generation;
+        em.builds++;
+    }
+    return em.done.wait(s);
+}
+
+// the stack and the persistent grid of a k_nee launch over `items` work items on `s`; the scene's emitter table is made
+// current first (sc->em.dev is what launch_nee then takes).  (budgeted defaults to false: api_render.inc declares it, for pass_nee)
+int nee_launch_cfg(vmx_scene *sc, hipStream_t s, const Tuning &tn, uint64_t items, bool rays, WorkDev &wk, LaunchCfg &cfg,
+                   bool budgeted) {
+    if (int rc = nee_emitters(sc, s)) return rc;
+    int blocks = 0;
+    HIP_TRY((hipError_t)query_nee_blocks_per_cu(kPathsBlock, (kPathsBlock / 64) * (tn.lds_entries + 1) * 512, rays, &blocks, budgeted,
+                                                sc->em.dev.n != 0));
+    if (blocks < 1) return fail(VMX_ERR_HIP, "kernel does not fit on a CU (LDS stack too deep?)");
+    cfg = paths_cfg(sc, tn.lds_entries, items, blocks);
+    return bind_stack(sc, tn, tn.lds_entries, cfg.grid, items, wk);
+}
+
 // One frame: vmx_render's set-up and pass loop (render_run), whose passes run their paths in k_nee (RenderJob::nee) — the
 // routine a light-sampled progressive handle steps through
 int nee_render_impl(vmx_scene *sc, const vmx_camera *cam, const vmx_opts *opts, float *d_out, hipStream_t s, vmx_stats *stats) {
@@ -95,25 +132,17 @@ int radiance_nee_run(vmx_scene *sc, const float *d_o, const float *d_d, uint32_t
     fr.libm_double = (opts->sampling & VMX_SAMPLING_LIBM_DOUBLE) ? 1u : 0u;
     fr.seed = opts->seed;
     if (ws.heads.ensure(kSubQueues * 32) || ws.counters.ensure(1)) return fail(VMX_ERR_NOMEM, "hipMalloc failed");
-    WorkDev wk;
-    std::memset(&wk, 0, sizeof(wk));
-    wk.heads = ws.heads.p;
+    WorkDev wk = make_work(ws.heads.p, nullptr);
     LaunchCfg cfg;
     if ((rc = nee_launch_cfg(sc, s, tn, n, true, wk, cfg))) return rc;
-    ws.events.reset();
+    CallScope call{sc, s, t0};
     std::vector<TimedLaunch> timed;
-    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
-    if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(ev0, s));
-    HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
-    if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
-    if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+    if ((rc = call.open()) || (rc = call.start()) || (rc = call.clear_counters())) return rc;
     HIP_TRY(hipMemsetAsync(ws.heads.p, 0, 4, s));
     if ((rc = timed_begin(ws, timed, s, 0, VMX_K_OTHER))) return rc;
     LAUNCH_TRY(launch_nee(sc->dev, fr, wk, PixelStateDev{nullptr, nullptr, nullptr}, d_o, d_d, n, d_out4, ws.counters.p, cfg, s, sc->em.dev));
     if ((rc = timed_end(timed, s))) return rc;
-    HIP_TRY(hipEventRecord(ev1, s));
-    rc = finish_stats(sc, s, timed, ev0, ev1, stats, 1, 1, t0);
+    rc = call.finish(timed, stats, 1, 1);
     if (rc == VMX_OK && stats) stats->samples = n;
     return rc;
 }

@@ -16,7 +16,7 @@ struct VMX_OPAQUE vmx_progressive {
     uint64_t generation = 0;        // the scene's when the handle began
     uint64_t samples = 0, passes = 0, steps = 0;
     bool failed = false;            // a step stopped half way: the schedule and the device state may disagree
-    // adaptive sampling (api_sampling.inc).  From the first selected step on the handle is ragged (job.ragged): `master` is
+    // adaptive sampling (api_sampling.inc).  From the first selected step on the handle is ragged (job.sched.ragged): `master` is
     // the list of its active pixels in the tile order of render_init_pixels, compacted in order after every step; a step
     // compacts it by its selection into the job's active list and runs the pass loop on that
     DevBuf<unsigned int> master[2];
@@ -109,7 +109,7 @@ int vmx_progressive_step(vmx_progressive *p, uint32_t samples, vmx_stats *stats)
     if (int rc = bind_device(sc)) return rc;
     if (p->generation != sc->generation) return fail(VMX_ERR_INVALID, "scene updated since vmx_progressive_begin");
     if (p->failed) return fail(VMX_ERR_INVALID, "an earlier step of this handle failed: end it and begin again");
-    if (p->job.ragged) return progressive_step_list(p, samples, nullptr, stats, nullptr, t0);
+    if (p->job.sched.ragged) return progressive_step_list(p, samples, nullptr, stats, nullptr, t0);
     vmx_stats st;
     std::memset(&st, 0, sizeof(st));
     if (p->job.n_active > 0) {

@@ -353,23 +353,24 @@ int vmx_radiance(const vmx_scene *csc, const float *origin, const float *dir, ui
     if ((opts->sampling & VMX_SAMPLING_MODE_MASK) > VMX_SAMPLING_CORRECTED ||
         (opts->sampling & ~(VMX_SAMPLING_MODE_MASK | VMX_SAMPLING_LIBM_DOUBLE | VMX_SAMPLING_ELIDE_DEAD)))
         return fail(VMX_ERR_INVALID, "unknown sampling mode");
-    // (bits 8-10 of reserved[0] select shading / traversal forms of vmx_render's split passes and mean nothing here:
-    // accepted and ignored, as render_impl accepts them)
-    const uint32_t pipeline = opts->reserved[0] & 0xFFu;
-    if (pipeline > 4 || (opts->reserved[0] & ~0x7FFu)) return fail(VMX_ERR_INVALID, "unknown pipeline form");
-    if (int rc = ab_check_forms(sc, pipeline)) return rc;
+    // (kFormsRadiance, vmx_host.h: the bits of reserved[0] that select shading forms of vmx_render's split passes mean
+    // nothing here and are accepted and ignored, as render_setup accepts them)
+    Forms f;
+    f.pipeline = opts->reserved[0] & kFormPipeline;
+    if (f.pipeline > 4 || (opts->reserved[0] & ~kFormsRadiance)) return fail(VMX_ERR_INVALID, "unknown pipeline form");
+    if (int rc = ab_check_forms(sc, f.pipeline)) return rc;
     if (n == 0) return VMX_OK;
-    const auto t0 = std::chrono::steady_clock::now();
+    CallScope call{sc, sc->stream, std::chrono::steady_clock::now()};
     std::lock_guard<std::mutex> lock(sc->mu);
     int rc = bind_device(sc);
     if (rc) return rc;
     Workspace &ws = sc->ws;
     hipStream_t s = sc->stream;
     if ((rc = sc->upd.done.wait(s))) return rc;
-    const bool count = opts->collect_counters != 0;
-    const bool legacy = pipeline == 2 || pipeline == 3;  // first-generation kernels (A/B library)
-    Tuning tn = make_tuning(sc, opts);
-    tn.pool = ab_pool_bit(opts) && !count;  // the phase-pure probe (vmx_trace_pool.inc)
+    const bool count = f.count = opts->collect_counters != 0;
+    const bool legacy = f.legacy = f.pipeline == 2 || f.pipeline == 3;  // first-generation kernels (A/B library)
+    const Tuning tn = make_tuning(sc, opts);
+    f.pool = ab_pool_bit(opts) && !count;  // the phase-pure probe (vmx_trace_pool.inc)
     FrameDev fr;
     std::memset(&fr, 0, sizeof(fr));
     fr.r2scale = (opts->sampling & VMX_SAMPLING_MODE_MASK) == VMX_SAMPLING_CORRECTED ? 1.0f : 10.0f;
@@ -392,30 +393,26 @@ int vmx_radiance(const vmx_scene *csc, const float *origin, const float *dir, ui
     }
     DevBuf<float> d_o, d_d;
     if (d_o.ensure((size_t)n * 3) || d_d.ensure((size_t)n * 3)) return fail(VMX_ERR_NOMEM, "hipMalloc failed");
-    ws.events.reset();
     std::vector<TimedLaunch> timed;
     uint64_t launches = 0;
-    hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
+    if ((rc = call.open())) return rc;
     auto body = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_o.p, origin, (size_t)n * 12, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_d.p, dir, (size_t)n * 12, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ev0, s));
-        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
-        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
-        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
         int r;
+        if ((r = call.start()) || (r = call.clear_counters())) return r;
         if (legacy) {
             r = ab_radiance_enqueue(sc, fr, q, d_o.p, d_d.p, n, opts->seed, count, tn.tail_threshold, s, timed, launches, bb);
         } else {
             HIP_TRY(hipMemsetAsync(qi[0].counts, 0, kSubQueues * 32 * 4, s));
             LAUNCH_TRY(launch_radiance_init_ids(d_o.p, d_d.p, n, opts->seed, pa, qi[0], (uint32_t)sc->num_cus, s));
             launches += 2;
-            r = run_ids(sc, fr, pa, qi, 0, ws.counters.p, count, tn, s, timed, launches, tb, rb);
+            r = run_ids(sc, fr, pa, qi, 0, ws.counters.p, f, tn, s, timed, launches, tb, rb);
         }
         if (r) return r;
-        HIP_TRY(hipEventRecord(ev1, s));
+        if ((r = call.stop())) return r;
         HIP_TRY(hipMemcpyAsync(out, ws.rad.p, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-        return finish_stats(sc, s, timed, ev0, ev1, stats, launches, 1, t0);
+        return call.finish(timed, stats, launches, 1);
     };
     rc = body();
     if (rc) (void)hipStreamSynchronize(s);  // (what was enqueued may still use d_o / d_d, which are freed here)

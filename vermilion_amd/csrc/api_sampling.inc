@@ -66,7 +66,7 @@ static int progressive_make_ragged(vmx_progressive *p) {
     if (job.n_active)
         HIP_TRY(hipMemcpyAsync(p->master[0].p, job.pixels->active[job.cur_list].p, (size_t)job.n_active * 4, hipMemcpyDeviceToDevice, job.s));
     p->cur_master = 0, p->n_master = job.n_active;
-    job.ragged = true;
+    job.sched.ragged = true;
     return VMX_OK;
 }
 
@@ -82,7 +82,7 @@ static int progressive_step_list(vmx_progressive *p, uint32_t samples, const uns
         if (selected) *selected = 0;
         return VMX_OK;
     }
-    if (!job.ragged)
+    if (!job.sched.ragged)
         if (int rc = progressive_make_ragged(p)) return rc;
     uint32_t n_sel = 0;
     int rc = progressive_compact(p, p->master[p->cur_master].p, p->n_master, d_select, job.pixels->active[job.cur_list].p, &n_sel);
@@ -241,7 +241,7 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
     uint32_t n_sel = 0;
     auto body = [&]() -> int {
         if (job.npix == 0) return VMX_OK;
-        if (!job.ragged)
+        if (!job.sched.ragged)
             if (int rc = progressive_make_ragged(p)) return rc;
         const uint32_t n_master = p->n_master;
         if (n_master == 0) return VMX_OK;
@@ -270,19 +270,14 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
         if (n_sel > n_master || items < n_sel || (uint64_t)items > (uint64_t)job.n_pad_max * job.smax)
             return fail(VMX_ERR_HIP, "budgeted step: the item scan does not fit the pass's workspace");
         // the pass: k_nee over the items, k_resolve_budget over the list
-        ws.events.reset();
+        CallScope call{sc, s, t0};
         job.timed.clear();
         job.passes = 0;
-        hipEvent_t ev0 = ws.events.get(), ev1 = ws.events.get();
-        if (!ev0 || !ev1) return fail(VMX_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(ev0, s));
+        if (int rc = call.open()) return rc;
+        if (int rc = call.start()) return rc;
         if (int rc = render_bind(sc, job, 0)) return rc;
-        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
-        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
-        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
-        WorkDev wk;
-        std::memset(&wk, 0, sizeof(wk));
-        wk.heads = ws.heads.p;
+        if (int rc = call.clear_counters()) return rc;
+        WorkDev wk = make_work(ws.heads.p, nullptr);
         wk.active = act;
         wk.n_active = n_sel, wk.n_pad = (n_sel + 63u) & ~63u, wk.samples = 1, wk.div_samples = make_fastdiv(1);
         wk.pixel_major = 1;
@@ -301,8 +296,7 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
         job.launches += 2;
         job.passes = 1;
         job.frame_passes++;
-        HIP_TRY(hipEventRecord(ev1, s));
-        int rc = finish_stats(sc, s, job.timed, ev0, ev1, &st, job.launches, job.passes, t0);
+        int rc = call.finish(job.timed, &st, job.launches, job.passes);
         job.launches = 0;
         if (rc) return rc;
         // the master list without the pixels this step completed, in order
@@ -318,7 +312,7 @@ static int progressive_step_budget(vmx_progressive *p, const unsigned int *d_bud
         (void)hipGetLastError();
         return rc;
     }
-    if (job.ragged) job.n_active = p->n_master;
+    if (job.sched.ragged) job.n_active = p->n_master;
     if (stats) *stats = st;
     if (selected) *selected = n_sel;
     return VMX_OK;

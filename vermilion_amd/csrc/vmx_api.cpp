@@ -29,6 +29,7 @@
 #include "vmx_device.h"
 #include "vmx_kernels.h"
 #include "pixel_claim.h"  // kListWords
+#include "pass_schedule.h"  // plan_pass, pass_form: the pure decisions of render_pass
 
 #ifndef VMX_LDS_PRIMARY
 #define VMX_LDS_PRIMARY 8  // LDS stack levels of the camera-ray kernel (A/B builds: make EXTRA=-DVMX_LDS_PRIMARY=n)
@@ -39,8 +40,11 @@ using namespace vmx;
 // The parts, one per family of entries:
 #include "vmx_host.h"          // shared: error reporting, the owners of device resources, the scene and its workspace, frame set-up
 #include "api_ab.inc"          // what only the A/B library runs, behind ab_* hooks (the host side's one VMX_AB_KERNELS conditional)
-#include "api_render.inc"      // the pass loop, BruteForceTracer; vmx_render*, vmx_local_rows
-#include "api_nee.inc"         // light sampling: vmx_render_nee*, vmx_radiance_nee
+#include "api_guide.inc"       // the guided bounce generation; vmx_guide_rays, vmx_guide_fused_rays, vmx_guide_list_entries, vmx_guide_trace*
+#include "api_claims.inc"      // per-pixel claims and list claims; vmx_pixel_claims, vmx_pixel_claim_lists, vmx_list_settled_rays, vmx_fused_camera_paths
+#include "api_render.inc"      // the pass loop by form (its schedule: pass_schedule.h); vmx_render*, vmx_local_rows
+#include "api_nee.inc"         // light sampling: the emitter table, vmx_render_nee*, vmx_radiance_nee
+#include "api_bruteforce.inc"  // BruteForceTracer: vmx_render_bruteforce*
 #include "api_scene.inc"       // vmx_scene_create / destroy / bind_texture / describe / timings / bvh
 #include "api_query.inc"       // vmx_trace, vmx_raycast*, vmx_query*, vmx_primary_ids, vmx_radiance, vmx_trig
 #include "api_image.inc"       // shared by the image-space entries below: handle, overlap and params checks; vmx_variance_default_params

@@ -425,6 +425,47 @@ int timed_end(std::vector<TimedLaunch> &timed, hipStream_t s) {
     return VMX_OK;
 }
 
+int finish_stats(vmx_scene *sc, hipStream_t s, std::vector<TimedLaunch> &timed, hipEvent_t ev0, hipEvent_t ev1, vmx_stats *stats,
+                 uint64_t launches, uint64_t passes, std::chrono::steady_clock::time_point t0);  // api_render.inc
+
+// One timed call on a scene's workspace.  open: the event pool starts over and the call's two events are taken; start /
+// stop: ev0 / ev1 go on the stream — stats->ms_device is what lies between them, and each entry decides where that is
+// relative to its own copies; clear_counters: the three device counters a call's statistics are read from; finish: stop,
+// unless the entry already has, then finish_stats waits for the stream and reads them.
+struct CallScope {
+    vmx_scene *sc;
+    hipStream_t s;
+    std::chrono::steady_clock::time_point t0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool stopped = false;
+    int open() {
+        sc->ws.events.reset();
+        ev0 = sc->ws.events.get(), ev1 = sc->ws.events.get();
+        return ev0 && ev1 ? VMX_OK : fail(VMX_ERR_HIP, "hipEventCreate failed");
+    }
+    int start() {
+        HIP_TRY(hipEventRecord(ev0, s));
+        return VMX_OK;
+    }
+    int clear_counters() {
+        Workspace &ws = sc->ws;
+        HIP_TRY(hipMemsetAsync(ws.counters.p, 0, sizeof(DevCounters), s));
+        if (ws.guide_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_ctr.p, 0, 16, s));
+        if (ws.guide_fused_ctr.p) HIP_TRY(hipMemsetAsync(ws.guide_fused_ctr.p, 0, 16, s));
+        return VMX_OK;
+    }
+    int stop() {
+        HIP_TRY(hipEventRecord(ev1, s));
+        stopped = true;
+        return VMX_OK;
+    }
+    int finish(std::vector<TimedLaunch> &timed, vmx_stats *stats, uint64_t launches, uint64_t passes) {
+        if (!stopped)
+            if (int rc = stop()) return rc;
+        return finish_stats(sc, s, timed, ev0, ev1, stats, launches, passes, t0);
+    }
+};
+
 // reads the 16 sub-queue tails; returns total and the largest
 int read_counts(vmx_scene *sc, unsigned int *d_counts, hipStream_t s, uint64_t &total, uint32_t &largest,
                 uint32_t sub_capacity = 0xffffffffu, uint32_t *per_queue = nullptr) {
@@ -448,16 +489,49 @@ struct Tuning {
     uint32_t refill_min, refill_primary, shade_min, leaf_min, tail_threshold;
     uint32_t lds_entries, lds_primary, lds_bounce;  // LDS stack levels: fused kernels, camera-ray trace, bounce trace
     uint32_t sort_mode;  // bounce reordering: obits | dbits << 4 | dir_major << 8 | chunk_log2 << 12 | shade_sorted << 20
-    bool two_phase;      // split passes of vmx_render: k_shade_ends + k_shade on what it queues (render_impl)
-    bool sorted;         // ... and the camera rays sorted by the trace kernel itself (k_trace_w<0, .., SORT>): no k_shade_ends
-    bool bounce_records; // one-phase shading of a render pass's bounce generations: the traversal kernel hands every ray on as a
-                         // dense (t, leaf slot, path id) record (k_trace_w<1, .., SORT> with WorkDev::keep_all) instead of a
-                         // scattered 8-byte hit[pid] store that k_shade<1> then gathers — same shading, every ray a full RayCast
-    bool pool;           // A/B library, reserved[0] bit 10: the bounce generations of a pass through k_trace_pool (phase-pure
-                         // steps, ray state in LDS; profiles/r04_state_pool.txt) — unsorted passes only
-    bool guide;          // the bounce generations of a render pass walk the scene's guide tree (k_trace_w<1, .., GUIDE>, guide_walk.h)
-                         // and a second launch of today's kernel traces the fallback list: a reference-tree scene with a valid
-                         // guide; not the counting build, the A/B pool or reserved[0] bit 14
+};
+
+// the WorkDev every launch site starts from: zeroed, the work heads, and with a tuning its refill and shade thresholds
+WorkDev make_work(unsigned int *heads, const Tuning *tn) {
+    WorkDev wk;
+    std::memset(&wk, 0, sizeof(wk));
+    wk.heads = heads;
+    if (tn) wk.refill_min = tn->refill_min, wk.shade_min = tn->shade_min;
+    return wk;
+}
+
+// ---- vmx_opts.reserved[0]: the pipeline form in the low byte, above it the switches the host reads --------------------
+constexpr uint32_t kFormPipeline = 0xFFu;      // the pipeline form, 0..4 (render_forms)
+constexpr uint32_t kFormOnePhase = 1u << 8;    // one-phase shading of the split passes: no k_shade_ends (Forms::two_phase)
+constexpr uint32_t kFormKeepEnds = 1u << 9;    // the camera rays keep k_shade_ends: the trace kernel does not sort them (Forms::sorted)
+constexpr uint32_t kFormPool = 1u << 10;       // A/B library: bounce generations through k_trace_pool (Forms::pool)
+constexpr uint32_t kFormNoClaims = 1u << 11;   // no per-pixel claims (Forms::claims_on)
+constexpr uint32_t kFormNoFuse = 1u << 12;     // claimed pixels are not fused into k_shade<0> (Forms::fuse_on)
+constexpr uint32_t kFormNoLists = 1u << 13;    // no list claims (Forms::lists_on)
+constexpr uint32_t kFormNoGuide = 1u << 14;    // bounce rays keep the reference tree (Forms::guide)
+// The bits vmx_render accepts: all of them.
+constexpr uint32_t kFormsRender = kFormPipeline | kFormOnePhase | kFormKeepEnds | kFormPool | kFormNoClaims | kFormNoFuse | kFormNoLists | kFormNoGuide;
+// The bits vmx_radiance accepts: it has no camera pass and never walks the guide, so the switches of the claims and of the
+// guide (bits 11-14) name nothing it runs and are refused as unknown; bits 8-9 are older than that rule — accepted and
+// ignored, so that one vmx_opts serves a frame and the rays that check it — and bit 10 selects its traversal (Forms::pool).
+constexpr uint32_t kFormsRadiance = kFormPipeline | kFormOnePhase | kFormKeepEnds | kFormPool;
+
+// what a call derives from those bits and its frame (render_forms: one statement per member, with the reasons)
+struct Forms {
+    uint32_t pipeline = 0;
+    bool count = false;           // the counting build (vmx_opts.collect_counters)
+    bool split_any = false, legacy = false;
+    bool two_phase = false;       // split passes: k_shade_ends + k_shade on what it queues
+    bool sorted = false;          // ... and the camera rays sorted by the trace kernel itself (k_trace_w<0, .., SORT>): no k_shade_ends
+    bool pool = false;            // A/B library: the bounce generations of a pass through k_trace_pool — unsorted passes only
+    bool guide = false;           // bounce generations walk the scene's guide tree (k_trace_w<1, .., GUIDE>, guide_walk.h), a second
+                                  // launch traces the fallback list; the fused launches are k_paths' GUIDE forms
+    bool bounce_records = false;  // one-phase shading: the traversal kernel hands every bounce ray on as a dense (t, leaf slot, path id)
+                                  // record (k_trace_w<1, .., SORT> with WorkDev::keep_all) instead of a scattered hit[pid] store
+    bool elide = false;           // camera paths of the split passes: compacted live list (VMX_SAMPLING_ELIDE_DEAD)
+    bool claims_on = false;       // split passes may use per-pixel claims (pixel_claim.h)
+    bool fuse_on = false;         // ... and a dense plain camera pass fuses its claimed pixels into k_shade<0>
+    bool lists_on = false;        // ... and the pixels without a claim get list claims
 };
 
 constexpr uint32_t kPathsBlock = 256;
@@ -472,14 +546,11 @@ struct RenderJob {
     FrameDev fr;
     vmx_opts opts;
     Tuning tn;
-    uint32_t npix = 0, pipeline = 0;
-    bool count = false, split_any = false, legacy = false, elide = false;
+    Forms f;
+    uint32_t npix = 0;
     // the light-sampling integrator (api_nee.inc; set by the caller right after render_setup): a pass's paths run in k_nee,
     // whatever the pipeline form, and a run binds only what that kernel and k_resolve use
     bool nee = false;
-    bool claims_on = false;  // split passes may use per-pixel claims (pixel_claim.h): not counting, not eliding, reserved[0] bit 11 clear
-    bool lists_on = false;   // ... and the pixels without a claim get list claims (reserved[0] bit 13 clear)
-    bool fuse_on = false;    // ... and a dense plain camera pass fuses its claimed pixels into k_shade<0> (reserved[0] bit 12 clear)
     uint32_t smax = 0, smax_alloc = 0;  // samples per pixel and pass: the most a pass takes / what the buffers are sized for
     uint32_t n_pad_max = 0, sub_cap = 0;
     uint64_t mem_budget = 0;
@@ -499,14 +570,9 @@ struct RenderJob {
     bool initialised = false;  // the tile-ordered pixel list is uploaded and the per-pixel state zeroed
     uint32_t n_active = 0;
     int cur_list = 0;
-    uint32_t n_uniform = 0;  // samples every active pixel has taken while no early stop was possible
-    uint32_t k_fixed = 0;    // fixed-spp mode: samples issued so far
-    // a progressive handle after its first selected step (api_sampling.inc): its pixels hold different counts, k_fixed means
-    // nothing any more, a pass takes min(smax, cap) samples and the kernels' k < kmax clipping ends each pixel on its own
-    bool ragged = false;
+    PassSchedule sched;      // pass_schedule.h: what plan_pass advances, and `ragged`
     bool moments = false;    // k_resolve<true>: accum.w carries the sum of squared luminances (VMX_PROGRESSIVE_MOMENTS)
-    uint64_t last_pass_pixels = 0, last_pass_breaks = 0;  // early-stop statistics of the previous pass
-    uint64_t frame_passes = 0;                            // passes since set-up
+    uint64_t frame_passes = 0;  // passes since set-up
     // the current run
     std::vector<TimedLaunch> timed;
     uint64_t launches = 0, passes = 0;
